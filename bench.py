@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: BBS+ proof_verify/s, BLS12-381, 32 messages / 8 disclosed, batch 4096 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
     python bench.py --config mixed65536 [--gpus N]     # BASELINE configs[4]: 65 536 mixed BN254 + BLS12-381 proofs
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else the bench
+measures: a longer timed region when the K steps are short, HIP events around every stage of the timed steps with the
+roofline and VALU-issue figures priced from them, the rate from resident batches, the other operations and the second
+curve (bench_extras.py) and the CPU baseline.  --dump-outputs DIR writes the statuses of the last timed steps (rank 0)
+as float32 .npy files, so that two builds can be compared output for output on the same seeded inputs.
 
 A step = one pass of core_proof_verify (src/proof_verify.rs:64-116) over one batch of 4096 proofs handed over in HOST
 buffers (BASELINE.json configs[3]; the proofs are produced untimed by the engine's own sign -> proof_gen).  The timed
@@ -17,9 +23,9 @@ Every in-flight slot holds a DIFFERENT batch (item ids offset by slot and by ran
 corrupted (one commitment incremented), and the statuses of every timed step are compared with the expected pattern
 after the timed region: a kernel that did nothing cannot pass (undecided items make bbs_job_wait fail).
 
-Timing: barrier + synchronize, K steps, barrier + synchronize; wall time = max over ranks.  HIP events around every
-stage of every timed step (recorded on the stream the stage is launched on) give the per-kernel durations of the same
-timed region.  Prints ONE JSON line (rank 0).
+Timing: barrier + synchronize, K steps, barrier + synchronize; wall time = max over ranks.  With --full, HIP events
+around every stage of every timed step (recorded on the stream the stage is launched on) give the per-kernel durations
+of the same timed region.  Prints ONE JSON line (rank 0).
 """
 import os
 
@@ -107,12 +113,13 @@ def make_slots(pc, suite, eng, n, L, R, n_slots, first_item, corrupt_slot=1):
     return slots, raw0
 
 
-def submit_loop(eng, slots, steps, inflight, first_step=0, collect_times=False, fifo=False):
+def submit_loop(eng, slots, steps, inflight, first_step=0, collect_times=False, fifo=False, results=None):
     """The serving loop of one submitting thread: step k submits slot k % len(slots); at most `inflight` jobs are
     outstanding; every job's statuses are read.  Jobs are retired in COMPLETION order (bbs_jobs_wait_any: the thread sleeps
     until whichever outstanding job finishes first, reads its statuses and submits the next batch in its place) -- waiting
     for the oldest job instead (fifo=True, round 3's loop, kept for the A/B) makes jobs submitted together finish together
-    and the loop run in convoys.  Returns (#status mismatches, {stage: summed ms}, summed job ms)."""
+    and the loop run in convoys.  `results` (a dict) receives {step: statuses} of the last `inflight` steps.
+    Returns (#status mismatches, {stage: summed ms}, summed job ms)."""
     from bbs_sign_amd import Job
     pending, bad = [], 0
     stage_ms, job_ms = {}, 0.0
@@ -121,11 +128,13 @@ def submit_loop(eng, slots, steps, inflight, first_step=0, collect_times=False, 
         nonlocal bad, job_ms
         if fifo:
             k = 0
-            pending[0][1].wait()                     # raises if any item was left undecided (BBS_E_STATE)
+            pending[0][2].wait()                     # raises if any item was left undecided (BBS_E_STATE)
         else:
-            k = Job.wait_any([j for _, j in pending])
-        slot, job = pending.pop(k)
+            k = Job.wait_any([j for _, _, j in pending])
+        step, slot, job = pending.pop(k)
         bad += int((job.result != slot.expect).sum())
+        if results is not None and step >= first_step + steps - inflight:
+            results[step] = job.result
         if collect_times:
             tot, st = job.stage_times()
             job_ms += tot
@@ -137,7 +146,7 @@ def submit_loop(eng, slots, steps, inflight, first_step=0, collect_times=False, 
         if len(pending) >= inflight:
             retire()
         slot = slots[k % len(slots)]
-        pending.append((slot, eng.submit_packed(slot.n, slot.args)))
+        pending.append((k, slot, eng.submit_packed(slot.n, slot.args)))
     while pending:
         retire()
     return bad, stage_ms, job_ms
@@ -196,10 +205,14 @@ def main():
                     "hardware queue of their own, independent of GPU_MAX_HW_QUEUES (for processes whose first HIP call precedes the library)")
     ap.add_argument("--fifo-retire", action="store_true", help="A/B: wait for the OLDEST outstanding job (round 3's loop) instead of "
                     "bbs_jobs_wait_any's completion order")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed sign/verify/proof_gen/BN254 figures")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: long region, stage events, "
+                    "roofline and VALU-issue figures, resident rate, other operations and curves, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the statuses of the last timed step (status.npy, "
+                    "[batch]) and of the last --inflight timed steps (status_last_round.npy, [steps, batch]) as float32, rank 0")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the untimed sign/verify/proof_gen/BN254 figures")
     ap.add_argument("--fixed-base-tree", type=int, default=None, help="A/B: bbs_ctx_set_fixed_base_tree on (1) / off (0); default = the library's")
-    ap.add_argument("--no-stage-timing", action="store_true", help="no HIP events in the timed region (A/B of their cost)")
+    ap.add_argument("--no-stage-timing", action="store_true", help="--full: no HIP events in the timed region (A/B of their cost)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                     "the N > 1 path on a box with fewer GPUs than ranks)")
     ap.add_argument("--all-ranks-on-device", type=int, default=None, help="rehearsal only: every rank uses this GPU")
@@ -210,9 +223,11 @@ def main():
                     "instead of one process per GPU and an all_gather")
     ap.add_argument("--pool-devices", default=None, help="--single-process: comma-separated member device ids (default 0 .. --gpus - 1; an "
                     "id may repeat: two members on one GPU)")
-    ap.add_argument("--min-region-s", type=float, default=1.0, help="if the K timed steps last less than this, a second, "
+    ap.add_argument("--min-region-s", type=float, default=1.0, help="--full: if the K timed steps last less than this, a second, "
                     "longer region of the same loop is timed and reported beside `value` as `long_region` (0 = off)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "proof_verify_4096":
+        raise SystemExit("bench.py: --dump-outputs goes with the headline config (proof_verify_4096)")
 
     if args.single_process:
         if args.config != "mixed65536":
@@ -288,23 +303,32 @@ def main():
     # every rank and every slot verifies its own batch: item ids offset by rank and slot
     slots, raw0 = make_slots(pc, suite, eng, n, L, R, n_slots, first_item=rank * n_slots * n)
     msgs, disclosed, rnds, sigs, proofs, dm = raw0
-    eng.set_stage_timing(not args.no_stage_timing)
+    stage_timing = args.full and not args.no_stage_timing
+    eng.set_stage_timing(stage_timing)
 
     bad, _, _ = submit_loop(eng, slots, max(args.warmup, n_slots), n_slots, fifo=args.fifo_retire)
     assert bad == 0, "warm-up statuses differ from the expected pattern"
 
+    results = {} if args.dump_outputs else None
     barrier()
     t0 = time.perf_counter()
-    bad, stage_ms, job_ms = submit_loop(eng, slots, args.steps, n_slots, first_step=0, collect_times=not args.no_stage_timing, fifo=args.fifo_retire)
+    bad, stage_ms, job_ms = submit_loop(eng, slots, args.steps, n_slots, first_step=0, collect_times=stage_timing, fifo=args.fifo_retire,
+                                        results=results)
     barrier()
     dt = time.perf_counter() - t0
     assert bad == 0, "timed statuses differ from the expected pattern (%d items)" % bad
     eng.set_stage_timing(False)
     passed = sum(int((slots[k % n_slots].expect == 1).sum()) for k in range(args.steps))
+    if results and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = np.stack([results[k] for k in sorted(results)]).astype(np.float32)
+        np.save(os.path.join(args.dump_outputs, "status.npy"), last[-1])
+        np.save(os.path.join(args.dump_outputs, "status_last_round.npy"), last)
     # the K steps the driver asked for may last a few tens of milliseconds, of which filling and draining the
     # `inflight` slots is a visible share: time the same loop once more over a region of at least --min-region-s
     long_region = None
-    if args.min_region_s > 0 and dt < args.min_region_s:
+    if args.full and args.min_region_s > 0 and dt < args.min_region_s:
         k2 = int(min(4096, max(args.steps, args.min_region_s / (dt / args.steps) * 1.1)))
         barrier()
         t1 = time.perf_counter()
@@ -318,9 +342,9 @@ def main():
     slots_data = [(proofs, dm, disclosed)]
     res_rate, res_stage, single = resident_rate(eng, slots_data * n_slots, n, max(32, args.steps // 2), n_slots,
                                                 args.latency_mode if args.latency_mode in (0, 1) else None) \
-        if rank == 0 else (None, None, None)
+        if rank == 0 and args.full else (None, None, None)
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         from bench_extras import other_ops
         extras = other_ops(args, pc, eng, suite, n, L, R, msgs, disclosed, rnds, sigs, proofs, dm, local_rank, submit_loop, make_slots, slots)
 
@@ -338,10 +362,6 @@ def main():
 
     if rank == 0:
         value = world * n * args.steps / dt
-        counters, counters_file = load_counters()
-        lib_hash = eng.lib.bbs_source_hash().decode()
-        counters_hash = (counters or {}).get("library_source_hash")
-        counters_current = (counters_hash == lib_hash) if counters_hash else None
         out = {
             "metric": "BBS+ proof_verify/sec (BLS12-381, 32-msg)",
             "value": value, "unit": "proof_verify/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -349,34 +369,40 @@ def main():
             "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": "BLS12-381 core_proof_verify, batch %d per GPU, 32 msgs / 8 disclosed, empty "
                                    "header/ph, one issuer key (BASELINE configs[3], proof_verify leg)" % n,
-                       "operating_point": ("ONE issuer key and generator set per GPU with %d-bit fixed-base windows (%.1f GB of tables: a choice for a "
-                                           "service with one issuer, sized for the 288 GB of HBM3E); the library's own default, "
-                                           "bbs_ctx_set_window_bits(ctx, 0), is 16 bits (2.1 GB) at 32 messages -- that rate is "
-                                           "`value_at_library_default_window_bits`" % (
-                                               args.window_bits, (L + 2) * ((256 + args.window_bits - 1) // args.window_bits) * (1 << (args.window_bits - 1)) * 128 / 1e9)),
                        "batch_per_gpu": n, "messages": L, "disclosed": R, "fixed_base_window_bits": args.window_bits,
                        "batches_in_flight": n_slots, "retire_order": "fifo (oldest first)" if args.fifo_retire else "completion (bbs_jobs_wait_any)",
                        "hw_queues": int(eng.lib.bbs_runtime_hw_queues()),
                        "dedicated_queues": args.dedicated_queues if args.dedicated_queues is not None else (os.environ.get("BBS_DEDICATED_QUEUES") or 0),
-                       "timed_region": "host buffers -> page-locked staging -> one async H2D -> device-side validation/"
-                                       "unpack -> kernels -> async D2H of statuses; one submitting thread per GPU "
-                                       "(SURVEY 8d)",
-                       "distinct_batches": n_slots, "corrupted_slot": "slot 1: every 16th item",
-                       "parallelism": "independent batches per GPU, no data-path collective"},
+                       "distinct_batches": n_slots, "corrupted_slot": "slot 1: every 16th item"},
             "checks": {"statuses_exact_every_step": True, "proofs_passed": int(cnt.item()),
                        "proofs_failed_as_expected": world * n * args.steps - int(cnt.item())},
-            "resident": {"proof_verify_per_s": res_rate, "host_inclusive_over_resident": value / world / res_rate,
-                         "stage_ms_per_step": res_stage,
-                         "note": "the same kernels on batches already uploaded / validated / unpacked in HBM, %d in "
-                                 "flight; never the headline" % n_slots},
-            "single_batch": dict(single["latency_form"] or single["throughput_form"],
-                                 form=("latency form = what the library's AUTO mode gives a job that is alone on its context "
-                                       "(bbs_ctx_set_latency_mode)") if single["latency_form"] else "throughput form (--latency-mode 0)",
-                                 throughput_form=single["throughput_form"]),
         }
-        if dt < 1.0:
-            out["timed_region_note"] = ("the timed region is %.0f ms (%d steps): filling and draining the %d in-flight slots is "
-                                        "inside it; `long_region` times the same loop for >= %.1f s" % (dt * 1e3, args.steps, n_slots, args.min_region_s))
+        if args.full:
+            counters, counters_file = load_counters()
+            lib_hash = eng.lib.bbs_source_hash().decode()
+            counters_hash = (counters or {}).get("library_source_hash")
+            counters_current = (counters_hash == lib_hash) if counters_hash else None
+            out["config"].update({
+                "operating_point": ("ONE issuer key and generator set per GPU with %d-bit fixed-base windows (%.1f GB of tables: a choice for a "
+                                    "service with one issuer, sized for the 288 GB of HBM3E); the library's own default, "
+                                    "bbs_ctx_set_window_bits(ctx, 0), is 16 bits (2.1 GB) at 32 messages -- that rate is "
+                                    "`value_at_library_default_window_bits`" % (
+                                        args.window_bits, (L + 2) * ((256 + args.window_bits - 1) // args.window_bits) * (1 << (args.window_bits - 1)) * 128 / 1e9)),
+                "timed_region": "host buffers -> page-locked staging -> one async H2D -> device-side validation/"
+                                "unpack -> kernels -> async D2H of statuses; one submitting thread per GPU "
+                                "(SURVEY 8d)",
+                "parallelism": "independent batches per GPU, no data-path collective"})
+            out["resident"] = {"proof_verify_per_s": res_rate, "host_inclusive_over_resident": value / world / res_rate,
+                               "stage_ms_per_step": res_stage,
+                               "note": "the same kernels on batches already uploaded / validated / unpacked in HBM, %d in "
+                                       "flight; never the headline" % n_slots}
+            out["single_batch"] = dict(single["latency_form"] or single["throughput_form"],
+                                       form=("latency form = what the library's AUTO mode gives a job that is alone on its context "
+                                             "(bbs_ctx_set_latency_mode)") if single["latency_form"] else "throughput form (--latency-mode 0)",
+                                       throughput_form=single["throughput_form"])
+            if dt < 1.0:
+                out["timed_region_note"] = ("the timed region is %.0f ms (%d steps): filling and draining the %d in-flight slots is "
+                                            "inside it; `long_region` times the same loop for >= %.1f s" % (dt * 1e3, args.steps, n_slots, args.min_region_s))
         if long_region is not None:
             out["long_region"] = {"steps": long_region[0], "seconds": long_region[1],
                                   "proof_verify_per_s": world * n * long_region[0] / long_region[1],
@@ -479,7 +505,7 @@ def main():
                 out["value_at_library_default_window_bits"] = {
                     "window_bits": 16, "proof_verify_per_s": w16["proof_verify_per_s"], "table_bytes": w16["table_bytes"],
                     "note": "the same submit loop on the same batches with the tables the library picks by itself (64 steps, untimed leg)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -208,6 +208,30 @@ def test_bench_starts_its_own_ranks():
     assert line["n_gpus"] == 2 and line["steps"] == 8 and line["checks"]["statuses_exact_every_step"] is True
 
 
+def test_bench_plain_run_dumps_last_statuses(tmp_path):
+    """A plain bench run (no --full) prints the headline only; --dump-outputs writes the statuses of the last timed step and
+    of the last --inflight timed steps as float32, the corrupted slot's every 16th item rejected."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "1024",
+                        "--inflight", "4", "--window-bits", "16", "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 6 and line["ms_per_step"] > 0 and line["checks"]["statuses_exact_every_step"] is True
+    assert not {"resident", "roofline", "valu_issue", "other_ops", "cpu_baseline", "long_region"} & set(line)
+    last, rnd = np.load(tmp_path / "status.npy"), np.load(tmp_path / "status_last_round.npy")
+    assert last.dtype == rnd.dtype == np.float32 and last.shape == (1024,) and rnd.shape == (4, 1024)
+    want = np.ones((4, 1024), np.float32)           # steps 2 .. 5 = slots 2, 3, 0, 1; slot 1 is the corrupted one
+    want[3, ::16] = 0
+    assert np.array_equal(rnd, want) and np.array_equal(last, want[3])
+
+
 # ---- the latency form of a job (T1 on three lanes, the two Miller loops on separate wavefronts): the same cases ----------
 LATENCY = pytest.mark.job_form(True)
 

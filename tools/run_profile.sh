@@ -3,7 +3,7 @@
 # eight in flight, the headline condition).  usage: tools/run_profile.sh <tag>
 TAG=${1:-r02}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
-B="$GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras"
+B="$(cd "$(dirname "$0")/.." && pwd)/bench.py --full --no-cpu-baseline --no-extras"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $B --steps 64 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || { echo stats failed; tail -5 $OUT/stats.err; exit 1; }
 echo "stats done"
