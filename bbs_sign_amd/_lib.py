@@ -14,6 +14,7 @@ PRODUCT_LIB = os.path.join(_HERE, "libbbs_sign_amd.so")
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_i8p = ctypes.POINTER(ctypes.c_int8)
 c_u64p = ctypes.POINTER(ctypes.c_uint64)
+c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_f32p = ctypes.POINTER(ctypes.c_float)
 vp = ctypes.c_void_p
 sz = ctypes.c_size_t
@@ -97,6 +98,20 @@ SIGNATURES = {
                                       c_u8p, c_u64p, c_i8p]),
     "bbs_verify_wire_submit": (ci, [vp, sz, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_verify_wire_batch": (ci, [vp, sz, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    # keyed verification: the context's key set, item i under key key_index[i] (the argument after n)
+    "bbs_ctx_set_public_keys": (ci, [vp, sz, c_u8p, c_i8p, c_i8p]),
+    "bbs_core_proof_verify_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,
+                                                c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_proof_verify_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,
+                                               c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_proof_verify_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                                c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_proof_verify_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                               c_u8p, c_u64p, c_i8p]),
+    "bbs_core_verify_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_verify_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_verify_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_verify_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
     "bbs_sign_wire_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_sign_wire_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),
     "bbs_sign_octets_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),

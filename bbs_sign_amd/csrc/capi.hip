@@ -627,6 +627,84 @@ int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, con
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_submit(ctx, n, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
+// keyed verification (keyed.hpp): the context's key set instead of its one public key, item i under key key_index[i]
+int bbs_ctx_set_public_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* pk, const int8_t* is_identity, int8_t* key_status) {
+    if (!ctx) return BBS_E_ARG;
+    return DISPATCH(ctx, AS_BLS(ctx)->set_public_keys(n_keys, pk, is_identity, key_status), AS_BN(ctx)->set_public_keys(n_keys, pk, is_identity, key_status));
+}
+int bbs_core_proof_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* pf, const uint8_t* cm,
+                                       const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
+                                       const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
+                                       bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    bbs_job* job = nullptr;
+    int rc = DISPATCH(ctx, (pv_upload<BlsCurve, true>(AS_BLS(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, &job, nullptr, nullptr, nullptr, nullptr, key_index)),
+                      (pv_upload<BnCurve, true>(AS_BN(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, &job, nullptr, nullptr, nullptr, nullptr, key_index)));
+    if (rc) return rc;
+    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+}
+int bbs_core_proof_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* pf, const uint8_t* cm,
+                                      const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
+                                      const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_proof_verify_keyed_submit(ctx, n, key_index, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, status, &job), job);
+}
+int bbs_proof_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* oct, const uint64_t* oct_off,
+                                       const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                       const uint64_t* di, const uint64_t* dio,
+                                       const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
+                                       bbs_job** job_out) {
+    if (!ctx || !status || !job_out || (n && (!oct_off || !msg_item_off))) return BBS_E_ARG;
+    if (!msg_byte_off) {                                  // no disclosed message in the whole batch
+        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
+        msg_byte_off = BBS_ZERO_OFF;
+    }
+    bbs_job* job = nullptr;
+    int rc = DISPATCH(ctx, (pv_upload<BlsCurve, true>(AS_BLS(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off, key_index)),
+                      (pv_upload<BnCurve, true>(AS_BN(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off, key_index)));
+    if (rc) return rc;
+    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+}
+int bbs_proof_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* oct, const uint64_t* oct_off,
+                                      const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                      const uint64_t* di, const uint64_t* dio,
+                                      const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_proof_verify_wire_keyed_submit(ctx, n, key_index, oct, oct_off, msg_bytes, msg_byte_off, msg_item_off, di, dio, h, ho, ph, pho, status, &job), job);
+}
+int bbs_core_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
+                                 const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    bbs_job* job = nullptr;
+    int rc = DISPATCH(ctx, (vf_upload<BlsCurve, true>(AS_BLS(ctx), n, sigs, m, mo, h, ho, &job, nullptr, nullptr, nullptr, key_index)),
+                      (vf_upload<BnCurve, true>(AS_BN(ctx), n, sigs, m, mo, h, ho, &job, nullptr, nullptr, nullptr, key_index)));
+    if (rc) return rc;
+    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+}
+int bbs_core_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
+                                const uint8_t* h, const uint64_t* ho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_verify_keyed_submit(ctx, n, key_index, sigs, m, mo, h, ho, status, &job), job);
+}
+int bbs_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
+                                 const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho,
+                                 int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out || (n && (!sig_octets || !msg_item_off))) return BBS_E_ARG;
+    if (!msg_byte_off) {
+        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
+        msg_byte_off = BBS_ZERO_OFF;
+    }
+    bbs_job* job = nullptr;
+    int rc = DISPATCH(ctx, (vf_upload<BlsCurve, true>(AS_BLS(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off, key_index)),
+                      (vf_upload<BnCurve, true>(AS_BN(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off, key_index)));
+    if (rc) return rc;
+    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+}
+int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
+                                const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_verify_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
+}
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                          const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status, bbs_job** job_out) {
     if (!ctx || !status || !job_out || (n && (!sig_octets_out || !msg_item_off))) return BBS_E_ARG;

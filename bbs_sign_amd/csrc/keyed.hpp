@@ -1,0 +1,158 @@
+// Keyed verification (bbs_ctx_set_public_keys, bbs_*_keyed_*): every item of a batch names one key of the context's KEY SET
+// instead of the context's single public key.  Only two things of a verification depend on the key: the Miller-loop line
+// table of W = pk and the midstate of the domain hash.  A key-set entry holds both; everything else (the fixed-base window
+// tables, BP2's line table, the Frobenius constants) stays in CtxConsts and is shared by all keys.
+//
+// Pairing order.  The six-lane pairing kernel (PairDist) reads W's line entries with SCALAR loads: the table is the same
+// for the ten items of a wavefront.  The host sorts a keyed batch by key (stable counting sort) into a slot -> item map:
+//   * first, whole wavefronts of ONE key (floor(c / 10) per key with c items): the key-uniform body -- the key is made
+//     wave-uniform with readfirstlane, the line loads stay scalar, the body is PairDist's plus the slot -> item lookup;
+//   * then the c mod 10 remaining items of every key, packed ten per wavefront: the mixed body -- each six-lane group
+//     reads its own key's lines with vector loads.
+// ONE launch covers both (PairDistKeyed picks the body per wavefront): as two launches on the job's pairing stream the
+// mixed wavefronts waited for the whole uniform launch, a second wavefront-time on the job's critical path (measured: 0.70
+// of the single-key rate on the headline loop).
+// Items keep their own index for points, gate and output; the slot map only decides which lanes compute which item.
+// DESIGN.md 8 has the layout and the measured registers and times.
+#pragma once
+#include "stages.hpp"
+
+namespace bbs {
+
+template <class C>
+struct KeyEntry {
+    LineTable<C> tab;            // lines of W = this key
+    HashCtx hash;                // domain prefix midstate with this key (dst_h2s as the context's)
+};
+
+constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;     // item whose key index is unknown or names a refused key
+constexpr int KEY_SLOTS_PER_WAVE = 10;         // == GRP_PER_WAVE (pairing_dist.hpp)
+
+// items with KEY_NONE are decided at ingest: BBS_ST_UNKNOWN_KEY, never computed (runs behind the ingest stage)
+struct KeyGateArgs { size_t n; const uint32_t* kidx; int8_t* status0; };
+struct KeyGate {
+    static __host__ __device__ void run(const KeyGateArgs& a, size_t i) {
+        if (a.kidx[i] == KEY_NONE) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
+    }
+};
+
+// the domain of a keyed item from its key's entry (lane per item, as PvScalars / VfScalars)
+template <class C, class A>
+struct KeyedScalarArgs { A a; const KeyEntry<C>* keys; const uint32_t* kidx; };
+template <class C>
+struct PvScalarsKeyed {
+    static __host__ __device__ void run(const KeyedScalarArgs<C, PvArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        pv_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash);
+    }
+};
+template <class C>
+struct VfScalarsKeyed {
+    static __host__ __device__ void run(const KeyedScalarArgs<C, VfArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        vf_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash);
+    }
+};
+
+// the keyed pairing step: e(Pa, W_key(i)) * e(+-Pb, BP2) == 1 for the items of the slots [0, n_slots)
+template <class C>
+struct PairKeyedArgs {
+    PairArgs<C> p;               // points, gate, output of the job (batch_ok unused: keyed jobs do not batch-verify)
+    const KeyEntry<C>* keys;
+    const uint32_t* kidx;        // [n] key of item i
+    const uint32_t* slot_item;   // [n_slots] pairing order: slot -> item
+    const uint32_t* wave_key;    // [n_uni / 10] key of uniform wavefront w
+    size_t n_uni;                // slots [0, n_uni): key-uniform wavefronts (a multiple of 10); [n_uni, n_slots): mixed
+    size_t n_slots;
+};
+template <class C>
+BBS_HD uint32_t pair_keyed_key(const PairKeyedArgs<C>& ka, size_t s, size_t i) {
+    return s < ka.n_uni ? ka.wave_key[s / KEY_SLOTS_PER_WAVE] : ka.kidx[i];
+}
+
+// host twin: one lane per (pair, slot), same item / key lookup as the device kernels; PairFinal follows per item
+template <class C>
+struct PairMillerKeyed {
+    static __host__ __device__ void run(const PairKeyedArgs<C>& ka, size_t t) {
+        constexpr int N = C::FpP::N;
+        const PairArgs<C>& a = ka.p;
+        const size_t n = a.n, ns = ka.n_slots;
+        const int pair = (int)(t / ns);
+        const size_t s = t - (size_t)pair * ns;
+        const size_t i = ka.slot_item[s];
+        if (a.gate_arr[i] != a.gate) return;
+        G1Aff<C> P = pair_load_point<C>(a, pair == 0 ? a.pa : a.pb, i);
+        if (pair == 1 && a.negate_b) P = g1a_neg<C>(P);
+        const LineTable<C>* tab = pair == 0 ? &ka.keys[pair_keyed_key<C>(ka, s, i)].tab : &a.cc->tab_bp2;
+        Fp12<C> f = f12_one<C>();
+        const bool skip = g1a_is_inf<C>(P) | (tab->q_is_identity != 0);
+        if (!skip) {
+            int li = 0;
+            const int nops = a.cc->sched.n_ops;
+            for (int k = 0; k < nops; k++) {
+                if (a.cc->sched.op[k] == 0) f = f12_sqr<C>(f);
+                else f = f12_mul_line<C>(f, tab->e[li++], P);
+            }
+            if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
+        }
+        f12_store<C>(a.fmiller + (size_t)pair * 12 * N * n, n, i, f);
+    }
+};
+
+#if !defined(BBS_HOST_TWIN)
+static_assert(KEY_SLOTS_PER_WAVE == GRP_PER_WAVE, "the host cuts the pairing order into wavefronts of GRP_PER_WAVE items");
+// PairDist over a slot map.  UNIFORM: every slot of the wavefront has the key wave_key[wave] -- read once, made
+// wave-uniform, so W's line entries are scalar loads exactly as in PairDist.  Mixed: each six-lane group reads the lines of
+// its own item's key (vector loads).
+template <class C, bool UNIFORM>
+__device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size_t t) {
+    const PairArgs<C>& a = ka.p;
+    const int lane = (int)(t & 63);
+    const int grp = lane / GRP;
+    if (grp >= GRP_PER_WAVE) return;
+    const size_t s = (t >> 6) * GRP_PER_WAVE + grp;
+    if (s >= ka.n_slots) return;
+    const size_t i = ka.slot_item[s];
+    if (a.gate_arr[i] != a.gate) return;
+    Lane6 L{grp * GRP, lane - grp * GRP};
+    const CtxConsts<C>* cc = a.cc;
+    const LineTable<C>* tw;
+    if constexpr (UNIFORM) tw = &ka.keys[__builtin_amdgcn_readfirstlane(ka.wave_key[t >> 6])].tab;
+    else tw = &ka.keys[ka.kidx[i]].tab;
+    G1Aff<C> Pa = pair_load_point<C>(a, a.pa, i);
+    G1Aff<C> Pb = pair_load_point<C>(a, a.pb, i);
+    if (a.negate_b) Pb = g1a_neg<C>(Pb);
+    const bool skipA = g1a_is_inf<C>(Pa) | (tw->q_is_identity != 0);
+    const bool skipB = g1a_is_inf<C>(Pb) | (cc->tab_bp2.q_is_identity != 0);
+    Fp2<C> f = d_one<C>(L);
+    if (!(skipA & skipB)) {
+        Fp2<C> m = d_one<C>(L);
+        int li = 0;
+        const int nops = cc->sched.n_ops;
+        for (int k = 0; k < nops; k++) {
+            if (cc->sched.op[k] == 0) {
+                m = d_sqr<C>(L, m);
+            } else {
+                if (!skipA) m = d_mul_line<C>(L, m, tw->e[li], Pa);
+                if (!skipB) m = d_mul_line<C>(L, m, cc->tab_bp2.e[li], Pb);
+                li++;
+            }
+        }
+        if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
+        const Fp2<C> mf = m;
+        f = d_final_exp<C>(L, mf, &cc->frob[0][0][0][0]);
+    }
+    const bool one = d_is_one<C>(L, f);
+    if (L.m == 0) a.out[i] = one ? 1 : 0;
+}
+template <class C>
+struct PairDistKeyed {
+    static constexpr int WAVES_PER_EU = BBS_PAIR_WAVES;
+    static __device__ void run(const PairKeyedArgs<C>& ka, size_t t) {
+        if ((t >> 6) * GRP_PER_WAVE < ka.n_uni) pair_dist_keyed<C, true>(ka, t);     // (uniform over the wavefront)
+        else pair_dist_keyed<C, false>(ka, t);
+    }
+};
+#endif
+
+}  // namespace bbs

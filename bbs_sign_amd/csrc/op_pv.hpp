@@ -25,16 +25,20 @@ struct PvJob : JobBase<C> {
     PvOctArgs<C> oct{};               // wire form only
     MsgHashArgs mh{};                 // wire form with raw messages only
     BvState<C> bv{};                  // batch verification only
+    KeyedJob<C> kj{};                 // keyed form only
 };
 
 // octets / oct_off != nullptr: the wire form (bbs_proof_verify_octets_*): proofs_fixed / commitments / commit_off are
 // ignored, the proofs come as octet strings and are decoded on the device (codec_dev.hpp PvOctDecode / PvOctIngest)
-template <class C>
+// KEYED (bbs_*_keyed_*, instantiated in tu_pvk_*.hip): item i is verified under key key_index[i] of the context's key set
+// (keyed.hpp): its own domain and W line table; the fused pairing kernel in both job forms, no batch verification
+template <class C, bool KEYED = false>
 int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t* commitments,
                      const uint64_t* commit_off, const uint8_t* dmsgs, const uint64_t* dmsg_off,
                      const uint64_t* didx, const uint64_t* didx_off, const uint8_t* headers,
                      const uint64_t* hdr_off, const uint8_t* ph, const uint64_t* ph_off, bbs_job** out,
-                     const uint8_t* octets, const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off) {
+                     const uint8_t* octets, const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                     const uint32_t* key_index = nullptr) {
     // msg_byte_off != nullptr (wire form only): the disclosed messages arrive as RAW BYTES -- message t of the batch is
     // msg_bytes[msg_byte_off[t] .. msg_byte_off[t + 1]), dmsg_off counts messages per item as before, dmsgs is ignored --
     // and are mapped to scalars on the device (msg_to_scalars, interface_utilities.rs:76-88)
@@ -44,7 +48,12 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
     constexpr int N = C::FpP::N;        // internal limbs
     constexpr int NC = C::FpP::NC;      // canonical 32-bit words
     constexpr int FPB = 4 * NC;
-    if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    if constexpr (KEYED) {
+        if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
+        if (n && !key_index) return BBS_E_ARG;
+    } else {
+        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    }
     if (!out || (n && (!dmsg_off || !didx_off))) return BBS_E_ARG;
     if (n && !wire && (!proofs_fixed || !commit_off)) return BBS_E_ARG;
     if (n && wire && !octets) return BBS_E_ARG;
@@ -53,6 +62,9 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
     const size_t rec = 6 * FPB + 128;
     auto job = std::unique_ptr<PvJob<C>>(new PvJob<C>(ctx));
     job->n = n;
+    std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
+    size_t kwords_at = 0;
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, key_index, job->kj, kwords);
     // ---- the batch as one staging image in page-locked memory, one asynchronous copy; everything else (the
     // reference's checks, range checks, unpacking, the SoA transposition) happens on the device: stage PvIngest
     // first ragged section: the commitments (core form) or the proof octet strings (wire form)
@@ -66,9 +78,10 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
     RaggedIn mb{raw ? (nm ? msg_byte_off + dmsg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
     // (the message section is ragged over MESSAGES, not items: stage_image places and fills it with nm as its count)
-    if (int rc0 = stage_image(job.get(), n, wire ? nullptr : proofs_fixed, wire ? 0 : rec, {&cm, &dm, &di, &hb, &pb}, raw ? &mb : nullptr, nm)) return rc0;
+    if (int rc0 = stage_image(job.get(), n, wire ? nullptr : proofs_fixed, wire ? 0 : rec, {&cm, &dm, &di, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
 
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
+    if constexpr (KEYED) keyed_bind<C>(job->kj, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     auto d64 = [&](size_t at) { return reinterpret_cast<const uint64_t*>(dimg + at); };
     auto d32 = [&](size_t at) { return reinterpret_cast<const uint32_t*>(dimg + at); };
     int rc = BBS_OK;
@@ -138,6 +151,9 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
         oa.status0 = job->d_status0.template as<int8_t>();
         if (rt::launch<PvOctDecode<C>>(job->stream(), oa, 3 * n) || rt::launch<PvOctIngest<C>>(job->stream(), oa, n)) return BBS_E_HIP;
     }
+    if constexpr (KEYED) {
+        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, job->d_status0.template as<int8_t>()))) return rc;
+    }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.pts; pa.pb = a.pts + (size_t)2 * NC * n; pa.negate_b = 1;
     pa.canonical = 1; pa.gate_arr = job->d_status0.template as<int8_t>(); pa.gate = ST_PENDING; pa.out = pair_ok;
@@ -164,14 +180,17 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
         if (layout == 3) j->stages.push_back({"pv_t1_chain", [j]() { return rt::launch<PvT1Chain<C>>(j->stream_aux(2), j->a, j->n); }, 2, 0});
         if (layout == 2 && !chains_behind_scalars) chains2();
         if (layout == 3) j->stages.push_back({"pv_var_mul", [j]() { return rt::launch<PvVarMul<C>>(j->stream(), j->a, j->n * (size_t)(j->a.nvar - PvVarMul<C>::first_part(j->a))); }});
-        j->stages.push_back({"pv_scalars", [j]() { return rt::launch<PvScalars<C>>(j->stream(), j->a, j->n); }});
+        if constexpr (KEYED)
+            j->stages.push_back({"pv_scalars_keyed", [j]() { return rt::launch<PvScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PvArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+        else
+            j->stages.push_back({"pv_scalars", [j]() { return rt::launch<PvScalars<C>>(j->stream(), j->a, j->n); }});
         if (layout == 2 && chains_behind_scalars) chains2();
         if (j->a.fixwk.pts0) j->stages.push_back({"pv_fixed_tree", [j]() { return rt::launch<PvFixedTree<C>>(j->stream(), j->a, j->n); }});
         else j->stages.push_back({"pv_fixed_chunks", [j]() { return rt::launch<PvFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});
         if (layout == 1) j->stages.push_back({"pv_chains", [j]() { return rt::launch<PvChains<C>>(j->stream(), j->a, j->n * PvChains<C>::units(j->a)); }});
     };
     const int join_chains = 2;      // Stage::join bit of the second side stream (ignored where nothing was forked onto it)
-    if (!ctx->batch_verify) {
+    if (KEYED || !ctx->batch_verify) {
         // every item its own pairing product, on the job's second stream concurrently with the MSM / challenge
         // stages: it needs only the proof's own points (canonical, converted in the kernel) and the flag the ingest stage
         // left.  First in the list: the second stream forks where its first stage stands, i.e. before the MSM chain.
@@ -180,11 +199,12 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
         // chain it oversubscribes the 1024 SIMDs and the queued wavefronts cost more than the split saves (measured
         // 5.1 ms split vs 4.4 ms fused, profiles/r03_j_latency_form_split.log)
         static const bool lat_split = []() { const char* v = getenv("BBS_PV_LAT_SPLIT"); return v && atoi(v) != 0; }();      // A/B knob
-        add_pairing_stages<C>(j, &j->pa, 1, "pair_miller", "pair_final_exp", "pairing_6lane", false, 0, lat_split);
+        if constexpr (KEYED) add_keyed_pairing_stages<C>(j, &j->kj, &j->pa, 1);
+        else add_pairing_stages<C>(j, &j->pa, 1, "pair_miller", "pair_final_exp", "pairing_6lane", false, 0, lat_split);
         msm_chain(pv_msm_layout(false, job->latency_form));
         j->stages.push_back({"pv_challenge", [j]() { return rt::launch<PvChallenge<C>>(j->stream(), j->a, j->n); }, 0, join_chains});
         j->stages.push_back({"pv_finish", [j]() { return rt::launch<PvFinish>(j->stream(), j->fin, j->n); }, 0, 1});
-    } else {
+    } else if constexpr (!KEYED) {
         // batch verification (pippenger.hpp): combined pairing checks instead of n products; if one fails, the per-item
         // kernel decides the items still pending (its lanes write Ok(true) and return at once otherwise).
         //  * latency form: the combination runs on the job's second stream BESIDE the MSM / challenge stages, over the

@@ -13,19 +13,28 @@ struct VfJob : JobBase<C> {
     VfOctArgs<C> oct{};               // wire form only
     MsgHashArgs mh{};                 // raw-message form only
     BvState<C> bv{};                  // batch verification only
+    KeyedJob<C> kj{};                 // keyed form only
 };
 
-template <class C>
+// KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
+// (keyed.hpp); the fused pairing kernel in both job forms, no batch verification
+template <class C, bool KEYED = false>
 int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
                      const uint8_t* headers, const uint64_t* hdr_off, bbs_job** out, const uint8_t* octets,
-                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off) {
+                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                     const uint32_t* key_index = nullptr) {
     // msg_byte_off != nullptr: the messages arrive as RAW BYTES (message t of the batch = msg_bytes[msg_byte_off[t] ..
     // msg_byte_off[t + 1]), msg_off counts messages per item, msgs is ignored) and are hashed to scalars on the device
     // octets != nullptr: the wire form -- n strings compress(A) || e instead of the records `sigs`
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
-    if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    if constexpr (KEYED) {
+        if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
+        if (n && !key_index) return BBS_E_ARG;
+    } else {
+        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    }
     if (!out || (n && ((!sigs && !octets) || !msg_off))) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
@@ -34,6 +43,9 @@ int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, c
     if (wire) sigs = octets;
     auto job = std::unique_ptr<VfJob<C>>(new VfJob<C>(ctx));
     job->n = n;
+    std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
+    size_t kwords_at = 0;
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, key_index, job->kj, kwords);
     // the batch as one staging image, one asynchronous copy; checks, range checks and the SoA transposition on the
     // device (stage VfIngest), as for proof_verify
     const bool raw = msg_byte_off != nullptr;
@@ -44,8 +56,9 @@ int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, c
     // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
     RaggedIn mb{raw ? (nm ? msg_byte_off + msg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
-    if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &hb}, raw ? &mb : nullptr, nm)) return rc0;
+    if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &hb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
+    if constexpr (KEYED) keyed_bind<C>(job->kj, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     int rc = BBS_OK;
     const size_t Lw = (size_t)std::max(L, 1), nn = std::max<size_t>(n, 1);
     VfArgs<C>& a = job->a;
@@ -88,6 +101,9 @@ int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, c
     ia.sig_a = sig_a; ia.sig_e = sig_e; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
     if (rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if constexpr (KEYED) {
+        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
+    }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.aff; pa.pb = a.aff + (size_t)2 * N * n; pa.negate_b = 0;
     pa.canonical = 0; pa.gate_arr = a.status; pa.gate = ST_PAIRING; pa.out = a.status; pa.fmiller = a.fmiller;
@@ -98,12 +114,17 @@ int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, c
     // (profiles/r05_e_verify_var_mul_side_stream.log).  Except batch verification's throughput form, whose jobs are kept alive
     // by the dozen and must own ONE hardware queue each (32 in flight: 4.2 M/s on one stream, 3.1 M/s on two).
     static const int side_forced = []() { const char* v = getenv("BBS_VF_SIDE"); return v ? atoi(v) : -1; }();      // A/B: 0 never, 1 always
-    const int side = side_forced >= 0 ? (side_forced ? 1 : 0) : ((ctx->batch_verify && !job->latency_form) ? 0 : 1);
+    const int side = side_forced >= 0 ? (side_forced ? 1 : 0) : ((!KEYED && ctx->batch_verify && !job->latency_form) ? 0 : 1);
     j->stages.push_back({"vf_var_mul", [j, side]() { return rt::launch<VfVarMul<C>>(side ? j->stream_aux(1) : j->stream(), j->a, j->n); }, side, 0});
-    j->stages.push_back({"vf_scalars", [j]() { return rt::launch<VfScalars<C>>(j->stream(), j->a, j->n); }});
+    if constexpr (KEYED)
+        j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+    else
+        j->stages.push_back({"vf_scalars", [j]() { return rt::launch<VfScalars<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"vf_fixed_chunks", [j]() { return rt::launch<VfFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});
     j->stages.push_back({"vf_combine", [j]() { return rt::launch<VfCombine<C>>(j->stream(), j->a, j->n); }, 0, 1});
-    if (!ctx->batch_verify) {
+    if constexpr (KEYED) {
+        add_keyed_pairing_stages<C>(j, &j->kj, &j->pa, 0);
+    } else if (!ctx->batch_verify) {
         add_pairing_stages<C>(j, &j->pa, 0, "pair_miller", "pair_final_exp", "pairing_6lane");
     } else {
         // e(A, W) e(e A - B, BP2) == 1 for all pending items at once: A and e A - B are in a.aff (Montgomery)

@@ -21,12 +21,14 @@
 #include <mutex>
 #include <memory>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/bbs_sign_amd.h"
 #include "host_g2.hpp"
 #include "codec_dev.hpp"
+#include "keyed.hpp"
 
 using namespace bbs;
 
@@ -553,6 +555,14 @@ struct Ctx : bbs_ctx {
     CtxConsts<C> hc{};               // host mirror
     DevBuf d_consts, d_tables, d_winbase, d_bases;
     bool consts_dirty = true;
+    // key set of the keyed entry points (bbs_ctx_set_public_keys, keyed.hpp): immutable once built; a keyed job holds a
+    // reference, so replacing the set never changes a job in flight, and the device array goes with its last holder
+    struct KeySet {
+        size_t n = 0;
+        std::vector<int8_t> status;  // per key: 1 accepted, BBS_ST_NOT_ON_CURVE refused
+        DevBuf d;                    // [n] KeyEntry<C>
+    };
+    std::shared_ptr<const KeySet> keys;
     // batch verification (pippenger.hpp): off by default = every item gets its own pairing product
     bool batch_verify = false;
     // caller vouches that every G1 input is in the prime-order subgroup: variable-base multiplications of the
@@ -632,10 +642,15 @@ struct Ctx : bbs_ctx {
         dst_too_long = dst.size() > 255;
         if (!dst_too_long) { std::memcpy(h.dst_h2s, dst.data(), dst.size()); h.dst_h2s_len = (uint32_t)dst.size(); }
         if (!(gens_set && pk_set)) { consts_dirty = true; return; }
+        domain_midstate(pk, h);
+        consts_dirty = true;
+    }
+    // the key-dependent part of the domain prefix (needs the generators): dom_* of h for key q
+    void domain_midstate(const G2Aff<C>& q, HashCtx& h) const {
         Sha256 s;
         xmd48_begin(s);
         uint8_t buf[4 * FPB];
-        g2_compress<C>(pk, buf);
+        g2_compress<C>(q, buf);
         sha256_bytes(s, buf, 2 * FPB);
         sha256_u64be(s, (uint64_t)L);
         for (const auto& g : gens) { g1_compress_host<C>(g, buf); sha256_bytes(s, buf, FPB); }
@@ -644,7 +659,6 @@ struct Ctx : bbs_ctx {
         h.dom_mid_total = s.total - s.fill;
         h.dom_tail_len = s.fill;
         for (uint32_t k = 0; k < s.fill; k++) h.dom_tail[k] = (uint8_t)(s.w[k >> 2] >> ((3 - (k & 3)) * 8));
-        consts_dirty = true;
     }
 
     int sync_consts() {
@@ -680,6 +694,48 @@ struct Ctx : bbs_ctx {
         }
         sk_set = false;
         return set_pk_internal(q);
+    }
+    // bbs_ctx_set_public_keys: every key is checked as set_public_key checks it and gets its W line table and domain
+    // midstate on the host (the subgroup check and the line table: 16 host threads; 4096 BLS12-381 keys in 0.52 s),
+    // then the whole set is ONE device array.  Needs the generators (set_generators drops the set: its midstates would
+    // be stale).  On failure the previous set stays.
+    int set_public_keys(size_t n_keys, const uint8_t* b, const int8_t* is_identity, int8_t* key_status) {
+        if (n_keys && !b) return BBS_E_ARG;
+        if (!n_keys) { keys.reset(); return BBS_OK; }
+        if (!gens_set) return BBS_E_STATE;
+        if (use()) return BBS_E_HIP;
+        std::shared_ptr<KeySet> ks(new KeySet());
+        ks->n = n_keys;
+        ks->status.assign(n_keys, (int8_t)BBS_ST_NOT_ON_CURVE);
+        std::vector<KeyEntry<C>> host(n_keys);
+        auto one = [&](size_t k) {
+            KeyEntry<C>& e = host[k];
+            std::memset(&e, 0, sizeof(e));
+            e.hash = hc.hash;                           // dst_h2s of the context
+            e.tab.q_is_identity = 1;
+            G2Aff<C> q{};
+            q.inf = is_identity && is_identity[k] != 0;
+            const uint8_t* p = b + k * 4 * FPB;
+            using P = typename C::FpP;
+            if (q.inf) { q.x = f2_zero<C>(); q.y = f2_zero<C>(); }
+            else if (!fe_from_le_bytes<P>(p, q.x.c0) || !fe_from_le_bytes<P>(p + FPB, q.x.c1) ||
+                     !fe_from_le_bytes<P>(p + 2 * FPB, q.y.c0) || !fe_from_le_bytes<P>(p + 3 * FPB, q.y.c1)) return;
+            if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q) || !build_line_table<C>(q, e.tab)) { e.tab.q_is_identity = 1; e.tab.n_lines = 0; return; }
+            domain_midstate(q, e.hash);
+            ks->status[k] = 1;
+        };
+        const size_t nt = std::min<size_t>({(size_t)16, n_keys, (size_t)std::max(1u, std::thread::hardware_concurrency())});
+        if (nt <= 1) { for (size_t k = 0; k < n_keys; k++) one(k); }
+        else {
+            std::vector<std::thread> th;
+            for (size_t t = 0; t < nt; t++) th.emplace_back([&, t]() { for (size_t k = t; k < n_keys; k += nt) one(k); });
+            for (auto& x : th) x.join();
+        }
+        if (ks->d.alloc(n_keys * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
+        if (rt::h2d(ks->d.p, host.data(), n_keys * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
+        if (key_status) std::memcpy(key_status, ks->status.data(), n_keys);
+        keys = std::move(ks);
+        return BBS_OK;
     }
     int set_secret_key(const uint8_t* sk32) {
         if (!sk32) return BBS_E_ARG;
@@ -874,6 +930,7 @@ struct JobBase : bbs_job {
     DevBuf d_raw;
     std::vector<std::pair<void*, size_t>> zero_on_reset;   // device arrays cleared before every run (fail closed)
     std::vector<std::unique_ptr<DevBuf>> bufs;
+    std::shared_ptr<const void> key_set;     // keyed jobs: the context's key set at upload (released after the streams synchronised)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};
     rt::Event ev_fork[bbs_job::N_AUX]{}, ev_join[bbs_job::N_AUX]{};
@@ -1027,15 +1084,18 @@ struct RaggedIn {
 // device buffers, fills the host image and enqueues the ONE host-to-device copy on the job's stream.
 template <class J>
 inline int stage_image(J* job, size_t n, const uint8_t* records, size_t rec_bytes, std::initializer_list<RaggedIn*> sections,
-                       RaggedIn* extra = nullptr, size_t extra_count = 0) {      // extra: a section ragged over extra_count entries
+                       RaggedIn* extra = nullptr, size_t extra_count = 0,        // extra: a section ragged over extra_count entries
+                       const std::vector<uint32_t>* words = nullptr, size_t* words_at = nullptr) {   // words: appended, at *words_at
     size_t cur = (n * rec_bytes + 15) & ~(size_t)15;
     for (RaggedIn* s : sections) s->place(cur, n);
     if (extra) extra->place(cur, extra_count);
+    if (words) { *words_at = cur; cur += (words->size() * 4 + 15) & ~(size_t)15; }
     if (job->h_raw.alloc(cur) || job->d_raw.alloc(cur)) return BBS_E_NOMEM;
     uint8_t* img = job->h_raw.template as<uint8_t>();
     if (n && rec_bytes) std::memcpy(img, records, n * rec_bytes);
     for (RaggedIn* s : sections) s->fill(img, n);
     if (extra) extra->fill(img, extra_count);
+    if (words && !words->empty()) std::memcpy(img + *words_at, words->data(), words->size() * 4);
     return rt::h2d_async(job->d_raw.p, img, cur, job->stream()) ? BBS_E_HIP : BBS_OK;
 }
 
@@ -1188,4 +1248,83 @@ void add_batch_decision(J* j, BvState<C>* bv, PairArgs<C>* fallback, int joins_a
     // no kernel of its own: the per-item kernel's lanes read the 16 verdicts first -- all passed: write Ok(true) and leave
     fallback->batch_ok = bv->batch_ok; fallback->n_checks = bv->n_checks;
     add_pairing_stages<C>(j, fallback, 0, "fallback_pair_miller", "fallback_pair_final_exp", "fallback_pairing_6lane", false, joins_aux);
+}
+
+// =============================================================================================
+// keyed jobs (keyed.hpp): per-item key indexes and the pairing order, built on the host at upload
+// =============================================================================================
+template <class C>
+struct KeyedJob {
+    const KeyEntry<C>* keys = nullptr;
+    const uint32_t* kidx = nullptr;          // [n] key of item i, KEY_NONE: unknown / refused (decided by KeyGate)
+    PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
+};
+// The host half, before the staging image is built: item i -> its key (KEY_NONE: unknown / refused) and the pairing order.
+// Items are sorted by key, stably (a counting sort); key k with c items fills floor(c / 10) key-uniform wavefronts, its c mod
+// 10 remaining items go to the mixed wavefronts behind them.  `words` = [kidx n][uniform slots][mixed slots][wave keys]; it
+// travels in the job's staging image (the one asynchronous copy), keyed_bind points the job at it.
+template <class C, class J>
+void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words) {
+    constexpr uint32_t W = (uint32_t)KEY_SLOTS_PER_WAVE;
+    const auto ks = ctx->keys;
+    j->key_set = ks;
+    const size_t nk = ks->n;
+    std::vector<uint32_t> cnt(nk, 0);
+    words.assign(3 * n + n / W + 1, 0);
+    uint32_t* kid = words.data();
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = key_index[i];
+        const bool ok = k < nk && ks->status[k] == 1;
+        kid[i] = ok ? k : KEY_NONE;
+        if (ok) cnt[k]++;
+    }
+    std::vector<uint32_t> ufirst(nk), mfirst(nk), seen(nk, 0);
+    size_t nu = 0, nm = 0;
+    for (size_t k = 0; k < nk; k++) {
+        ufirst[k] = (uint32_t)nu; nu += cnt[k] / W * W;
+        mfirst[k] = (uint32_t)nm; nm += cnt[k] % W;
+    }
+    uint32_t* uslot = words.data() + n;
+    uint32_t* mslot = uslot + nu;
+    uint32_t* wkey = mslot + nm;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = kid[i];
+        if (k == KEY_NONE) continue;
+        const uint32_t full = cnt[k] / W * W, s = seen[k]++;
+        if (s < full) uslot[ufirst[k] + s] = (uint32_t)i;
+        else mslot[mfirst[k] + s - full] = (uint32_t)i;
+    }
+    for (size_t k = 0, w = 0; k < nk; k++)
+        for (uint32_t q = 0; q < cnt[k] / W; q++) wkey[w++] = (uint32_t)k;
+    words.resize(n + nu + nm + nu / W);
+    kj.keys = ks->d.template as<KeyEntry<C>>();
+    kj.pair.keys = kj.keys; kj.pair.n_uni = nu; kj.pair.n_slots = nu + nm;
+}
+// the device half: d = the words' place in the device copy of the staging image
+template <class C>
+void keyed_bind(KeyedJob<C>& kj, size_t n, const uint32_t* d) {
+    kj.kidx = d;
+    kj.pair.kidx = d; kj.pair.slot_item = d + n; kj.pair.wave_key = d + n + kj.pair.n_slots;
+}
+// behind the ingest stage: items with an unknown key are decided (BBS_ST_UNKNOWN_KEY)
+template <class J>
+int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
+    return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
+}
+// the pairing step of a keyed job on the main (aux = 0) or second stream, as add_pairing_stages: the fused kernel in both job
+// forms.  kj->pair.p is copied from *pa when the stage is launched.
+template <class C, class J>
+void add_keyed_pairing_stages(J* j, KeyedJob<C>* kj, const PairArgs<C>* pa, int aux) {
+#ifdef BBS_HOST_TWIN
+    j->stages.push_back({"pair_miller_keyed", [j, kj, pa, aux]() {
+        kj->pair.p = *pa;
+        return rt::launch<PairMillerKeyed<C>>(aux ? j->stream_aux() : j->stream(), kj->pair, kj->pair.n_slots * 2);
+    }, aux, 0});
+    j->stages.push_back({"pair_final_exp", [j, pa, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pa, pa->n); }, aux, 0});
+#else
+    j->stages.push_back({"pairing_6lane_keyed", [j, kj, pa, aux]() {
+        kj->pair.p = *pa;
+        return rt::launch<PairDistKeyed<C>>(aux ? j->stream_aux() : j->stream(), kj->pair, ((kj->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64);
+    }, aux, 0});
+#endif
 }

@@ -605,28 +605,33 @@ struct PvIngest {
     }
 };
 
-// stage 1 (lane per item): domain, fixed-base scalars
+// stage 1 (lane per item): domain, fixed-base scalars.  h: the domain prefix of the item's key (the context's, or its key-set
+// entry in a keyed job: keyed.hpp PvScalarsKeyed)
+template <class C>
+BBS_HD void pv_scalars_item(const PvArgs<C>& a, size_t i, const HashCtx& h) {
+    using R = typename C::FrP;
+    const size_t n = a.n;
+    Fr<C> dom = domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
+    soa_st<8>(a.dom, n, i, dom.v);
+    Fr<C> c_canon = fr_load_canon<C>(a.sc + (size_t)3 * 8 * n, n, i);
+    Fr<C> c_m = fr_to_mont<C>(c_canon);
+    // P1 * c
+    soa_st<8>(a.fscal, n, i, c_canon.v);
+    // Q1 * (domain * c) : mont_mul(dom_mont, c_canon) = dom*c canonical... dom is Montgomery:
+    Fr<C> dc = fe_mul<R>(dom, c_canon);                 // (dom*R)*c/R = dom*c canonical
+    soa_st<8>(a.fscal + (size_t)1 * 8 * n, n, i, dc.v);
+    for (int j = 0; j < a.L; j++) {
+        Fr<C> s = fr_load_canon<C>(a.slots + (size_t)j * 8 * n, n, i);
+        const uint32_t m = a.dmask[(size_t)(j >> 5) * n + i];
+        if ((m >> (j & 31)) & 1u) s = fe_mul<R>(c_m, s);    // (c*R)*m/R = c*m canonical
+        soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, s.v);
+    }
+}
 template <class C>
 struct PvScalars {
     static __host__ __device__ void run(const PvArgs<C>& a, size_t i) {
-        using R = typename C::FrP;
         if (a.status[i] != ST_PENDING) return;
-        const size_t n = a.n;
-        Fr<C> dom = domain_from_header<C>(a.cc->hash, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
-        soa_st<8>(a.dom, n, i, dom.v);
-        Fr<C> c_canon = fr_load_canon<C>(a.sc + (size_t)3 * 8 * n, n, i);
-        Fr<C> c_m = fr_to_mont<C>(c_canon);
-        // P1 * c
-        soa_st<8>(a.fscal, n, i, c_canon.v);
-        // Q1 * (domain * c) : mont_mul(dom_mont, c_canon) = dom*c canonical... dom is Montgomery:
-        Fr<C> dc = fe_mul<R>(dom, c_canon);                 // (dom*R)*c/R = dom*c canonical
-        soa_st<8>(a.fscal + (size_t)1 * 8 * n, n, i, dc.v);
-        for (int j = 0; j < a.L; j++) {
-            Fr<C> s = fr_load_canon<C>(a.slots + (size_t)j * 8 * n, n, i);
-            const uint32_t m = a.dmask[(size_t)(j >> 5) * n + i];
-            if ((m >> (j & 31)) & 1u) s = fe_mul<R>(c_m, s);    // (c*R)*m/R = c*m canonical
-            soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, s.v);
-        }
+        pv_scalars_item<C>(a, i, a.cc->hash);
     }
 };
 
@@ -1174,22 +1179,27 @@ struct VfIngest {
     }
 };
 
+// h: the domain prefix of the item's key (as pv_scalars_item)
+template <class C>
+BBS_HD void vf_scalars_item(const VfArgs<C>& a, size_t i, const HashCtx& h) {
+    using R = typename C::FrP;
+    const size_t n = a.n;
+    Fr<C> dom = fe_to_canonical<R>(domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]));
+    Fr<C> one = fe_zero<R>();
+    one.v[0] = 1;
+    soa_st<8>(a.fscal, n, i, one.v);
+    soa_st<8>(a.fscal + (size_t)8 * n, n, i, dom.v);
+    for (int j = 0; j < a.L; j++) {
+        uint32_t m[8];
+        soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
+        soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, m);
+    }
+}
 template <class C>
 struct VfScalars {
     static __host__ __device__ void run(const VfArgs<C>& a, size_t i) {
-        using R = typename C::FrP;
         if (a.status[i] != ST_PENDING) return;
-        const size_t n = a.n;
-        Fr<C> dom = fe_to_canonical<R>(domain_from_header<C>(a.cc->hash, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]));
-        Fr<C> one = fe_zero<R>();
-        one.v[0] = 1;
-        soa_st<8>(a.fscal, n, i, one.v);
-        soa_st<8>(a.fscal + (size_t)8 * n, n, i, dom.v);
-        for (int j = 0; j < a.L; j++) {
-            uint32_t m[8];
-            soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
-            soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, m);
-        }
+        vf_scalars_item<C>(a, i, a.cc->hash);
     }
 };
 

@@ -186,6 +186,109 @@ class Engine:
         buf = _bytes_arr(self._fp(x0) + self._fp(x1) + self._fp(y0) + self._fp(y1))
         self._chk(self.lib.bbs_ctx_set_public_key(self.h, _u8(buf), 0), "bbs_ctx_set_public_key")
 
+    def set_public_keys(self, keys) -> np.ndarray:
+        """bbs_ctx_set_public_keys: the context's KEY SET for the keyed entry points (``*_keyed_*``); ``keys[k]`` as for
+        set_public_key (None = the identity).  Returns the per-key statuses: 1, or -41 for a key set_public_key would refuse.
+        An empty list clears the set."""
+        n = len(keys)
+        rec = 4 * self.fpb
+        buf = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        ident = np.zeros(max(n, 1), dtype=np.int8)
+        for k, pk in enumerate(keys):
+            if pk is None:
+                ident[k] = 1
+                continue
+            (x0, x1), (y0, y1) = pk
+            buf[k * rec:(k + 1) * rec] = np.frombuffer(self._fp(x0) + self._fp(x1) + self._fp(y0) + self._fp(y1), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        self._chk(self.lib.bbs_ctx_set_public_keys(self.h, n, _u8(buf), ident.ctypes.data_as(_lib.c_i8p),
+                                                   st.ctypes.data_as(_lib.c_i8p)), "bbs_ctx_set_public_keys")
+        return st[:n]
+
+    @staticmethod
+    def _key_index(key_index, n):
+        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32).reshape(-1))
+        if ki.size != n:
+            raise ValueError("key_index: %d entries for %d items" % (ki.size, n))
+        if not n:
+            ki = np.zeros(1, dtype=np.uint32)
+        return ki, ki.ctypes.data_as(_lib.c_u32p)
+
+    def _keyed_submit(self, fn, n, key_index, args, fixup=None) -> "Job":
+        ki, kp = self._key_index(key_index, n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        j = ctypes.c_void_p()
+        self._chk(getattr(self.lib, fn)(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), fn)
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._fixup = (lambda: fixup(st)) if fixup else None
+        return job
+
+    # keyed verification: item i under key key_index[i] of the key set (set_public_keys); -44 for an unknown key
+    def core_proof_verify_keyed_submit(self, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> "Job":
+        n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
+        return self._keyed_submit("bbs_core_proof_verify_keyed_submit", n, key_index, args)
+
+    def core_proof_verify_keyed_batch(self, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> np.ndarray:
+        n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
+        ki, kp = self._key_index(key_index, n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        self._chk(self.lib.bbs_core_proof_verify_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)),
+                  "bbs_core_proof_verify_keyed_batch")
+        return st[:n]
+
+    def proof_verify_wire_keyed_submit(self, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> "Job":
+        n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
+        return self._keyed_submit("bbs_proof_verify_wire_keyed_submit", n, key_index, args)
+
+    def proof_verify_wire_keyed_batch(self, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> np.ndarray:
+        n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
+        ki, kp = self._key_index(key_index, n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        self._chk(self.lib.bbs_proof_verify_wire_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)),
+                  "bbs_proof_verify_wire_keyed_batch")
+        return st[:n]
+
+    def _vf_core_args(self, signatures, messages, headers):
+        n = len(signatures)
+        sg = self._sigs(signatures) if n else np.zeros(1, dtype=np.uint8)
+        ms, mo = self._scalars(messages)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        return n, (sg, ms, mo, hb, ho), (_u8(sg), _u8(ms), _u64(mo), _u8(hb), _u64(ho))
+
+    def core_verify_keyed_submit(self, key_index, signatures, messages, headers=None) -> "Job":
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        return self._keyed_submit("bbs_core_verify_keyed_submit", n, key_index, args)
+
+    def core_verify_keyed_batch(self, key_index, signatures, messages, headers=None) -> np.ndarray:
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        ki, kp = self._key_index(key_index, n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        self._chk(self.lib.bbs_core_verify_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_core_verify_keyed_batch")
+        return st[:n]
+
+    def _vf_wire_args(self, sig_octets, messages_raw, headers):
+        n = len(sig_octets)
+        ob, bad = self._sig_octets(sig_octets)
+        mb, mbo, mio = self._raw_msgs(messages_raw)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        # a string of the wrong length travels as zeros and is -42 afterwards -- unless its key is unknown (-44 first)
+        fix = (lambda st: [st.__setitem__(i, -42) for i in bad if st[i] != -44]) if bad else None
+        return n, (ob, mb, mbo, mio, hb, ho), (_u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u8(hb), _u64(ho)), fix
+
+    def verify_wire_keyed_submit(self, key_index, sig_octets, messages_raw, headers=None) -> "Job":
+        n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
+        return self._keyed_submit("bbs_verify_wire_keyed_submit", n, key_index, args, fix)
+
+    def verify_wire_keyed_batch(self, key_index, sig_octets, messages_raw, headers=None) -> np.ndarray:
+        n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
+        ki, kp = self._key_index(key_index, n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        self._chk(self.lib.bbs_verify_wire_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_verify_wire_keyed_batch")
+        if fix:
+            fix(st)
+        return st[:n]
+
     def set_secret_key(self, sk: int):
         buf = _bytes_arr(self._fr(sk))
         self._chk(self.lib.bbs_ctx_set_secret_key(self.h, _u8(buf)), "bbs_ctx_set_secret_key")

@@ -63,6 +63,8 @@ extern "C" {
 #define BBS_ST_NO_RESOURCES (-43)            /* bbs_issuer_* only: the context of this item's message count could not be set
                                               * up (device memory, or every resident context busy at the context limit); the
                                               * item was NOT computed -- the other items of the call were; retry later */
+#define BBS_ST_UNKNOWN_KEY (-44)             /* keyed entry points only: the item's key index is >= the key set's size or names a
+                                              * key that bbs_ctx_set_public_keys refused; decided at ingest, never computed */
 
 /* batch-level errors */
 #define BBS_OK 0
@@ -305,6 +307,63 @@ int bbs_verify_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* signature_octe
 int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* signature_octets,
                           const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                           const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+
+/* ------------------------------------------------------------------------------------------
+ * Keyed verification: ONE context verifies items of MANY issuers.  The reference takes the public key per call
+ * (src/verify.rs:18-50, src/proof_verify.rs:19-61); here a context holds a KEY SET beside its generators and every item of a
+ * keyed batch names its key by index.  The fixed-base tables, which depend only on the generators and api_id, are shared by
+ * all keys; a key costs its W line table and its domain midstate (~30 KB of device memory on BLS12-381).
+ * ------------------------------------------------------------------------------------------ */
+/* n_keys issuer public keys (affine records as bbs_ctx_set_public_key; is_identity may be NULL = none).  key_status[k] (may
+ * be NULL): 1, or BBS_ST_NOT_ON_CURVE for a key bbs_ctx_set_public_key would refuse (not on the twist / not of order r).
+ * Replaces the context's previous key set; n_keys = 0 clears it.  Independent of bbs_ctx_set_public_key.  Needs the
+ * generators (BBS_E_STATE); bbs_ctx_set_generators clears the key set.  A set is immutable once built and every keyed job
+ * holds the set it was created with: replacing it while jobs are in flight does not change their results.  BBS_E_NOMEM if
+ * the set does not fit on the device (the previous set stays). */
+int bbs_ctx_set_public_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* pk_affine, const int8_t* is_identity,
+                            int8_t* key_status);
+/* Keyed forms of bbs_core_proof_verify_*, bbs_proof_verify_wire_*, bbs_core_verify_* and bbs_verify_wire_*: the arguments
+ * of the un-keyed form plus key_index (n entries) after n.  For an item whose key_index names an accepted key the status is
+ * what the un-keyed form gives on a context with the same generators, api_id, window bits and modes and that key set by
+ * bbs_ctx_set_public_key; for an index >= the set's size or naming a refused key it is BBS_ST_UNKNOWN_KEY.  BBS_E_STATE
+ * without generators or a key set, BBS_E_ARG for a NULL key_index with n > 0.  Batch verification
+ * (bbs_ctx_set_batch_verification) does not apply: every item gets its own pairing product.  The _submit forms return
+ * ordinary jobs (bbs_job_wait, bbs_jobs_wait_any, bbs_job_free). */
+int bbs_core_proof_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proofs_fixed,
+                                       const uint8_t* commitments, const uint64_t* commit_off,
+                                       const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
+                                       const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                       const uint8_t* headers, const uint64_t* hdr_off,
+                                       const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out);
+int bbs_core_proof_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proofs_fixed,
+                                      const uint8_t* commitments, const uint64_t* commit_off,
+                                      const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
+                                      const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                      const uint8_t* headers, const uint64_t* hdr_off,
+                                      const uint8_t* ph, const uint64_t* ph_off, int8_t* status);
+int bbs_proof_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proof_octets,
+                                       const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                       const uint64_t* msg_item_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                       const uint8_t* headers, const uint64_t* hdr_off,
+                                       const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out);
+int bbs_proof_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proof_octets,
+                                      const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                      const uint64_t* msg_item_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                      const uint8_t* headers, const uint64_t* hdr_off,
+                                      const uint8_t* ph, const uint64_t* ph_off, int8_t* status);
+int bbs_core_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
+                                 const uint8_t* messages, const uint64_t* msg_off,
+                                 const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out);
+int bbs_core_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
+                                const uint8_t* messages, const uint64_t* msg_off,
+                                const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+int bbs_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
+                                 const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                 const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out);
+int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
+                                const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+
 /* The reference's PUBLIC sign (src/sign.rs:32-60): raw messages in, signature octet strings out (as bbs_sign_octets_*). */
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                          const uint64_t* msg_item_off, const uint8_t* headers, const uint64_t* hdr_off,

@@ -271,4 +271,155 @@ inline std::vector<Result<bool>> proof_verify_batch(const PublicKey& pk, const s
     return out;
 }
 
+// ---- many issuers: one PublicKey per item (the reference's per-call key, src/verify.rs:18-50, src/proof_verify.rs:19-61) ----
+namespace detail {
+// one context per (curve, message count, device) holding a KEY SET (bbs_ctx_set_public_keys) instead of one key: the
+// fixed-base tables are built once for every issuer.  The set is the distinct keys of the last call; a call that brings a
+// key the set lacks registers the union (keys are never dropped while the context lives).
+struct KeyedCtx {
+    CtxPtr ctx;
+    std::mutex mu;                                    // one call at a time per context (the C ABI's rule)
+    std::map<std::string, uint32_t> index;            // key record (+ identity flag) -> position in the set
+    Bytes records;                                    // the set, n x 4 fp_bytes
+    std::vector<int8_t> identity;
+};
+inline std::shared_ptr<KeyedCtx> keyed_context(Curve c, size_t L, int device = 0) {
+    static std::mutex mu;
+    static std::map<std::string, std::shared_ptr<KeyedCtx>> cache;
+    const std::string k = std::to_string((int)c) + ":" + std::to_string(L) + ":" + std::to_string(device);
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cache.find(k);
+    if (it != cache.end()) return it->second;
+    const size_t fpb = bbs_fp_bytes((int)c);
+    const Bytes aid = api_id(c);
+    Bytes gens((L + 1) * 2 * fpb);
+    check(bbs_create_generators((int)c, L + 1, aid.data(), aid.size(), gens.data()), "bbs_create_generators");
+    bbs_ctx* raw = nullptr;
+    check(bbs_ctx_create((int)c, device, &raw), "bbs_ctx_create");
+    auto kc = std::make_shared<KeyedCtx>();
+    kc->ctx = CtxPtr(raw, CtxDeleter());
+    check(bbs_ctx_set_generators(raw, gens.data(), L + 1, aid.data(), aid.size()), "bbs_ctx_set_generators");
+    cache[k] = kc;
+    return kc;
+}
+// (under kc.mu) the key index of every item; registers the keys the set lacks.  A key bbs_ctx_set_public_key would
+// refuse throws, as the single-key functions do.
+inline std::vector<uint32_t> key_indexes(KeyedCtx& kc, Curve c, const std::vector<const PublicKey*>& pks) {
+    const size_t rec = 4 * bbs_fp_bytes((int)c);
+    std::vector<uint32_t> ki(pks.size());
+    const size_t before = kc.identity.size();
+    for (size_t i = 0; i < pks.size(); i++) {
+        const PublicKey& pk = *pks[i];
+        if (pk.curve != c || (!pk.identity && pk.pk.size() != rec)) throw std::runtime_error("public key of another curve or size");
+        std::string id(1, pk.identity ? 'i' : 'p');
+        if (!pk.identity) id.append(pk.pk.begin(), pk.pk.end());
+        auto it = kc.index.find(id);
+        if (it == kc.index.end()) {
+            it = kc.index.emplace(id, (uint32_t)kc.identity.size()).first;
+            if (pk.identity) kc.records.insert(kc.records.end(), rec, 0);
+            else kc.records.insert(kc.records.end(), pk.pk.begin(), pk.pk.end());
+            kc.identity.push_back(pk.identity ? 1 : 0);
+        }
+        ki[i] = it->second;
+    }
+    if (kc.identity.size() != before) {
+        std::vector<int8_t> st(kc.identity.size());
+        const int rc = bbs_ctx_set_public_keys(kc.ctx.get(), kc.identity.size(), kc.records.data(), kc.identity.data(), st.data());
+        if (rc != BBS_OK) { kc.index.clear(); kc.records.clear(); kc.identity.clear(); check(rc, "bbs_ctx_set_public_keys"); }
+        for (int8_t x : st)
+            if (x != 1) { kc.index.clear(); kc.records.clear(); kc.identity.clear(); bbs_ctx_set_public_keys(kc.ctx.get(), 0, nullptr, nullptr, nullptr);
+                          check(BBS_E_PUBLIC_KEY, "bbs_ctx_set_public_keys"); }
+    }
+    return ki;
+}
+inline std::vector<Result<bool>> bool_results(const std::vector<int8_t>& st, size_t n) {
+    std::vector<Result<bool>> out;
+    for (size_t i = 0; i < n; i++) {
+        raise_if_not_variant(st[i]);
+        out.push_back(st[i] >= 0 ? Result<bool>::ok(st[i] == 1) : Result<bool>::err(st[i]));
+    }
+    return out;
+}
+}  // namespace detail
+
+// proof_verify_batch with ONE PublicKey PER ITEM: element i is what proof_verify(pks[i], proofs[i], ...) returns.  One
+// context per (curve, message count, device) with a key set serves every issuer (bbs_core_proof_verify_keyed_batch).
+inline std::vector<Result<bool>> proof_verify_batch(const std::vector<PublicKey>& pks, const std::vector<Proof>& proofs,
+                                                    const std::vector<Bytes>& headers, const std::vector<Bytes>& phs,
+                                                    const std::vector<std::vector<Bytes>>& disclosed_msgs,
+                                                    const std::vector<std::vector<size_t>>& disclosed_indexes, size_t message_count) {
+    const size_t n = proofs.size();
+    if (pks.size() != n) throw std::runtime_error("proof_verify_batch: one public key per proof");
+    if (!n) return {};
+    const Curve c = pks[0].curve;
+    auto kc = detail::keyed_context(c, message_count);
+    std::lock_guard<std::mutex> g(kc->mu);
+    std::vector<const PublicKey*> pp;
+    for (const auto& k : pks) pp.push_back(&k);
+    const std::vector<uint32_t> ki = detail::key_indexes(*kc, c, pp);
+    std::vector<Bytes> all_msgs;
+    for (const auto& item : disclosed_msgs) all_msgs.insert(all_msgs.end(), item.begin(), item.end());
+    const Bytes dm = detail::msg_to_scalars(kc->ctx.get(), c, all_msgs);
+    Bytes fixed, cm, hb, pb;
+    std::vector<uint64_t> coff{0}, moff{0}, idx, ioff{0}, hoff{0}, poff{0};
+    for (size_t i = 0; i < n; i++) {
+        fixed.insert(fixed.end(), proofs[i].fixed.begin(), proofs[i].fixed.end());
+        cm.insert(cm.end(), proofs[i].commitments.begin(), proofs[i].commitments.end());
+        coff.push_back(cm.size() / 32);
+        moff.push_back(moff.back() + disclosed_msgs[i].size());
+        idx.insert(idx.end(), disclosed_indexes[i].begin(), disclosed_indexes[i].end());
+        ioff.push_back(idx.size());
+        hb.insert(hb.end(), headers[i].begin(), headers[i].end());
+        hoff.push_back(hb.size());
+        pb.insert(pb.end(), phs[i].begin(), phs[i].end());
+        poff.push_back(pb.size());
+    }
+    idx.push_back(0);
+    std::vector<int8_t> st(n, 0);
+    detail::check(bbs_core_proof_verify_keyed_batch(kc->ctx.get(), n, ki.data(), detail::ptr(fixed), detail::ptr(cm), coff.data(), detail::ptr(dm),
+                                                    moff.data(), idx.data(), ioff.data(), detail::ptr(hb), hoff.data(), detail::ptr(pb),
+                                                    poff.data(), st.data()),
+                  "bbs_core_proof_verify_keyed_batch");
+    return detail::bool_results(st, n);
+}
+
+// PublicKey::verify over n items, ONE PublicKey PER ITEM: element i is what pks[i].verify(sigs[i], headers[i], msgs[i])
+// returns.  Items are grouped by their number of messages, one keyed context per count (bbs_core_verify_keyed_batch).
+inline std::vector<Result<bool>> verify_batch(const std::vector<PublicKey>& pks, const std::vector<Signature>& sigs,
+                                              const std::vector<Bytes>& headers, const std::vector<std::vector<Bytes>>& msgs) {
+    const size_t n = sigs.size();
+    if (pks.size() != n || headers.size() != n || msgs.size() != n) throw std::runtime_error("verify_batch: one key, header, message list per signature");
+    std::vector<Result<bool>> out(n);
+    if (!n) return out;
+    const Curve c = pks[0].curve;
+    std::map<size_t, std::vector<size_t>> by_len;
+    for (size_t i = 0; i < n; i++) by_len[msgs[i].size()].push_back(i);
+    for (const auto& grp : by_len) {
+        const std::vector<size_t>& items = grp.second;
+        auto kc = detail::keyed_context(c, grp.first);
+        std::lock_guard<std::mutex> g(kc->mu);
+        std::vector<const PublicKey*> pp;
+        for (size_t i : items) pp.push_back(&pks[i]);
+        const std::vector<uint32_t> ki = detail::key_indexes(*kc, c, pp);
+        std::vector<Bytes> all;
+        Bytes sg, hb;
+        std::vector<uint64_t> moff{0}, hoff{0};
+        for (size_t i : items) {
+            all.insert(all.end(), msgs[i].begin(), msgs[i].end());
+            moff.push_back(all.size());
+            sg.insert(sg.end(), sigs[i].record.begin(), sigs[i].record.end());
+            hb.insert(hb.end(), headers[i].begin(), headers[i].end());
+            hoff.push_back(hb.size());
+        }
+        const Bytes sc = detail::msg_to_scalars(kc->ctx.get(), c, all);
+        std::vector<int8_t> st(items.size(), 0);
+        detail::check(bbs_core_verify_keyed_batch(kc->ctx.get(), items.size(), ki.data(), detail::ptr(sg), detail::ptr(sc), moff.data(),
+                                                  detail::ptr(hb), hoff.data(), st.data()),
+                      "bbs_core_verify_keyed_batch");
+        const auto r = detail::bool_results(st, items.size());
+        for (size_t t = 0; t < items.size(); t++) out[items[t]] = r[t];
+    }
+    return out;
+}
+
 }  // namespace bbs_plus
