@@ -46,9 +46,26 @@ extern "C" __attribute__((visibility("default"))) int bbs_runtime_queue_budget(i
 // =============================================================================================
 // C ABI
 // =============================================================================================
-#define DISPATCH(ctx, expr_bls, expr_bn) ((ctx)->curve == BBS_CURVE_BLS12_381 ? (expr_bls) : (expr_bn))
-#define AS_BLS(ctx) static_cast<Ctx<BlsCurve>*>(ctx)
-#define AS_BN(ctx) static_cast<Ctx<BnCurve>*>(ctx)
+// The one curve dispatch: hands the context, typed by its curve, to a generic callable, so that every argument list is
+// written once.  curve_of<decltype(c)> names the curve inside such a callable where it cannot be deduced from c.
+template <class F>
+static decltype(auto) with_curve(bbs_ctx* ctx, F&& f) {
+    return ctx->curve == BBS_CURVE_BLS12_381 ? f(static_cast<Ctx<BlsCurve>*>(ctx)) : f(static_cast<Ctx<BnCurve>*>(ctx));
+}
+template <class P> struct curve_of_ctx;
+template <class C> struct curve_of_ctx<Ctx<C>*> { using type = C; };
+template <class P> using curve_of = typename curve_of_ctx<P>::type;
+// an input descriptor (ops_decl.hpp) to the upload template of its operation and of the context's curve
+template <bool KEYED = false>
+static int upload(bbs_ctx* ctx, size_t n, const PvIn& in, bbs_job** job) {
+    return with_curve(ctx, [&](auto* c) { return pv_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
+}
+template <bool KEYED = false>
+static int upload(bbs_ctx* ctx, size_t n, const VfIn& in, bbs_job** job) {
+    return with_curve(ctx, [&](auto* c) { return vf_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
+}
+static int upload(bbs_ctx* ctx, size_t n, const SgIn& in, bbs_job** job) { return with_curve(ctx, [&](auto* c) { return sg_upload(c, n, in, job); }); }
+static int upload(bbs_ctx* ctx, size_t n, const PgIn& in, bbs_job** job) { return with_curve(ctx, [&](auto* c) { return pg_upload(c, n, in, job); }); }
 
 // ---- host-side helpers shared by both curves --------------------------------------------------
 template <class C>
@@ -236,6 +253,95 @@ static int proofs_to_octets_batch(size_t n, const uint8_t* pf, const uint8_t* cm
     return BBS_OK;
 }
 
+// ---- the submit path shared by the *_submit / *_batch entry points ---------------------------------
+// upload (one asynchronous H2D copy + the ingest kernel) -> kernels -> asynchronous copy of the statuses to page-locked
+// memory; nothing waits for the device.  bbs_job_wait delivers the statuses to `status`.
+// The ONE submit epilogue of every *_submit entry point: run the stages, enqueue the copy of the statuses (sign / proof_gen:
+// and of the produced records) to page-locked memory behind them, arm the completion notification behind that, and only
+// then let the job know where bbs_job_wait has to deliver.  On any failure the job is freed and nothing is handed out.
+// (bbs_job_wait refuses with BBS_E_STATE if an item was left undecided: fail closed, tested for every entry point.)
+static int submit_with_results(bbs_job* job, int8_t* status, uint8_t* o1, uint8_t* o2, uint64_t* o3, bbs_job** job_out) {
+    job->hold_arm = true;
+    int rc = job->run();
+    job->hold_arm = false;
+    if (!rc) rc = job->enqueue_status_fetch();
+    if (!rc && (o1 || o2 || o3)) rc = job->enqueue_result_fetch();
+    if (!rc) rc = job->arm_completion();
+    if (rc) { delete job; return rc; }
+    job->deliver_to = status;
+    job->results_wanted = o1 || o2 || o3;
+    job->set_result_targets(o1, o2, o3);
+    *job_out = job;
+    return BBS_OK;
+}
+// the *_batch forms: submit, wait, free
+static int wait_and_free(int rc_submit, bbs_job* const& job) {      // by reference: read after the submit call has set it
+    if (rc_submit) return rc_submit;
+    const int rc = job->wait();
+    delete job;
+    return rc;
+}
+// the tail of every verify-family *_submit: descriptor -> with_curve -> *_upload -> submit_with_results
+template <bool KEYED, class In>
+static int verify_submit(bbs_ctx* ctx, size_t n, const In& in, int8_t* status, bbs_job** job_out) {
+    bbs_job* job = nullptr;
+    if (int rc = upload<KEYED>(ctx, n, in, &job)) return rc;
+    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+}
+// raw messages, but the whole batch has none: msg_byte_off may be null then, and is pointed at one zero that is never indexed
+static int empty_raw_batch(const uint64_t*& msg_byte_off, const uint64_t* msg_item_off, size_t n) {
+    if (msg_byte_off) return BBS_OK;
+    if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
+    msg_byte_off = zero_off1();
+    return BBS_OK;
+}
+// Each single-key export and its keyed twin (keyed.hpp: the context's key set instead of its one public key, item i under
+// key key_index[i]) are one function; the single-key export passes no key_index.
+template <bool KEYED>
+static int core_proof_verify_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proofs_fixed,
+                                    const uint8_t* commitments, const uint64_t* commit_off, const uint8_t* disclosed_msgs,
+                                    const uint64_t* dmsg_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                    const uint8_t* headers, const uint64_t* hdr_off, const uint8_t* ph, const uint64_t* ph_off,
+                                    int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    return verify_submit<KEYED>(ctx, n, PvIn{.proofs_fixed = proofs_fixed, .commitments = commitments, .commit_off = commit_off,
+                                             .disclosed_msgs = disclosed_msgs, .dmsg_off = dmsg_off, .disclosed_idx = disclosed_idx,
+                                             .didx_off = didx_off, .headers = headers, .hdr_off = hdr_off, .ph = ph, .ph_off = ph_off,
+                                             .key_index = key_index}, status, job_out);
+}
+// the public proof_verify of the reference for a fixed number of messages, in one call: proof octets AND the disclosed
+// messages as raw bytes (msg_to_scalars on the device in front of the ingest stage)
+template <bool KEYED>
+static int proof_verify_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proof_octets, const uint64_t* oct_off,
+                                    const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                    const uint64_t* disclosed_idx, const uint64_t* didx_off, const uint8_t* headers, const uint64_t* hdr_off,
+                                    const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out || (n && (!oct_off || !msg_item_off))) return BBS_E_ARG;
+    if (int rc = empty_raw_batch(msg_byte_off, msg_item_off, n)) return rc;
+    return verify_submit<KEYED>(ctx, n, PvIn{.dmsg_off = msg_item_off, .disclosed_idx = disclosed_idx, .didx_off = didx_off,
+                                             .headers = headers, .hdr_off = hdr_off, .ph = ph, .ph_off = ph_off,
+                                             .proof_octets = proof_octets, .oct_off = oct_off, .msg_bytes = msg_bytes,
+                                             .msg_byte_off = msg_byte_off, .key_index = key_index}, status, job_out);
+}
+template <bool KEYED>
+static int core_verify_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures, const uint8_t* messages,
+                              const uint64_t* msg_off, const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    return verify_submit<KEYED>(ctx, n, VfIn{.signatures = signatures, .messages = messages, .msg_off = msg_off, .headers = headers,
+                                             .hdr_off = hdr_off, .key_index = key_index}, status, job_out);
+}
+// the reference's PUBLIC verify for a context's number of messages, in one call: signature octet strings and raw messages
+// in (msg_to_scalars on the device)
+template <bool KEYED>
+static int verify_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets, const uint8_t* msg_bytes,
+                              const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* headers, const uint64_t* hdr_off,
+                              int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out || (n && (!signature_octets || !msg_item_off))) return BBS_E_ARG;
+    if (int rc = empty_raw_batch(msg_byte_off, msg_item_off, n)) return rc;
+    return verify_submit<KEYED>(ctx, n, VfIn{.msg_off = msg_item_off, .headers = headers, .hdr_off = hdr_off, .signature_octets = signature_octets,
+                                             .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off, .key_index = key_index}, status, job_out);
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -278,27 +384,27 @@ void bbs_ctx_destroy(bbs_ctx* ctx) { delete ctx; }
 int bbs_ctx_set_window_bits(bbs_ctx* ctx, int bits) {
     if (!ctx || (bits != 0 && (bits < 4 || bits > 22))) return BBS_E_ARG;      // 0: chosen from the free device memory at set_generators
     // (takes effect at the next bbs_ctx_set_generators; the width of tables already built does not change)
-    if (ctx->curve == BBS_CURVE_BLS12_381) AS_BLS(ctx)->win_bits_requested = bits; else AS_BN(ctx)->win_bits_requested = bits;
+    with_curve(ctx, [&](auto* c) { c->win_bits_requested = bits; });
     return BBS_OK;
 }
 int bbs_ctx_set_batch_verification(bbs_ctx* ctx, int enabled, const uint8_t* seed32) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->set_batch_verification(enabled, seed32), AS_BN(ctx)->set_batch_verification(enabled, seed32));
+    return with_curve(ctx, [&](auto* c) { return c->set_batch_verification(enabled, seed32); });
 }
 int bbs_ctx_set_points_in_subgroup(bbs_ctx* ctx, int vouched) {
     if (!ctx) return BBS_E_ARG;
-    if (ctx->curve == BBS_CURVE_BLS12_381) AS_BLS(ctx)->points_in_subgroup = vouched != 0; else AS_BN(ctx)->points_in_subgroup = vouched != 0;
+    with_curve(ctx, [&](auto* c) { c->points_in_subgroup = vouched != 0; });
     return BBS_OK;
 }
 int bbs_ctx_set_latency_mode(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     if (enabled < 0 || enabled > 2) return BBS_E_ARG;
-    if (ctx->curve == BBS_CURVE_BLS12_381) AS_BLS(ctx)->latency_mode = enabled; else AS_BN(ctx)->latency_mode = enabled;
+    with_curve(ctx, [&](auto* c) { c->latency_mode = enabled; });
     return BBS_OK;
 }
 int bbs_ctx_set_fixed_base_tree(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
-    if (ctx->curve == BBS_CURVE_BLS12_381) AS_BLS(ctx)->fix_tree = enabled != 0; else AS_BN(ctx)->fix_tree = enabled != 0;
+    with_curve(ctx, [&](auto* c) { c->fix_tree = enabled != 0; });
     return BBS_OK;
 }
 int bbs_selftest_glv_split(int curve, const uint8_t* k32, uint8_t* k1_16, uint8_t* k2_16, int* neg1, int* neg2) {
@@ -326,57 +432,54 @@ int bbs_selftest_mul3(int curve, int glv, const uint8_t* points, const uint8_t* 
 }
 int bbs_ctx_set_generators(bbs_ctx* ctx, const uint8_t* g, size_t count, const uint8_t* api_id, size_t api_id_len) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->set_generators(g, count, api_id, api_id_len), AS_BN(ctx)->set_generators(g, count, api_id, api_id_len));
+    return with_curve(ctx, [&](auto* c) { return c->set_generators(g, count, api_id, api_id_len); });
 }
 int bbs_ctx_set_public_key(bbs_ctx* ctx, const uint8_t* pk, int is_identity) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->set_public_key(pk, is_identity), AS_BN(ctx)->set_public_key(pk, is_identity));
+    return with_curve(ctx, [&](auto* c) { return c->set_public_key(pk, is_identity); });
 }
 int bbs_ctx_set_secret_key(bbs_ctx* ctx, const uint8_t* sk32) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->set_secret_key(sk32), AS_BN(ctx)->set_secret_key(sk32));
+    return with_curve(ctx, [&](auto* c) { return c->set_secret_key(sk32); });
 }
 int bbs_ctx_get_public_key(bbs_ctx* ctx, uint8_t* out, int* inf) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->get_public_key(out, inf), AS_BN(ctx)->get_public_key(out, inf));
+    return with_curve(ctx, [&](auto* c) { return c->get_public_key(out, inf); });
 }
 int bbs_ctx_get_public_key_compressed(bbs_ctx* ctx, uint8_t* out, size_t cap, size_t* len_out) {
     if (!ctx || !out) return BBS_E_ARG;
     const size_t need = 2 * bbs_fp_bytes(ctx->curve);
     if (cap < need) return BBS_E_ARG;
-    if (ctx->curve == BBS_CURVE_BLS12_381) {
-        if (!AS_BLS(ctx)->pk_set) return BBS_E_STATE;
-        g2_compress<BlsCurve>(AS_BLS(ctx)->pk, out);
-    } else {
-        if (!AS_BN(ctx)->pk_set) return BBS_E_STATE;
-        g2_compress<BnCurve>(AS_BN(ctx)->pk, out);
-    }
-    if (len_out) *len_out = need;
-    return BBS_OK;
+    return with_curve(ctx, [&](auto* c) {
+        if (!c->pk_set) return BBS_E_STATE;
+        g2_compress(c->pk, out);
+        if (len_out) *len_out = need;
+        return BBS_OK;
+    });
 }
 
 int bbs_core_proof_verify_upload(bbs_ctx* ctx, size_t n, const uint8_t* pf, const uint8_t* cm, const uint64_t* cmo,
                                  const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
                                  const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, bbs_job** job) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, pv_upload<BlsCurve>(AS_BLS(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, job, nullptr, nullptr, nullptr, nullptr),
-                    pv_upload<BnCurve>(AS_BN(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, job, nullptr, nullptr, nullptr, nullptr));
+    return upload(ctx, n, PvIn{.proofs_fixed = pf, .commitments = cm, .commit_off = cmo, .disclosed_msgs = dm, .dmsg_off = dmo, .disclosed_idx = di,
+                               .didx_off = dio, .headers = h, .hdr_off = ho, .ph = ph, .ph_off = pho}, job);
 }
 int bbs_core_verify_upload(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                            const uint8_t* h, const uint64_t* ho, bbs_job** job) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, vf_upload<BlsCurve>(AS_BLS(ctx), n, sigs, m, mo, h, ho, job, nullptr, nullptr, nullptr), vf_upload<BnCurve>(AS_BN(ctx), n, sigs, m, mo, h, ho, job, nullptr, nullptr, nullptr));
+    return upload(ctx, n, VfIn{.signatures = sigs, .messages = m, .msg_off = mo, .headers = h, .hdr_off = ho}, job);
 }
 int bbs_core_sign_upload(bbs_ctx* ctx, size_t n, const uint8_t* m, const uint64_t* mo, const uint8_t* h, const uint64_t* ho, bbs_job** job) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, sg_upload<BlsCurve>(AS_BLS(ctx), n, m, mo, h, ho, job, nullptr, nullptr), sg_upload<BnCurve>(AS_BN(ctx), n, m, mo, h, ho, job, nullptr, nullptr));
+    return upload(ctx, n, SgIn{.messages = m, .msg_off = mo, .headers = h, .hdr_off = ho}, job);
 }
 int bbs_core_proof_gen_upload(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                               const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
                               const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, bbs_job** job) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, pg_upload<BlsCurve>(AS_BLS(ctx), n, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho, job, nullptr, nullptr, nullptr),
-                    pg_upload<BnCurve>(AS_BN(ctx), n, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho, job, nullptr, nullptr, nullptr));
+    return upload(ctx, n, PgIn{.signatures = sigs, .messages = m, .msg_off = mo, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd,
+                               .rnd_off = rno, .headers = h, .hdr_off = ho, .ph = ph, .ph_off = pho}, job);
 }
 
 size_t bbs_device_free_bytes(int device_id) {
@@ -495,42 +598,11 @@ int bbs_job_stage_times(bbs_job* job, float* total_ms, float* kernel_ms, int cap
     return job ? job->stage_times(total_ms, kernel_ms, cap, n_stages) : BBS_E_ARG;
 }
 
-// upload (one asynchronous H2D copy + the ingest kernel) -> kernels -> asynchronous copy of the statuses to page-locked
-// memory; nothing waits for the device.  bbs_job_wait delivers the statuses to `status`.
-// The ONE submit epilogue of every *_submit entry point: run the stages, enqueue the copy of the statuses (sign / proof_gen:
-// and of the produced records) to page-locked memory behind them, arm the completion notification behind that, and only
-// then let the job know where bbs_job_wait has to deliver.  On any failure the job is freed and nothing is handed out.
-// (bbs_job_wait refuses with BBS_E_STATE if an item was left undecided: fail closed, tested for every entry point.)
-static int submit_with_results(bbs_job* job, int8_t* status, uint8_t* o1, uint8_t* o2, uint64_t* o3, bbs_job** job_out) {
-    job->hold_arm = true;
-    int rc = job->run();
-    job->hold_arm = false;
-    if (!rc) rc = job->enqueue_status_fetch();
-    if (!rc && (o1 || o2 || o3)) rc = job->enqueue_result_fetch();
-    if (!rc) rc = job->arm_completion();
-    if (rc) { delete job; return rc; }
-    job->deliver_to = status;
-    job->results_wanted = o1 || o2 || o3;
-    job->set_result_targets(o1, o2, o3);
-    *job_out = job;
-    return BBS_OK;
-}
-// the *_batch forms: submit, wait, free
-static int wait_and_free(int rc_submit, bbs_job* const& job) {      // by reference: read after the submit call has set it
-    if (rc_submit) return rc_submit;
-    const int rc = job->wait();
-    delete job;
-    return rc;
-}
 int bbs_core_proof_verify_submit(bbs_ctx* ctx, size_t n, const uint8_t* pf, const uint8_t* cm, const uint64_t* cmo,
                                  const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
                                  const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
                                  bbs_job** job_out) {
-    if (!status || !job_out) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = bbs_core_proof_verify_upload(ctx, n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, &job);
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return core_proof_verify_submit<false>(ctx, n, nullptr, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, status, job_out);
 }
 int bbs_core_proof_verify_batch(bbs_ctx* ctx, size_t n, const uint8_t* pf, const uint8_t* cm, const uint64_t* cmo,
                                 const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
@@ -544,30 +616,15 @@ int bbs_proof_verify_octets_submit(bbs_ctx* ctx, size_t n, const uint8_t* oct, c
                                    const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
                                    bbs_job** job_out) {
     if (!ctx || !status || !job_out || (n && !oct_off)) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, pv_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, nullptr, nullptr, dm, dmo, di, dio, h, ho, ph, pho, &job, oct, oct_off, nullptr, nullptr),
-                      pv_upload<BnCurve>(AS_BN(ctx), n, nullptr, nullptr, nullptr, dm, dmo, di, dio, h, ho, ph, pho, &job, oct, oct_off, nullptr, nullptr));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return verify_submit<false>(ctx, n, PvIn{.disclosed_msgs = dm, .dmsg_off = dmo, .disclosed_idx = di, .didx_off = dio, .headers = h,
+                                             .hdr_off = ho, .ph = ph, .ph_off = pho, .proof_octets = oct, .oct_off = oct_off}, status, job_out);
 }
-// the public proof_verify of the reference for a fixed number of messages, in one call: proof octets AND the disclosed
-// messages as raw bytes (msg_to_scalars on the device in front of the ingest stage)
 int bbs_proof_verify_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* oct, const uint64_t* oct_off,
                                  const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                                  const uint64_t* di, const uint64_t* dio,
                                  const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
                                  bbs_job** job_out) {
-    if (!ctx || !status || !job_out || (n && (!oct_off || !msg_item_off))) return BBS_E_ARG;
-    static const uint64_t zero_off[1] = {0};
-    if (!msg_byte_off) {                                  // no disclosed message in the whole batch
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = zero_off;
-    }
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, pv_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off),
-                      pv_upload<BnCurve>(AS_BN(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return proof_verify_wire_submit<false>(ctx, n, nullptr, oct, oct_off, msg_bytes, msg_byte_off, msg_item_off, di, dio, h, ho, ph, pho, status, job_out);
 }
 int bbs_proof_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* oct, const uint64_t* oct_off,
                                 const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
@@ -584,64 +641,39 @@ int bbs_proof_verify_octets_batch(bbs_ctx* ctx, size_t n, const uint8_t* oct, co
 }
 int bbs_core_verify_submit(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                            const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
-    if (!status || !job_out) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = bbs_core_verify_upload(ctx, n, sigs, m, mo, h, ho, &job);
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return core_verify_submit<false>(ctx, n, nullptr, sigs, m, mo, h, ho, status, job_out);
 }
 // verify from the wire: signature octet strings (compress(A) || e) decoded and checked on the device in front of
 // core_verify; statuses as bbs_signature_from_octets followed by core_verify would give them
 int bbs_verify_octets_submit(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* m, const uint64_t* mo,
                              const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
     if (!ctx || !status || !job_out || (n && !sig_octets)) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, vf_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, m, mo, h, ho, &job, sig_octets, nullptr, nullptr),
-                      vf_upload<BnCurve>(AS_BN(ctx), n, nullptr, m, mo, h, ho, &job, sig_octets, nullptr, nullptr));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return verify_submit<false>(ctx, n, VfIn{.messages = m, .msg_off = mo, .headers = h, .hdr_off = ho, .signature_octets = sig_octets}, status, job_out);
 }
 int bbs_verify_octets_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* m, const uint64_t* mo,
                             const uint8_t* h, const uint64_t* ho, int8_t* status) {
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_octets_submit(ctx, n, sig_octets, m, mo, h, ho, status, &job), job);
 }
-// the reference's PUBLIC verify / sign for a context's number of messages, in one call: raw messages in (msg_to_scalars on
-// the device), signatures as octet strings in (verify) / out (sign)
-static const uint64_t BBS_ZERO_OFF[1] = {0};
 int bbs_verify_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                            const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out || (n && (!sig_octets || !msg_item_off))) return BBS_E_ARG;
-    if (!msg_byte_off) {
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = BBS_ZERO_OFF;
-    }
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, vf_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off),
-                      vf_upload<BnCurve>(AS_BN(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return verify_wire_submit<false>(ctx, n, nullptr, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, job_out);
 }
 int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                           const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, int8_t* status) {
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_submit(ctx, n, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
-// keyed verification (keyed.hpp): the context's key set instead of its one public key, item i under key key_index[i]
+// keyed verification (keyed.hpp)
 int bbs_ctx_set_public_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* pk, const int8_t* is_identity, int8_t* key_status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, AS_BLS(ctx)->set_public_keys(n_keys, pk, is_identity, key_status), AS_BN(ctx)->set_public_keys(n_keys, pk, is_identity, key_status));
+    return with_curve(ctx, [&](auto* c) { return c->set_public_keys(n_keys, pk, is_identity, key_status); });
 }
 int bbs_core_proof_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* pf, const uint8_t* cm,
                                        const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
                                        const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
                                        bbs_job** job_out) {
-    if (!ctx || !status || !job_out) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, (pv_upload<BlsCurve, true>(AS_BLS(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, &job, nullptr, nullptr, nullptr, nullptr, key_index)),
-                      (pv_upload<BnCurve, true>(AS_BN(ctx), n, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, &job, nullptr, nullptr, nullptr, nullptr, key_index)));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return core_proof_verify_submit<true>(ctx, n, key_index, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, status, job_out);
 }
 int bbs_core_proof_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* pf, const uint8_t* cm,
                                       const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
@@ -654,16 +686,7 @@ int bbs_proof_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* k
                                        const uint64_t* di, const uint64_t* dio,
                                        const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status,
                                        bbs_job** job_out) {
-    if (!ctx || !status || !job_out || (n && (!oct_off || !msg_item_off))) return BBS_E_ARG;
-    if (!msg_byte_off) {                                  // no disclosed message in the whole batch
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = BBS_ZERO_OFF;
-    }
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, (pv_upload<BlsCurve, true>(AS_BLS(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off, key_index)),
-                      (pv_upload<BnCurve, true>(AS_BN(ctx), n, nullptr, nullptr, nullptr, nullptr, msg_item_off, di, dio, h, ho, ph, pho, &job, oct, oct_off, msg_bytes, msg_byte_off, key_index)));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return proof_verify_wire_submit<true>(ctx, n, key_index, oct, oct_off, msg_bytes, msg_byte_off, msg_item_off, di, dio, h, ho, ph, pho, status, job_out);
 }
 int bbs_proof_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* oct, const uint64_t* oct_off,
                                       const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
@@ -674,12 +697,7 @@ int bbs_proof_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* ke
 }
 int bbs_core_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                                  const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, (vf_upload<BlsCurve, true>(AS_BLS(ctx), n, sigs, m, mo, h, ho, &job, nullptr, nullptr, nullptr, key_index)),
-                      (vf_upload<BnCurve, true>(AS_BN(ctx), n, sigs, m, mo, h, ho, &job, nullptr, nullptr, nullptr, key_index)));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return core_verify_submit<true>(ctx, n, key_index, sigs, m, mo, h, ho, status, job_out);
 }
 int bbs_core_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                                 const uint8_t* h, const uint64_t* ho, int8_t* status) {
@@ -689,32 +707,21 @@ int bbs_core_verify_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
 int bbs_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
                                  const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho,
                                  int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out || (n && (!sig_octets || !msg_item_off))) return BBS_E_ARG;
-    if (!msg_byte_off) {
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = BBS_ZERO_OFF;
-    }
-    bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, (vf_upload<BlsCurve, true>(AS_BLS(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off, key_index)),
-                      (vf_upload<BnCurve, true>(AS_BN(ctx), n, nullptr, nullptr, msg_item_off, h, ho, &job, sig_octets, msg_bytes, msg_byte_off, key_index)));
-    if (rc) return rc;
-    return submit_with_results(job, status, nullptr, nullptr, nullptr, job_out);
+    return verify_wire_submit<true>(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, job_out);
 }
 int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
                                 const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, int8_t* status) {
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
+// the reference's PUBLIC sign: raw messages in (msg_to_scalars on the device), signatures as octet strings out
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                          const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status, bbs_job** job_out) {
     if (!ctx || !status || !job_out || (n && (!sig_octets_out || !msg_item_off))) return BBS_E_ARG;
-    if (!msg_byte_off) {
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = BBS_ZERO_OFF;
-    }
+    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
+    if (rc) return rc;
     bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, sg_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, msg_item_off, h, ho, &job, msg_bytes, msg_byte_off),
-                      sg_upload<BnCurve>(AS_BN(ctx), n, nullptr, msg_item_off, h, ho, &job, msg_bytes, msg_byte_off));
+    rc = upload(ctx, n, SgIn{.msg_off = msg_item_off, .headers = h, .hdr_off = ho, .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off}, &job);
     if (rc) return rc;
     if ((rc = job->set_octet_form())) { delete job; return rc; }
     return submit_with_results(job, status, sig_octets_out, nullptr, nullptr, job_out);
@@ -786,13 +793,12 @@ int bbs_proof_gen_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets,
                               const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
                               uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
     if (!ctx || !status || !job_out || !oct_off_out || (n && (!octets_out || !sig_octets || !msg_item_off))) return BBS_E_ARG;
-    if (!msg_byte_off) {
-        if (n && msg_item_off[n] != msg_item_off[0]) return BBS_E_ARG;
-        msg_byte_off = BBS_ZERO_OFF;
-    }
+    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
+    if (rc) return rc;
     bbs_job* job = nullptr;
-    int rc = DISPATCH(ctx, pg_upload<BlsCurve>(AS_BLS(ctx), n, nullptr, nullptr, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho, &job, sig_octets, msg_bytes, msg_byte_off),
-                      pg_upload<BnCurve>(AS_BN(ctx), n, nullptr, nullptr, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho, &job, sig_octets, msg_bytes, msg_byte_off));
+    rc = upload(ctx, n, PgIn{.msg_off = msg_item_off, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd, .rnd_off = rno, .headers = h,
+                             .hdr_off = ho, .ph = ph, .ph_off = pho, .signature_octets = sig_octets, .msg_bytes = msg_bytes,
+                             .msg_byte_off = msg_byte_off}, &job);
     if (rc) return rc;
     if ((rc = job->set_octet_form())) { delete job; return rc; }
     return submit_with_results(job, status, octets_out, nullptr, oct_off_out, job_out);
@@ -841,17 +847,17 @@ int bbs_core_proof_gen_batch(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const 
 // ---- unit-parity primitives -------------------------------------------------------------------
 int bbs_hash_to_scalar_batch(bbs_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* off, const uint8_t* dst, size_t dst_len, uint8_t* out) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, h2s_batch<BlsCurve>(AS_BLS(ctx), n, msgs, off, dst, dst_len, out), h2s_batch<BnCurve>(AS_BN(ctx), n, msgs, off, dst, dst_len, out));
+    return with_curve(ctx, [&](auto* c) { return h2s_batch(c, n, msgs, off, dst, dst_len, out); });
 }
 
 int bbs_g1_msm_batch(bbs_ctx* ctx, size_t n, const uint8_t* fs, size_t nf, const uint8_t* vp, const uint8_t* vs, size_t nv, uint8_t* out, int8_t* status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, msm_batch<BlsCurve>(AS_BLS(ctx), n, fs, nf, vp, vs, nv, out, status), msm_batch<BnCurve>(AS_BN(ctx), n, fs, nf, vp, vs, nv, out, status));
+    return with_curve(ctx, [&](auto* c) { return msm_batch(c, n, fs, nf, vp, vs, nv, out, status); });
 }
 
 int bbs_g1_msm_pippenger(bbs_ctx* ctx, size_t n, const uint8_t* pts, const uint8_t* scal, uint8_t* out, int* out_inf, int8_t* status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, msm_pippenger<BlsCurve>(AS_BLS(ctx), n, pts, scal, out, out_inf, status), msm_pippenger<BnCurve>(AS_BN(ctx), n, pts, scal, out, out_inf, status));
+    return with_curve(ctx, [&](auto* c) { return msm_pippenger(c, n, pts, scal, out, out_inf, status); });
 }
 
 // ---- host-side setup helpers (once per ciphersuite / key; no GPU involved) ---------------------
@@ -1028,13 +1034,11 @@ int bbs_proof_from_octets(int curve, const uint8_t* octets, size_t len, uint8_t*
 }
 int bbs_g1_decompress_batch(bbs_ctx* ctx, size_t n, const uint8_t* compressed, uint8_t* out_affine, int8_t* code) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, g1_decompress_batch<BlsCurve>(AS_BLS(ctx), n, compressed, out_affine, code),
-                    g1_decompress_batch<BnCurve>(AS_BN(ctx), n, compressed, out_affine, code));
+    return with_curve(ctx, [&](auto* c) { return g1_decompress_batch(c, n, compressed, out_affine, code); });
 }
 int bbs_signatures_from_octets_batch(bbs_ctx* ctx, size_t n, const uint8_t* octets, uint8_t* sig_records_out, int8_t* status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, signatures_from_octets_batch<BlsCurve>(AS_BLS(ctx), n, octets, sig_records_out, status),
-                    signatures_from_octets_batch<BnCurve>(AS_BN(ctx), n, octets, sig_records_out, status));
+    return with_curve(ctx, [&](auto* c) { return signatures_from_octets_batch(c, n, octets, sig_records_out, status); });
 }
 int bbs_proofs_to_octets_batch(int curve, size_t n, const uint8_t* pf, const uint8_t* cm, const uint64_t* cm_off, uint8_t* out, uint64_t* out_off,
                                int8_t* status) {
@@ -1045,8 +1049,7 @@ int bbs_proofs_to_octets_batch(int curve, size_t n, const uint8_t* pf, const uin
 int bbs_proofs_from_octets_batch(bbs_ctx* ctx, size_t n, const uint8_t* octets, const uint64_t* oct_off, uint8_t* pf_out, uint8_t* cm_out,
                                  uint64_t* cm_off_out, int8_t* status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, proofs_from_octets_batch<BlsCurve>(AS_BLS(ctx), n, octets, oct_off, pf_out, cm_out, cm_off_out, status),
-                    proofs_from_octets_batch<BnCurve>(AS_BN(ctx), n, octets, oct_off, pf_out, cm_out, cm_off_out, status));
+    return with_curve(ctx, [&](auto* c) { return proofs_from_octets_batch(c, n, octets, oct_off, pf_out, cm_out, cm_off_out, status); });
 }
 int bbs_public_key_to_octets(int curve, const uint8_t* pk_affine, int is_identity, uint8_t* out) {
     if (!CURVE_OK(curve) || !out || (!is_identity && !pk_affine)) return BBS_E_ARG;
@@ -1059,7 +1062,7 @@ int bbs_public_key_from_octets(int curve, const uint8_t* octets, uint8_t* pk_aff
 
 int bbs_selftest_f12(bbs_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* out_single, uint8_t* out_dist) {
     if (!ctx || !a || !b || !out_single || !out_dist) return BBS_E_ARG;
-    return DISPATCH(ctx, selftest_f12<BlsCurve>(AS_BLS(ctx), op, a, b, out_single, out_dist), selftest_f12<BnCurve>(AS_BN(ctx), op, a, b, out_single, out_dist));
+    return with_curve(ctx, [&](auto* c) { return selftest_f12(c, op, a, b, out_single, out_dist); });
 }
 
 int bbs_selftest_inv(int curve, int scalar_field, const uint8_t* x, uint8_t* out_safegcd, uint8_t* out_fermat) {
@@ -1421,7 +1424,7 @@ int bbs_issuer_proof_gen(bbs_issuer* is, size_t n, const uint8_t* sig_octets, co
 
 int bbs_pairing_product2_is_one_batch(bbs_ctx* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, int8_t* status) {
     if (!ctx) return BBS_E_ARG;
-    return DISPATCH(ctx, pairing_batch<BlsCurve>(AS_BLS(ctx), n, pa, pb, status), pairing_batch<BnCurve>(AS_BN(ctx), n, pa, pb, status));
+    return with_curve(ctx, [&](auto* c) { return pairing_batch(c, n, pa, pb, status); });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Host orchestration of one batched operation (template over the curve); instantiated by the
 // per-curve translation units tu_*.hip so the library builds in parallel.
 #pragma once
-#include "runtime.hpp"
+#include "ops_decl.hpp"
 
 // ---- proof_gen ---------------------------------------------------------------------------------
 template <class C>
@@ -86,31 +86,26 @@ struct PgJob : JobBase<C> {
 };
 
 template <class C>
-int pg_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
-                     const uint64_t* didx, const uint64_t* didx_off, const uint8_t* rnd, const uint64_t* rnd_off,
-                     const uint8_t* headers, const uint64_t* hdr_off, const uint8_t* ph, const uint64_t* ph_off,
-                     bbs_job** out, const uint8_t* sig_octets, const uint8_t* msg_bytes, const uint64_t* msg_byte_off) {
-    // sig_octets != nullptr: the signatures arrive as octet strings compress(A) || e (decoded and subgroup-checked on the
-    // device, `sigs` ignored); msg_byte_off != nullptr: the messages arrive as raw bytes (see vf_upload)
+int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
     if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
-    const bool wire = sig_octets != nullptr, raw = msg_byte_off != nullptr;
-    if (!out || (n && ((!sigs && !wire) || !msg_off || !didx_off || !rnd_off || !rnd))) return BBS_E_ARG;
-    if (wire) sigs = sig_octets;
+    const bool wire = in.signature_octets != nullptr, raw = in.msg_byte_off != nullptr;
+    if (!out || (n && ((!in.signatures && !wire) || !in.msg_off || !in.didx_off || !in.rnd_off || !in.random_scalars))) return BBS_E_ARG;
+    const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
     const size_t rec = wire ? (size_t)FPB + 32 : (size_t)2 * FPB + 32;
     auto job = std::unique_ptr<PgJob<C>>(new PgJob<C>(ctx));
     job->n = n;
-    RaggedIn ms{msg_off, msgs, 32}, di{didx_off, reinterpret_cast<const uint8_t*>(didx), 8}, rs{rnd_off, rnd, 32},
-             hb{hdr_off, headers, 1}, pb{ph_off, ph, 1};
+    RaggedIn ms{in.msg_off, in.messages, 32}, di{in.didx_off, reinterpret_cast<const uint8_t*>(in.disclosed_idx), 8}, rs{in.rnd_off, in.random_scalars, 32},
+             hb{in.hdr_off, in.headers, 1}, pb{in.ph_off, in.ph, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !di.measure(n) || !rs.measure(n) || !hb.measure(n) || !pb.measure(n)) return BBS_E_ARG;
     const size_t nm = raw ? (size_t)ms.total : 0;
     // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? msg_byte_off + msg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
+    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
     if (hb.total > 0xF0000000ull || pb.total > 0xF0000000ull) return BBS_E_ARG;
     // Host side, one comparison per item (no field data is touched): the contract of this ABI on the number of random
@@ -118,10 +113,10 @@ int pg_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, c
     // reference's checks, range checks, deduplication, unpacking, SoA transposition, and the layout of the results
     // (stage PgEmit) -- happens on the device.
     for (size_t i = 0; i < n; i++) {
-        const size_t l = (size_t)(msg_off[i + 1] - msg_off[i]);
-        const size_t r = (size_t)(didx_off[i + 1] - didx_off[i]);
-        const size_t nr = (size_t)(rnd_off[i + 1] - rnd_off[i]);
-        const uint64_t* idx = didx + didx_off[i];
+        const size_t l = (size_t)(in.msg_off[i + 1] - in.msg_off[i]);
+        const size_t r = (size_t)(in.didx_off[i + 1] - in.didx_off[i]);
+        const size_t nr = (size_t)(in.rnd_off[i + 1] - in.rnd_off[i]);
+        const uint64_t* idx = in.disclosed_idx + in.didx_off[i];
         if (r > l) continue;                                          // -> InvalidDisclosedIndicesLength on the device
         bool bad = false;
         for (size_t k = 0; k < r; k++) if (idx[k] >= l) bad = true;

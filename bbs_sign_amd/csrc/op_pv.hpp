@@ -1,7 +1,7 @@
 // Host orchestration of one batched operation (template over the curve); instantiated by the
 // per-curve translation units tu_*.hip so the library builds in parallel.
 #pragma once
-#include "runtime.hpp"
+#include "ops_decl.hpp"
 
 // ---- proof_verify ----------------------------------------------------------------------------
 // where a job's doubling chains run (see pv_upload): 3 / 2 / 1; BBS_PV_MSM_LAYOUT overrides (A/B), read once.
@@ -28,35 +28,26 @@ struct PvJob : JobBase<C> {
     KeyedJob<C> kj{};                 // keyed form only
 };
 
-// octets / oct_off != nullptr: the wire form (bbs_proof_verify_octets_*): proofs_fixed / commitments / commit_off are
-// ignored, the proofs come as octet strings and are decoded on the device (codec_dev.hpp PvOctDecode / PvOctIngest)
+// the form is deduced from the fields of PvIn that are set (ops_decl.hpp)
 // KEYED (bbs_*_keyed_*, instantiated in tu_pvk_*.hip): item i is verified under key key_index[i] of the context's key set
 // (keyed.hpp): its own domain and W line table; the fused pairing kernel in both job forms, no batch verification
-template <class C, bool KEYED = false>
-int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t* commitments,
-                     const uint64_t* commit_off, const uint8_t* dmsgs, const uint64_t* dmsg_off,
-                     const uint64_t* didx, const uint64_t* didx_off, const uint8_t* headers,
-                     const uint64_t* hdr_off, const uint8_t* ph, const uint64_t* ph_off, bbs_job** out,
-                     const uint8_t* octets, const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
-                     const uint32_t* key_index = nullptr) {
-    // msg_byte_off != nullptr (wire form only): the disclosed messages arrive as RAW BYTES -- message t of the batch is
-    // msg_bytes[msg_byte_off[t] .. msg_byte_off[t + 1]), dmsg_off counts messages per item as before, dmsgs is ignored --
-    // and are mapped to scalars on the device (msg_to_scalars, interface_utilities.rs:76-88)
-    const bool wire = oct_off != nullptr;
-    const bool raw = msg_byte_off != nullptr;
+template <class C, bool KEYED>
+int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
+    const bool wire = in.oct_off != nullptr;
+    const bool raw = in.msg_byte_off != nullptr;
     if (raw && !wire) return BBS_E_ARG;
     constexpr int N = C::FpP::N;        // internal limbs
     constexpr int NC = C::FpP::NC;      // canonical 32-bit words
     constexpr int FPB = 4 * NC;
     if constexpr (KEYED) {
         if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
-        if (n && !key_index) return BBS_E_ARG;
+        if (n && !in.key_index) return BBS_E_ARG;
     } else {
         if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
     }
-    if (!out || (n && (!dmsg_off || !didx_off))) return BBS_E_ARG;
-    if (n && !wire && (!proofs_fixed || !commit_off)) return BBS_E_ARG;
-    if (n && wire && !octets) return BBS_E_ARG;
+    if (!out || (n && (!in.dmsg_off || !in.didx_off))) return BBS_E_ARG;
+    if (n && !wire && (!in.proofs_fixed || !in.commit_off)) return BBS_E_ARG;
+    if (n && wire && !in.proof_octets) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
     const size_t rec = 6 * FPB + 128;
@@ -64,21 +55,21 @@ int pv_upload(Ctx<C>* ctx, size_t n, const uint8_t* proofs_fixed, const uint8_t*
     job->n = n;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, key_index, job->kj, kwords);
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
     // ---- the batch as one staging image in page-locked memory, one asynchronous copy; everything else (the
     // reference's checks, range checks, unpacking, the SoA transposition) happens on the device: stage PvIngest
     // first ragged section: the commitments (core form) or the proof octet strings (wire form)
-    RaggedIn cm{wire ? oct_off : commit_off, wire ? octets : commitments, wire ? (size_t)1 : (size_t)32}, dm{dmsg_off, dmsgs, 32},
-             di{didx_off, reinterpret_cast<const uint8_t*>(didx), 8}, hb{hdr_off, headers, 1}, pb{ph_off, ph, 1};
+    RaggedIn cm{wire ? in.oct_off : in.commit_off, wire ? in.proof_octets : in.commitments, wire ? (size_t)1 : (size_t)32}, dm{in.dmsg_off, in.disclosed_msgs, 32},
+             di{in.didx_off, reinterpret_cast<const uint8_t*>(in.disclosed_idx), 8}, hb{in.hdr_off, in.headers, 1}, pb{in.ph_off, in.ph, 1};
     dm.offsets_only = raw;
     if (!cm.measure(n) || !dm.measure(n) || !di.measure(n) || !hb.measure(n) || !pb.measure(n)) return BBS_E_ARG;
     if (hb.total > 0xF0000000ull || pb.total > 0xF0000000ull) return BBS_E_ARG;
     const size_t nm = raw ? (size_t)dm.total : 0;                   // disclosed messages of the whole batch
     // (message t of the batch is entry dmsg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? msg_byte_off + dmsg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
+    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.dmsg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
     // (the message section is ragged over MESSAGES, not items: stage_image places and fills it with nm as its count)
-    if (int rc0 = stage_image(job.get(), n, wire ? nullptr : proofs_fixed, wire ? 0 : rec, {&cm, &dm, &di, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
+    if (int rc0 = stage_image(job.get(), n, wire ? nullptr : in.proofs_fixed, wire ? 0 : rec, {&cm, &dm, &di, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
 
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
     if constexpr (KEYED) keyed_bind<C>(job->kj, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));

@@ -1,7 +1,7 @@
 // Host orchestration of one batched operation (template over the curve); instantiated by the
 // per-curve translation units tu_*.hip so the library builds in parallel.
 #pragma once
-#include "runtime.hpp"
+#include "ops_decl.hpp"
 
 // ---- sign --------------------------------------------------------------------------------------
 template <class C>
@@ -38,25 +38,23 @@ struct SgJob : JobBase<C> {
 };
 
 template <class C>
-int sg_upload(Ctx<C>* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* headers,
-                     const uint64_t* hdr_off, bbs_job** out, const uint8_t* msg_bytes, const uint64_t* msg_byte_off) {
-    // msg_byte_off != nullptr: raw messages, hashed to scalars on the device (see vf_upload)
+int sg_upload(Ctx<C>* ctx, size_t n, const SgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     if (!ctx->gens_set || !ctx->sk_set) return BBS_E_STATE;
-    if (!out || (n && !msg_off)) return BBS_E_ARG;
+    if (!out || (n && !in.msg_off)) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
     auto job = std::unique_ptr<SgJob<C>>(new SgJob<C>(ctx));
     job->n = n;
     // staging image + device-side checks (stage VfIngest without a signature record: sign.rs:77-79's length check,
     // range checks of the messages, SoA transposition)
-    const bool raw = msg_byte_off != nullptr;
-    RaggedIn ms{msg_off, msgs, 32}, hb{hdr_off, headers, 1};
+    const bool raw = in.msg_byte_off != nullptr;
+    RaggedIn ms{in.msg_off, in.messages, 32}, hb{in.hdr_off, in.headers, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !hb.measure(n) || hb.total > 0xF0000000ull) return BBS_E_ARG;
     const size_t nm = raw ? (size_t)ms.total : 0;
     // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? msg_byte_off + msg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
+    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
     if (int rc0 = stage_image(job.get(), n, nullptr, 0, {&ms, &hb}, raw ? &mb : nullptr, nm)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();

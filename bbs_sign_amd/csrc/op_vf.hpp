@@ -1,7 +1,7 @@
 // Host orchestration of one batched operation (template over the curve); instantiated by the
 // per-curve translation units tu_*.hip so the library builds in parallel.
 #pragma once
-#include "runtime.hpp"
+#include "ops_decl.hpp"
 
 // ---- verify ------------------------------------------------------------------------------------
 template <class C>
@@ -18,43 +18,37 @@ struct VfJob : JobBase<C> {
 
 // KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
 // (keyed.hpp); the fused pairing kernel in both job forms, no batch verification
-template <class C, bool KEYED = false>
-int vf_upload(Ctx<C>* ctx, size_t n, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
-                     const uint8_t* headers, const uint64_t* hdr_off, bbs_job** out, const uint8_t* octets,
-                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
-                     const uint32_t* key_index = nullptr) {
-    // msg_byte_off != nullptr: the messages arrive as RAW BYTES (message t of the batch = msg_bytes[msg_byte_off[t] ..
-    // msg_byte_off[t + 1]), msg_off counts messages per item, msgs is ignored) and are hashed to scalars on the device
-    // octets != nullptr: the wire form -- n strings compress(A) || e instead of the records `sigs`
+template <class C, bool KEYED>
+int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
     if constexpr (KEYED) {
         if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
-        if (n && !key_index) return BBS_E_ARG;
+        if (n && !in.key_index) return BBS_E_ARG;
     } else {
         if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
     }
-    if (!out || (n && ((!sigs && !octets) || !msg_off))) return BBS_E_ARG;
+    if (!out || (n && ((!in.signatures && !in.signature_octets) || !in.msg_off))) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
-    const bool wire = octets != nullptr;
+    const bool wire = in.signature_octets != nullptr;
     const size_t rec = wire ? (size_t)FPB + 32 : (size_t)2 * FPB + 32;
-    if (wire) sigs = octets;
+    const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
     auto job = std::unique_ptr<VfJob<C>>(new VfJob<C>(ctx));
     job->n = n;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, key_index, job->kj, kwords);
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
     // the batch as one staging image, one asynchronous copy; checks, range checks and the SoA transposition on the
     // device (stage VfIngest), as for proof_verify
-    const bool raw = msg_byte_off != nullptr;
-    RaggedIn ms{msg_off, msgs, 32}, hb{hdr_off, headers, 1};
+    const bool raw = in.msg_byte_off != nullptr;
+    RaggedIn ms{in.msg_off, in.messages, 32}, hb{in.hdr_off, in.headers, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !hb.measure(n) || hb.total > 0xF0000000ull) return BBS_E_ARG;
     const size_t nm = raw ? (size_t)ms.total : 0;
     // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? msg_byte_off + msg_off[0] : zero_off1()) : nullptr, msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
+    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
     if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
     if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &hb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();

@@ -214,11 +214,25 @@ class Engine:
             ki = np.zeros(1, dtype=np.uint32)
         return ki, ki.ctypes.data_as(_lib.c_u32p)
 
-    def _keyed_submit(self, fn, n, key_index, args, fixup=None) -> "Job":
-        ki, kp = self._key_index(key_index, n)
+    # ---- the one call of every verify-family export: statuses out, nothing else.  `args` in C parameter order, `key_index`
+    # for the keyed exports, `fixup(st)` applied to the delivered statuses.  A successful call writes every entry: the
+    # -128 the buffer starts with never shows, and an entry nobody wrote cannot read as a verdict (fail closed).
+    def _status_call(self, fn, n, args, key_index, tail=()):
         st = np.full(max(n, 1), -128, dtype=np.int8)
+        key = () if key_index is None else self._key_index(key_index, n)
+        self._chk(getattr(self.lib, fn)(self.h, n, *key[1:], *args, st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+        return st
+
+    def _status_batch(self, fn, n, args, key_index=None, fixup=None) -> np.ndarray:
+        st = self._status_call(fn, n, args, key_index)
+        if fixup:
+            fixup(st)
+        return st[:n]
+
+    def _status_submit(self, fn, n, args, key_index=None, fixup=None) -> "Job":
+        """Everything enqueued, nothing waited for; ``job.wait()`` then ``job.result``."""
         j = ctypes.c_void_p()
-        self._chk(getattr(self.lib, fn)(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), fn)
+        st = self._status_call(fn, n, args, key_index, (ctypes.byref(j),))
         job = Job(self, j, n)
         job.result = st[:n]
         job._fixup = (lambda: fixup(st)) if fixup else None
@@ -227,27 +241,19 @@ class Engine:
     # keyed verification: item i under key key_index[i] of the key set (set_public_keys); -44 for an unknown key
     def core_proof_verify_keyed_submit(self, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> "Job":
         n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
-        return self._keyed_submit("bbs_core_proof_verify_keyed_submit", n, key_index, args)
+        return self._status_submit("bbs_core_proof_verify_keyed_submit", n, args, key_index)
 
     def core_proof_verify_keyed_batch(self, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> np.ndarray:
         n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
-        ki, kp = self._key_index(key_index, n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_core_proof_verify_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)),
-                  "bbs_core_proof_verify_keyed_batch")
-        return st[:n]
+        return self._status_batch("bbs_core_proof_verify_keyed_batch", n, args, key_index)
 
     def proof_verify_wire_keyed_submit(self, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> "Job":
         n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
-        return self._keyed_submit("bbs_proof_verify_wire_keyed_submit", n, key_index, args)
+        return self._status_submit("bbs_proof_verify_wire_keyed_submit", n, args, key_index)
 
     def proof_verify_wire_keyed_batch(self, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> np.ndarray:
         n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
-        ki, kp = self._key_index(key_index, n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_proof_verify_wire_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)),
-                  "bbs_proof_verify_wire_keyed_batch")
-        return st[:n]
+        return self._status_batch("bbs_proof_verify_wire_keyed_batch", n, args, key_index)
 
     def _vf_core_args(self, signatures, messages, headers):
         n = len(signatures)
@@ -258,36 +264,43 @@ class Engine:
 
     def core_verify_keyed_submit(self, key_index, signatures, messages, headers=None) -> "Job":
         n, keep, args = self._vf_core_args(signatures, messages, headers)
-        return self._keyed_submit("bbs_core_verify_keyed_submit", n, key_index, args)
+        return self._status_submit("bbs_core_verify_keyed_submit", n, args, key_index)
 
     def core_verify_keyed_batch(self, key_index, signatures, messages, headers=None) -> np.ndarray:
         n, keep, args = self._vf_core_args(signatures, messages, headers)
-        ki, kp = self._key_index(key_index, n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_core_verify_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_core_verify_keyed_batch")
-        return st[:n]
+        return self._status_batch("bbs_core_verify_keyed_batch", n, args, key_index)
+
+    @staticmethod
+    def _wrong_length_fixup(bad):
+        """``bad`` from _sig_octets: a string of the wrong length travelled as zeros and is -42 afterwards -- unless its key
+        is unknown (-44 first)."""
+        def fix(st):
+            for i in bad:
+                if st[i] != -44:
+                    st[i] = -42
+        return fix if bad else None
+
+    def _vf_oct_args(self, sig_octets, messages, headers):
+        n = len(sig_octets)
+        ob, bad = self._sig_octets(sig_octets)
+        ms, mo = self._scalars(messages)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        return n, (ob, ms, mo, hb, ho), (_u8(ob), _u8(ms), _u64(mo), _u8(hb), _u64(ho)), self._wrong_length_fixup(bad)
 
     def _vf_wire_args(self, sig_octets, messages_raw, headers):
         n = len(sig_octets)
         ob, bad = self._sig_octets(sig_octets)
         mb, mbo, mio = self._raw_msgs(messages_raw)
         hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        # a string of the wrong length travels as zeros and is -42 afterwards -- unless its key is unknown (-44 first)
-        fix = (lambda st: [st.__setitem__(i, -42) for i in bad if st[i] != -44]) if bad else None
-        return n, (ob, mb, mbo, mio, hb, ho), (_u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u8(hb), _u64(ho)), fix
+        return n, (ob, mb, mbo, mio, hb, ho), (_u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u8(hb), _u64(ho)), self._wrong_length_fixup(bad)
 
     def verify_wire_keyed_submit(self, key_index, sig_octets, messages_raw, headers=None) -> "Job":
         n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
-        return self._keyed_submit("bbs_verify_wire_keyed_submit", n, key_index, args, fix)
+        return self._status_submit("bbs_verify_wire_keyed_submit", n, args, key_index, fix)
 
     def verify_wire_keyed_batch(self, key_index, sig_octets, messages_raw, headers=None) -> np.ndarray:
         n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
-        ki, kp = self._key_index(key_index, n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_verify_wire_keyed_batch(self.h, n, kp, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_verify_wire_keyed_batch")
-        if fix:
-            fix(st)
-        return st[:n]
+        return self._status_batch("bbs_verify_wire_keyed_batch", n, args, key_index, fix)
 
     def set_secret_key(self, sk: int):
         buf = _bytes_arr(self._fr(sk))
@@ -358,10 +371,7 @@ class Engine:
     def core_proof_verify_batch(self, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> np.ndarray:
         """core_proof_verify (src/proof_verify.rs:64-116) over a batch; returns int8 statuses."""
         n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
-        st = np.zeros(max(n, 1), dtype=np.int8)
-        self._chk(self.lib.bbs_core_proof_verify_batch(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p)),
-                  "bbs_core_proof_verify_batch")
-        return st[:n]
+        return self._status_batch("bbs_core_proof_verify_batch", n, args)
 
     def core_proof_verify_upload(self, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> "Job":
         n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
@@ -376,24 +386,12 @@ class Engine:
 
     def submit_packed(self, n, args) -> "Job":
         """The same from already packed ctypes arguments (``_pv_inputs``): the per-batch host work of a serving loop."""
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_core_proof_verify_submit(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)),
-                  "bbs_core_proof_verify_submit")
-        job = Job(self, j, n)
-        job.result = st[:n]
-        return job
+        return self._status_submit("bbs_core_proof_verify_submit", n, args)
 
     def core_verify_batch(self, signatures, messages, headers=None) -> np.ndarray:
         """core_verify (src/verify.rs:53-93) over a batch."""
-        n = len(signatures)
-        sg = self._sigs(signatures)
-        ms, mo = self._scalars(messages)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        st = np.zeros(max(n, 1), dtype=np.int8)
-        self._chk(self.lib.bbs_core_verify_batch(self.h, n, _u8(sg), _u8(ms), _u64(mo), _u8(hb), _u64(ho),
-                                                 st.ctypes.data_as(_lib.c_i8p)), "bbs_core_verify_batch")
-        return st[:n]
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        return self._status_batch("bbs_core_verify_batch", n, args)
 
     def _oct_inputs(self, octets, disclosed_msgs, disclosed_idx, headers, phs):
         n = len(octets)
@@ -409,9 +407,7 @@ class Engine:
     def proof_verify_octets_batch(self, octets, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> np.ndarray:
         """bbs_proof_verify_octets_batch: proof octet strings in (decoded and subgroup-checked on the device), statuses out."""
         n, keep, args = self._oct_inputs(octets, disclosed_msgs, disclosed_idx, headers, phs)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_proof_verify_octets_batch(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_proof_verify_octets_batch")
-        return st[:n]
+        return self._status_batch("bbs_proof_verify_octets_batch", n, args)
 
     @staticmethod
     def _raw_msgs(items):
@@ -424,15 +420,8 @@ class Engine:
 
     def verify_wire_batch(self, sig_octets, messages_raw, headers=None) -> np.ndarray:
         """bbs_verify_wire_batch: the reference's public verify -- signature octets and raw messages in, statuses out."""
-        n = len(sig_octets)
-        ob, bad = self._sig_octets(sig_octets)
-        mb, mbo, mio = self._raw_msgs(messages_raw)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_verify_wire_batch(self.h, n, _u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u8(hb), _u64(ho),
-                                                 st.ctypes.data_as(_lib.c_i8p)), "bbs_verify_wire_batch")
-        st[bad] = -42
-        return st[:n]
+        n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
+        return self._status_batch("bbs_verify_wire_batch", n, args, fixup=fix)
 
     def sign_wire_batch(self, messages_raw, headers=None):
         """bbs_sign_wire_batch: the reference's public sign -- raw messages in, (signature octet strings, statuses) out."""
@@ -489,42 +478,19 @@ class Engine:
         """bbs_proof_verify_wire_batch: proof octets and raw disclosed messages in, statuses out (the reference's public
         proof_verify for this context's number of messages)."""
         n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_proof_verify_wire_batch(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p)), "bbs_proof_verify_wire_batch")
-        return st[:n]
+        return self._status_batch("bbs_proof_verify_wire_batch", n, args)
 
     def proof_verify_wire_submit(self, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> "Job":
         n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_proof_verify_wire_submit(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)),
-                  "bbs_proof_verify_wire_submit")
-        job = Job(self, j, n)
-        job.result = st[:n]
-        return job
+        return self._status_submit("bbs_proof_verify_wire_submit", n, args)
 
     def proof_verify_octets_submit_packed(self, n, args) -> "Job":
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_proof_verify_octets_submit(self.h, n, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)),
-                  "bbs_proof_verify_octets_submit")
-        job = Job(self, j, n)
-        job.result = st[:n]
-        return job
+        return self._status_submit("bbs_proof_verify_octets_submit", n, args)
 
     def core_verify_submit(self, signatures, messages, headers=None) -> "Job":
         """bbs_core_verify_submit: everything enqueued, nothing waited for; ``job.wait()`` then ``job.result``."""
-        n = len(signatures)
-        sg = self._sigs(signatures)
-        ms, mo = self._scalars(messages)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_core_verify_submit(self.h, n, _u8(sg), _u8(ms), _u64(mo), _u8(hb), _u64(ho),
-                                                  st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), "bbs_core_verify_submit")
-        job = Job(self, j, n)
-        job.result = st[:n]
-        return job
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        return self._status_submit("bbs_core_verify_submit", n, args)
 
     def _sig_octets(self, octets):
         """-> (flat buffer of n strings of fp_bytes + 32 octets, indexes of the items whose string has another length).
@@ -537,38 +503,17 @@ class Engine:
 
     def verify_octets_batch(self, sig_octets, messages, headers=None) -> np.ndarray:
         """bbs_verify_octets_batch: signature octet strings in (decoded and subgroup-checked on the device), statuses out."""
-        n = len(sig_octets)
-        ob, bad = self._sig_octets(sig_octets)
-        ms, mo = self._scalars(messages)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        self._chk(self.lib.bbs_verify_octets_batch(self.h, n, _u8(ob), _u8(ms), _u64(mo), _u8(hb), _u64(ho),
-                                                   st.ctypes.data_as(_lib.c_i8p)), "bbs_verify_octets_batch")
-        st[bad] = -42
-        return st[:n]
+        n, keep, args, fix = self._vf_oct_args(sig_octets, messages, headers)
+        return self._status_batch("bbs_verify_octets_batch", n, args, fixup=fix)
 
     def verify_octets_submit(self, sig_octets, messages, headers=None) -> "Job":
-        n = len(sig_octets)
-        ob, bad = self._sig_octets(sig_octets)
-        ms, mo = self._scalars(messages)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_verify_octets_submit(self.h, n, _u8(ob), _u8(ms), _u64(mo), _u8(hb), _u64(ho),
-                                                    st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), "bbs_verify_octets_submit")
-        job = Job(self, j, n)
-        job.result = st[:n]
-        job._fixup = (lambda: st.__setitem__(bad, -42)) if bad else None
-        return job
+        n, keep, args, fix = self._vf_oct_args(sig_octets, messages, headers)
+        return self._status_submit("bbs_verify_octets_submit", n, args, fixup=fix)
 
     def core_verify_upload(self, signatures, messages, headers=None) -> "Job":
-        n = len(signatures)
-        sg = self._sigs(signatures)
-        ms, mo = self._scalars(messages)
-        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
         j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_core_verify_upload(self.h, n, _u8(sg), _u8(ms), _u64(mo), _u8(hb), _u64(ho),
-                                                  ctypes.byref(j)), "bbs_core_verify_upload")
+        self._chk(self.lib.bbs_core_verify_upload(self.h, n, *args, ctypes.byref(j)), "bbs_core_verify_upload")
         return Job(self, j, n)
 
     def _dec_sigs(self, out: np.ndarray, st: np.ndarray, n: int):

@@ -232,6 +232,41 @@ inline Result<bool> proof_verify(const PublicKey& pk, const Proof& proof, const 
     return st >= 0 ? Result<bool>::ok(st == 1) : Result<bool>::err(st);
 }
 
+namespace detail {
+// a proof_verify batch as the C ABI takes it: flat buffers and offset vectors (n + 1 entries each) from the items
+struct PvBatch {
+    Bytes fixed, cm, dm, hb, pb;
+    std::vector<uint64_t> coff{0}, moff{0}, idx, ioff{0}, hoff{0}, poff{0};
+    PvBatch(bbs_ctx* ctx, Curve c, const std::vector<Proof>& proofs, const std::vector<Bytes>& headers, const std::vector<Bytes>& phs,
+            const std::vector<std::vector<Bytes>>& disclosed_msgs, const std::vector<std::vector<size_t>>& disclosed_indexes) {
+        std::vector<Bytes> all_msgs;
+        for (const auto& item : disclosed_msgs) all_msgs.insert(all_msgs.end(), item.begin(), item.end());
+        dm = msg_to_scalars(ctx, c, all_msgs);
+        for (size_t i = 0; i < proofs.size(); i++) {
+            fixed.insert(fixed.end(), proofs[i].fixed.begin(), proofs[i].fixed.end());
+            cm.insert(cm.end(), proofs[i].commitments.begin(), proofs[i].commitments.end());
+            coff.push_back(cm.size() / 32);
+            moff.push_back(moff.back() + disclosed_msgs[i].size());
+            idx.insert(idx.end(), disclosed_indexes[i].begin(), disclosed_indexes[i].end());
+            ioff.push_back(idx.size());
+            hb.insert(hb.end(), headers[i].begin(), headers[i].end());
+            hoff.push_back(hb.size());
+            pb.insert(pb.end(), phs[i].begin(), phs[i].end());
+            poff.push_back(pb.size());
+        }
+        idx.push_back(0);
+    }
+};
+inline std::vector<Result<bool>> bool_results(const std::vector<int8_t>& st, size_t n) {
+    std::vector<Result<bool>> out;
+    for (size_t i = 0; i < n; i++) {
+        raise_if_not_variant(st[i]);
+        out.push_back(st[i] >= 0 ? Result<bool>::ok(st[i] == 1) : Result<bool>::err(st[i]));
+    }
+    return out;
+}
+}  // namespace detail
+
 // proof_verify for n proofs of one issuer and one message count at once (what a verifier service calls: one engine
 // batch instead of n calls); element i of the result is what proof_verify(...) returns for proof i
 inline std::vector<Result<bool>> proof_verify_batch(const PublicKey& pk, const std::vector<Proof>& proofs,
@@ -241,34 +276,12 @@ inline std::vector<Result<bool>> proof_verify_batch(const PublicKey& pk, const s
     const Curve c = pk.curve;
     const size_t n = proofs.size();
     auto ctx = detail::context(c, message_count, false, pk.pk, pk.identity);
-    std::vector<Bytes> all_msgs;
-    for (const auto& item : disclosed_msgs) all_msgs.insert(all_msgs.end(), item.begin(), item.end());
-    const Bytes dm = detail::msg_to_scalars(ctx.get(), c, all_msgs);
-    Bytes fixed, cm, hb, pb;
-    std::vector<uint64_t> coff{0}, moff{0}, idx, ioff{0}, hoff{0}, poff{0};
-    for (size_t i = 0; i < n; i++) {
-        fixed.insert(fixed.end(), proofs[i].fixed.begin(), proofs[i].fixed.end());
-        cm.insert(cm.end(), proofs[i].commitments.begin(), proofs[i].commitments.end());
-        coff.push_back(cm.size() / 32);
-        moff.push_back(moff.back() + disclosed_msgs[i].size());
-        idx.insert(idx.end(), disclosed_indexes[i].begin(), disclosed_indexes[i].end());
-        ioff.push_back(idx.size());
-        hb.insert(hb.end(), headers[i].begin(), headers[i].end());
-        hoff.push_back(hb.size());
-        pb.insert(pb.end(), phs[i].begin(), phs[i].end());
-        poff.push_back(pb.size());
-    }
-    idx.push_back(0);
+    const detail::PvBatch b(ctx.get(), c, proofs, headers, phs, disclosed_msgs, disclosed_indexes);
     std::vector<int8_t> st(n ? n : 1, 0);
-    detail::check(bbs_core_proof_verify_batch(ctx.get(), n, detail::ptr(fixed), detail::ptr(cm), coff.data(), detail::ptr(dm), moff.data(),
-                                              idx.data(), ioff.data(), detail::ptr(hb), hoff.data(), detail::ptr(pb), poff.data(), st.data()),
+    detail::check(bbs_core_proof_verify_batch(ctx.get(), n, detail::ptr(b.fixed), detail::ptr(b.cm), b.coff.data(), detail::ptr(b.dm), b.moff.data(),
+                                              b.idx.data(), b.ioff.data(), detail::ptr(b.hb), b.hoff.data(), detail::ptr(b.pb), b.poff.data(), st.data()),
                   "bbs_core_proof_verify_batch");
-    std::vector<Result<bool>> out;
-    for (size_t i = 0; i < n; i++) {
-        detail::raise_if_not_variant(st[i]);
-        out.push_back(st[i] >= 0 ? Result<bool>::ok(st[i] == 1) : Result<bool>::err(st[i]));
-    }
-    return out;
+    return detail::bool_results(st, n);
 }
 
 // ---- many issuers: one PublicKey per item (the reference's per-call key, src/verify.rs:18-50, src/proof_verify.rs:19-61) ----
@@ -332,14 +345,6 @@ inline std::vector<uint32_t> key_indexes(KeyedCtx& kc, Curve c, const std::vecto
     }
     return ki;
 }
-inline std::vector<Result<bool>> bool_results(const std::vector<int8_t>& st, size_t n) {
-    std::vector<Result<bool>> out;
-    for (size_t i = 0; i < n; i++) {
-        raise_if_not_variant(st[i]);
-        out.push_back(st[i] >= 0 ? Result<bool>::ok(st[i] == 1) : Result<bool>::err(st[i]));
-    }
-    return out;
-}
 }  // namespace detail
 
 // proof_verify_batch with ONE PublicKey PER ITEM: element i is what proof_verify(pks[i], proofs[i], ...) returns.  One
@@ -357,28 +362,11 @@ inline std::vector<Result<bool>> proof_verify_batch(const std::vector<PublicKey>
     std::vector<const PublicKey*> pp;
     for (const auto& k : pks) pp.push_back(&k);
     const std::vector<uint32_t> ki = detail::key_indexes(*kc, c, pp);
-    std::vector<Bytes> all_msgs;
-    for (const auto& item : disclosed_msgs) all_msgs.insert(all_msgs.end(), item.begin(), item.end());
-    const Bytes dm = detail::msg_to_scalars(kc->ctx.get(), c, all_msgs);
-    Bytes fixed, cm, hb, pb;
-    std::vector<uint64_t> coff{0}, moff{0}, idx, ioff{0}, hoff{0}, poff{0};
-    for (size_t i = 0; i < n; i++) {
-        fixed.insert(fixed.end(), proofs[i].fixed.begin(), proofs[i].fixed.end());
-        cm.insert(cm.end(), proofs[i].commitments.begin(), proofs[i].commitments.end());
-        coff.push_back(cm.size() / 32);
-        moff.push_back(moff.back() + disclosed_msgs[i].size());
-        idx.insert(idx.end(), disclosed_indexes[i].begin(), disclosed_indexes[i].end());
-        ioff.push_back(idx.size());
-        hb.insert(hb.end(), headers[i].begin(), headers[i].end());
-        hoff.push_back(hb.size());
-        pb.insert(pb.end(), phs[i].begin(), phs[i].end());
-        poff.push_back(pb.size());
-    }
-    idx.push_back(0);
+    const detail::PvBatch b(kc->ctx.get(), c, proofs, headers, phs, disclosed_msgs, disclosed_indexes);
     std::vector<int8_t> st(n, 0);
-    detail::check(bbs_core_proof_verify_keyed_batch(kc->ctx.get(), n, ki.data(), detail::ptr(fixed), detail::ptr(cm), coff.data(), detail::ptr(dm),
-                                                    moff.data(), idx.data(), ioff.data(), detail::ptr(hb), hoff.data(), detail::ptr(pb),
-                                                    poff.data(), st.data()),
+    detail::check(bbs_core_proof_verify_keyed_batch(kc->ctx.get(), n, ki.data(), detail::ptr(b.fixed), detail::ptr(b.cm), b.coff.data(), detail::ptr(b.dm),
+                                                    b.moff.data(), b.idx.data(), b.ioff.data(), detail::ptr(b.hb), b.hoff.data(), detail::ptr(b.pb),
+                                                    b.poff.data(), st.data()),
                   "bbs_core_proof_verify_keyed_batch");
     return detail::bool_results(st, n);
 }

@@ -80,12 +80,63 @@ def test_misuse_is_refused(twin, curve):
     assert lib.bbs_job_fetch_signatures(job, _u8(sigs)) == E_ARG
     assert lib.bbs_job_fetch_proofs(job, _u8(pf), none8, none64) == E_ARG
     lib.bbs_job_free(job)
+    # The verify family: each single-key export and its keyed twin refuse a NULL context, status or job_out with
+    # BBS_E_ARG, and do so before they look at the context's state (this one has no key set: BBS_E_STATE for the keyed
+    # forms, which also comes before the NULL key_index is looked at).
+    nul_i8 = ctypes.cast(None, _lib.c_i8p)
+    ki = np.zeros(n, dtype=np.uint32)
+    kp, nokey = ki.ctypes.data_as(_lib.c_u32p), ctypes.cast(None, _lib.c_u32p)
+    octs = np.zeros(n * 400, dtype=np.uint8)
+    ooff = np.arange(0, (n + 1) * 400, 400, dtype=np.uint64)
+    family = {
+        "core_proof_verify": (_u8(pf), _u8(msgs), _u64(zero), _u8(msgs), _u64(zero), _u64(good), _u64(zero), none8, none64, none8, none64),
+        "proof_verify_wire": (_u8(octs), _u64(ooff), none8, none64, _u64(zero), _u64(good), _u64(zero), none8, none64, none8, none64),
+        "core_verify": (_u8(sigs), _u8(msgs), _u64(good), none8, none64),
+        "verify_wire": (_u8(sigs), none8, none64, _u64(zero), none8, none64),
+    }
+    # raw messages announced by the item offsets, but no byte offsets: refused before anything else is looked at
+    no_byte_off = {
+        "proof_verify_wire": (_u8(octs), _u64(ooff), _u8(msgs), none64, _u64(good), _u64(good), _u64(zero), none8, none64, none8, none64),
+        "verify_wire": (_u8(sigs), _u8(msgs), none64, _u64(good), none8, none64),
+    }
+    for name, args in family.items():
+        for keyed in (False, True):
+            submit = getattr(lib, "bbs_%s%s_submit" % (name, "_keyed" if keyed else ""))
+            batch = getattr(lib, "bbs_%s%s_batch" % (name, "_keyed" if keyed else ""))
+            key = (kp,) if keyed else ()
+            what = (name, keyed)
+            assert submit(None, n, *key, *args, i8, ctypes.byref(job)) == E_ARG, what
+            assert submit(h, n, *key, *args, nul_i8, ctypes.byref(job)) == E_ARG, what
+            assert submit(h, n, *key, *args, i8, None) == E_ARG, what
+            assert batch(None, n, *key, *args, i8) == E_ARG, what
+            assert batch(h, n, *key, *args, nul_i8) == E_ARG, what
+            if keyed:
+                assert submit(h, n, kp, *args, i8, ctypes.byref(job)) == E_STATE, what
+                assert submit(h, n, nokey, *args, i8, ctypes.byref(job)) == E_STATE, what
+                assert batch(h, n, kp, *args, i8) == E_STATE, what
+            if name in no_byte_off:
+                assert submit(h, n, *key, *no_byte_off[name], i8, ctypes.byref(job)) == E_ARG, what
+                assert batch(h, n, *key, *no_byte_off[name], i8) == E_ARG, what
+    # with a key set: a NULL key_index with n > 0 is BBS_E_ARG, with n = 0 it is not needed
+    eng.set_public_keys([bbs.sk_to_pk(suite, 7)])
+    for name, args in family.items():
+        submit = getattr(lib, "bbs_%s_keyed_submit" % name)
+        assert submit(h, n, nokey, *args, i8, ctypes.byref(job)) == E_ARG, name
+        assert submit(h, n, kp, *args, nul_i8, ctypes.byref(job)) == E_ARG, name
+        assert getattr(lib, "bbs_%s_keyed_batch" % name)(h, 0, nokey, *args, i8) == 0, name
     eng.close()
     # a context that is not set up: no generators / no key
     bare = ctypes.c_void_p()
     assert lib.bbs_ctx_create(0 if curve == "bls12_381" else 1, 0, ctypes.byref(bare)) == 0
     assert lib.bbs_core_verify_batch(bare, n, _u8(sigs), _u8(msgs), _u64(good), none8, none64, i8) == E_STATE
     assert lib.bbs_core_sign_batch(bare, n, _u8(msgs), _u64(good), none8, none64, _u8(sigs), i8) == E_STATE
+    for name, args in family.items():
+        for keyed in (False, True):
+            submit = getattr(lib, "bbs_%s%s_submit" % (name, "_keyed" if keyed else ""))
+            key = (kp,) if keyed else ()
+            assert submit(bare, n, *key, *args, i8, ctypes.byref(job)) == E_STATE, (name, keyed)
+            assert submit(bare, n, *key, *args, nul_i8, ctypes.byref(job)) == E_ARG, (name, keyed)
+            assert submit(bare, n, *key, *args, i8, None) == E_ARG, (name, keyed)
     lib.bbs_ctx_destroy(bare)
 
 

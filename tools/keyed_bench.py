@@ -83,20 +83,8 @@ def loop(submit, steps, warmup):
 
 def packed(eng, fn, n, args, keep, key_index=None):
     """A submit function over arguments packed ONCE (as bench.py's serving loop): only the C call is per step."""
-    import ctypes
-    from bbs_sign_amd import _lib
-    from bbs_sign_amd.engine import Job
-    if key_index is not None:
-        ki, kp = eng._key_index(key_index, n)
-        args = (kp,) + tuple(args)
-        keep = (keep, ki)
-
     def submit():
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        j = ctypes.c_void_p()
-        eng._chk(getattr(eng.lib, fn)(eng.h, n, *args, st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), fn)
-        job = Job(eng, j, n)
-        job.result = st[:n]
+        job = eng._status_submit(fn, n, args, key_index)
         job.keep = keep
         return job
     return submit
