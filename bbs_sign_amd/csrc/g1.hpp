@@ -12,16 +12,6 @@
 namespace bbs {
 
 #define FP typename C::FpP
-// point doubling / mixed addition with the multipliers INLINED: operands stay in VGPRs; measured
-// on MI355X the MSM stage drops 7.4 -> 5.8 ms (the non-inlined form, -DBBS_G1_CALL_MUL, pays for
-// argument traffic through scratch on every call)
-#ifndef BBS_G1_CALL_MUL
-#define G1MUL fe_mul_i
-#define G1SQR fe_sqr_i
-#else
-#define G1MUL fe_mul
-#define G1SQR fe_sqr
-#endif
 
 template <class C>
 struct G1Aff {        // (0,0) encodes the identity (not on either curve: b != 0)
@@ -62,24 +52,26 @@ BBS_HD bool g1a_on_curve(const G1Aff<C>& p) {
     return fe_eq<FP>(lhs, rhs);
 }
 
+// Point doubling / mixed addition call the INLINED multipliers (fe_mul_i / fe_sqr_i): operands stay in VGPRs; measured on
+// MI355X the MSM stage drops 7.4 -> 5.8 ms (the called form pays for argument traffic through scratch on every call).
 // dbl-2009-l (a = 0): 2M + 5S; the linear steps are single reduction chains (fe_lin)
 template <class C>
 BBS_HD G1Jac<C> g1j_dbl(const G1Jac<C>& p) {
     // identity (Z=0) maps to Z3 = 2*Y*0 = 0 : stays the identity.  Y = 0 cannot happen on
     // these curves (no point of order 2: x^3 = -b has no root in Fp for b = 4 / b = 3).
-    Fp<C> A = G1SQR<FP>(p.x);
-    Fp<C> B = G1SQR<FP>(p.y);
-    Fp<C> Cc = G1SQR<FP>(B);
-    Fp<C> t2 = G1SQR<FP>(fe_add_nr<FP>(p.x, B));              // (X + B)^2, lazy sum feeds the squarer
+    Fp<C> A = fe_sqr_i<FP>(p.x);
+    Fp<C> B = fe_sqr_i<FP>(p.y);
+    Fp<C> Cc = fe_sqr_i<FP>(B);
+    Fp<C> t2 = fe_sqr_i<FP>(fe_add_nr<FP>(p.x, B));           // (X + B)^2, lazy sum feeds the squarer
     Fp<C> D = fe_lin<FP, 2, -2, -2>(t2, A, Cc);               // 2((X+B)^2 - A - C)
     Fp<C> E = fe_scale<FP, 3>(A);
-    Fp<C> F = G1SQR<FP>(E);
+    Fp<C> F = fe_sqr_i<FP>(E);
     G1Jac<C> r;
     r.x = fe_lin<FP, 1, -2>(F, D);
     Fp<C> c4 = fe_scale<FP, 4>(Cc);
-    Fp<C> m = G1MUL<FP>(E, fe_sub<FP>(D, r.x));
+    Fp<C> m = fe_mul_i<FP>(E, fe_sub<FP>(D, r.x));
     r.y = fe_lin<FP, 1, -2>(m, c4);                            // E (D - X3) - 8 C
-    r.z = fe_scale<FP, 2>(G1MUL<FP>(p.y, p.z));
+    r.z = fe_scale<FP, 2>(fe_mul_i<FP>(p.y, p.z));
     return r;
 }
 
@@ -88,24 +80,24 @@ template <class C>
 BBS_HD G1Jac<C> g1j_add_aff(const G1Jac<C>& p, const G1Aff<C>& q) {
     if (g1a_is_inf<C>(q)) return p;
     if (g1j_is_inf<C>(p)) return {q.x, q.y, fe_one<FP>()};
-    Fp<C> Z1Z1 = G1SQR<FP>(p.z);
-    Fp<C> U2 = G1MUL<FP>(q.x, Z1Z1);
-    Fp<C> S2 = G1MUL<FP>(G1MUL<FP>(q.y, p.z), Z1Z1);
+    Fp<C> Z1Z1 = fe_sqr_i<FP>(p.z);
+    Fp<C> U2 = fe_mul_i<FP>(q.x, Z1Z1);
+    Fp<C> S2 = fe_mul_i<FP>(fe_mul_i<FP>(q.y, p.z), Z1Z1);
     Fp<C> H = fe_sub<FP>(U2, p.x);
     Fp<C> rr = fe_lin<FP, 2, -2>(S2, p.y);                     // 2 (S2 - Y1); zero iff S2 == Y1 (p odd)
     if (fe_is_zero<FP>(H)) {
         if (fe_is_zero<FP>(rr)) return g1j_dbl<C>(p);
         return g1j_inf<C>();
     }
-    Fp<C> HH = G1SQR<FP>(H);
+    Fp<C> HH = fe_sqr_i<FP>(H);
     Fp<C> I = fe_scale<FP, 4>(HH);
-    Fp<C> J = G1MUL<FP>(H, I);
-    Fp<C> V = G1MUL<FP>(p.x, I);
+    Fp<C> J = fe_mul_i<FP>(H, I);
+    Fp<C> V = fe_mul_i<FP>(p.x, I);
     G1Jac<C> r;
-    r.x = fe_lin<FP, 1, -1, -2>(G1SQR<FP>(rr), J, V);
-    Fp<C> m = G1MUL<FP>(rr, fe_sub<FP>(V, r.x));
-    r.y = fe_lin<FP, 1, -2>(m, G1MUL<FP>(p.y, J));
-    r.z = fe_lin<FP, 1, -1, -1>(G1SQR<FP>(fe_add_nr<FP>(p.z, H)), Z1Z1, HH);
+    r.x = fe_lin<FP, 1, -1, -2>(fe_sqr_i<FP>(rr), J, V);
+    Fp<C> m = fe_mul_i<FP>(rr, fe_sub<FP>(V, r.x));
+    r.y = fe_lin<FP, 1, -2>(m, fe_mul_i<FP>(p.y, J));
+    r.z = fe_lin<FP, 1, -1, -1>(fe_sqr_i<FP>(fe_add_nr<FP>(p.z, H)), Z1Z1, HH);
     return r;
 }
 
@@ -211,20 +203,20 @@ BBS_HD G1Jac<C> g1_mul_aff_naf(const G1Aff<C>& p, const uint32_t* k) {
 // mixed addition that also returns Z3 / Z1 (= 2 H); false in an exceptional case
 template <class C>
 BBS_HD bool g1j_add_aff_zr(const G1Jac<C>& p, const G1Aff<C>& q, G1Jac<C>& r, Fp<C>& zr) {
-    Fp<C> Z1Z1 = G1SQR<FP>(p.z);
-    Fp<C> U2 = G1MUL<FP>(q.x, Z1Z1);
-    Fp<C> S2 = G1MUL<FP>(G1MUL<FP>(q.y, p.z), Z1Z1);
+    Fp<C> Z1Z1 = fe_sqr_i<FP>(p.z);
+    Fp<C> U2 = fe_mul_i<FP>(q.x, Z1Z1);
+    Fp<C> S2 = fe_mul_i<FP>(fe_mul_i<FP>(q.y, p.z), Z1Z1);
     Fp<C> H = fe_sub<FP>(U2, p.x);
     if (fe_is_zero<FP>(H)) return false;
     Fp<C> rr = fe_lin<FP, 2, -2>(S2, p.y);
-    Fp<C> HH = G1SQR<FP>(H);
+    Fp<C> HH = fe_sqr_i<FP>(H);
     Fp<C> I = fe_scale<FP, 4>(HH);
-    Fp<C> J = G1MUL<FP>(H, I);
-    Fp<C> V = G1MUL<FP>(p.x, I);
-    r.x = fe_lin<FP, 1, -1, -2>(G1SQR<FP>(rr), J, V);
-    Fp<C> m = G1MUL<FP>(rr, fe_sub<FP>(V, r.x));
-    r.y = fe_lin<FP, 1, -2>(m, G1MUL<FP>(p.y, J));
-    r.z = fe_lin<FP, 1, -1, -1>(G1SQR<FP>(fe_add_nr<FP>(p.z, H)), Z1Z1, HH);
+    Fp<C> J = fe_mul_i<FP>(H, I);
+    Fp<C> V = fe_mul_i<FP>(p.x, I);
+    r.x = fe_lin<FP, 1, -1, -2>(fe_sqr_i<FP>(rr), J, V);
+    Fp<C> m = fe_mul_i<FP>(rr, fe_sub<FP>(V, r.x));
+    r.y = fe_lin<FP, 1, -2>(m, fe_mul_i<FP>(p.y, J));
+    r.z = fe_lin<FP, 1, -1, -1>(fe_sqr_i<FP>(fe_add_nr<FP>(p.z, H)), Z1Z1, HH);
     zr = fe_dbl<FP>(H);
     return true;
 }
@@ -328,10 +320,6 @@ BBS_HD G1Aff<C> g1_tab_digit(const T& tab, uint32_t U, bool flip = false) {     
 // callee's frame and its saved registers to the kernel's scratch; everyone else calls the non-inlined wrapper below)
 template <class C, class W>
 BBS_HD void g1_mul_aff_tab_inl(const G1Aff<C>& p, const uint32_t* k, const W where, G1Jac<C>& out) {
-#ifdef BBS_G1_MUL_NAF
-    out = g1_mul_aff_naf<C>(p, k);
-    return;
-#endif
     typename W::Tab tab;
     where.init(tab);
     Fp<C> zc;
@@ -591,7 +579,7 @@ BBS_HD void g1_mul_aff_glv_tab_inl(const G1Aff<C>& p, const uint32_t* k, const W
     for (int s = 0; s < STEPS; s++) {
         G1Aff<C> q = qn;
         if (s + 1 < STEPS) qn = fetch(s + 1);
-        if (s & 1) q.x = G1MUL<FP>(q.x, beta);          // phi, applied after the next entry has been requested
+        if (s & 1) q.x = fe_mul_i<FP>(q.x, beta);       // phi, applied after the next entry has been requested
         const int rd = s >> 1;
         if ((s & 1) == 0 && rd >= 1 && rd <= 31) {
 #pragma unroll 1
@@ -624,9 +612,6 @@ BBS_HD G1Jac<C> g1_mul_aff_glv_tab(const G1Aff<C>& p, const uint32_t* k, const W
 // is a budget (DESIGN.md 5 rule 6).
 template <class C, bool GLV = false>
 BBS_HD bool g1_mul3_tabs_fast(const uint32_t* k0, const uint32_t* k1, const uint32_t* k2, uint32_t* tabs, size_t stride, G1Jac<C>& out) {
-#ifdef BBS_G1_MUL_NAF
-    return false;
-#endif
     constexpr int N = C::FpP::N;
     constexpr size_t TW = (size_t)G1_TAB * 2 * N;
     Fp<C> zc0 = fe_one<FP>(), zc1 = zc0, zc2 = zc0;
@@ -685,7 +670,7 @@ BBS_HD bool g1_mul3_tabs_fast(const uint32_t* k0, const uint32_t* k1, const uint
         for (int s = 0; s < STEPS; s++) {
             G1Aff<C> q = qn;
             if (s + 1 < STEPS) qn = fetch(s + 1);
-            if (s & 1) q.x = G1MUL<FP>(q.x, beta);      // phi (odd terms), applied after the next entry has been requested
+            if (s & 1) q.x = fe_mul_i<FP>(q.x, beta);   // phi (odd terms), applied after the next entry has been requested
             const int rd = s / 6;
             if (s == 6 * rd && rd >= 1 && rd <= 31) {
 #pragma unroll 1
@@ -749,9 +734,6 @@ BBS_HD G1Jac<C> g1_mul3_aff(const G1Aff<C>& p0, const uint32_t* k0, const G1Aff<
 // and free of indexed locals, as g1_mul3_tabs_fast (round 5: its frame was 1216 bytes below the kernel's).
 template <class C, bool GLV = false>
 BBS_HD bool g1_mul2_tabs_fast(const uint32_t* k0, const uint32_t* k1, uint32_t* tabs, size_t stride, G1Jac<C>& out) {
-#ifdef BBS_G1_MUL_NAF
-    return false;
-#endif
     constexpr int N = C::FpP::N;
     constexpr size_t TW = (size_t)G1_TAB * 2 * N;
     Fp<C> zc0 = fe_one<FP>(), zc1 = zc0;
@@ -808,7 +790,7 @@ BBS_HD bool g1_mul2_tabs_fast(const uint32_t* k0, const uint32_t* k1, uint32_t* 
         for (int s = 0; s < STEPS; s++) {
             G1Aff<C> q = qn;
             if (s + 1 < STEPS) qn = fetch(s + 1);
-            if (s & 1) q.x = G1MUL<FP>(q.x, beta);      // phi (odd terms), applied after the next entry has been requested
+            if (s & 1) q.x = fe_mul_i<FP>(q.x, beta);   // phi (odd terms), applied after the next entry has been requested
             const int rd = s / 4;
             if (s == 4 * rd && rd >= 1 && rd <= 31) {
 #pragma unroll 1
@@ -962,6 +944,4 @@ BBS_HD G1Jac<C> g1_mul_aff_sel_hbm(const G1Aff<C>& p, const uint32_t* k, bool gl
 }
 
 #undef FP
-#undef G1MUL
-#undef G1SQR
 }  // namespace bbs

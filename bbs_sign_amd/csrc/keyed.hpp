@@ -147,7 +147,7 @@ __device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size
 }
 template <class C>
 struct PairDistKeyed {
-    static constexpr int WAVES_PER_EU = BBS_PAIR_WAVES;
+    static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairKeyedArgs<C>& ka, size_t t) {
         if ((t >> 6) * GRP_PER_WAVE < ka.n_uni) pair_dist_keyed<C, true>(ka, t);     // (uniform over the wavefront)
         else pair_dist_keyed<C, false>(ka, t);

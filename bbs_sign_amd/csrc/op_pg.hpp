@@ -177,11 +177,10 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     a.nvar = job->latency_form ? PG_NVAR : PG_NVAR_JOINT;
     a.vtab = job->template scratch<uint32_t>((size_t)PG_NVAR * G1_TAB * 2 * N * std::max<size_t>(n, 1), rc);
     a.ctab = nullptr; a.comb_ok = nullptr;
-    static const bool use_comb = [] { const char* v = getenv("BBS_PG_COMB"); return !v || atoi(v) != 0; }();     // A/B: BBS_PG_COMB=0
     // (where the GLV split is on -- BN254 always, BLS12-381 for vouched or decoded points -- the comb runs over the 64-bit halves
     // of the split scalars: 64 doublings of preparation per point instead of 192; the plain comb there measured -12 % on BN254
-    // against the 126-doubling joint chains)
-    if (a.nvar == PG_NVAR_JOINT && use_comb) {
+    // against the 126-doubling joint chains; comb against joint chains without it: profiles/r04_q_proof_gen_comb.log)
+    if (a.nvar == PG_NVAR_JOINT) {
         a.ctab = job->template scratch<uint32_t>((size_t)2 * comb_table_words(N) * std::max<size_t>(n, 1), rc);
         a.comb_ok = job->template scratch<int8_t>(2 * std::max<size_t>(n, 1), rc);
     }

@@ -4,15 +4,13 @@
 #include "ops_decl.hpp"
 
 // ---- proof_verify ----------------------------------------------------------------------------
-// where a job's doubling chains run (see pv_upload): 3 / 2 / 1; BBS_PV_MSM_LAYOUT overrides (A/B), read once.
+// where a job's doubling chains run (see pv_upload): 3 / 2 / 1.
 // one_queue: the job is meant to own ONE hardware queue (batch verification's throughput form keeps many jobs alive).
 // latency_form: T1's three terms are single multiplications (PvVarMul parts 0 .. 2): all four multiplications go to the side
 // stream as one launch, so that the main stream's scalars -> fixed-base chunks run BESIDE them -- on the main stream in front
 // of the scalars they made the MSM chain (2.85 + 0.13 + 0.9 + 0.6 ms) longer than the pairing (4.2 ms) it runs beside:
 // one batch at a time 4.7 against 4.35 ms (profiles/r05_a_ab_split_msm_layouts.log, new3 vs new2).
 inline int pv_msm_layout(bool one_queue, bool latency_form) {
-    static const int forced = []() { const char* v = getenv("BBS_PV_MSM_LAYOUT"); const int k = v ? atoi(v) : 0; return (k >= 1 && k <= 3) ? k : 0; }();
-    if (forced) return forced;
     return one_queue ? 1 : (latency_form ? 2 : 3);
 }
 template <class C>
@@ -189,9 +187,8 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         // follows the MSM chain (verify: 7.4 -> 6.9 ms), but beside the 768 wavefronts of this operation's latency-form MSM
         // chain it oversubscribes the 1024 SIMDs and the queued wavefronts cost more than the split saves (measured
         // 5.1 ms split vs 4.4 ms fused, profiles/r03_j_latency_form_split.log)
-        static const bool lat_split = []() { const char* v = getenv("BBS_PV_LAT_SPLIT"); return v && atoi(v) != 0; }();      // A/B knob
         if constexpr (KEYED) add_keyed_pairing_stages<C>(j, &j->kj, &j->pa, 1);
-        else add_pairing_stages<C>(j, &j->pa, 1, "pair_miller", "pair_final_exp", "pairing_6lane", false, 0, lat_split);
+        else add_pairing_stages<C>(j, &j->pa, 1, "pair_miller", "pair_final_exp", "pairing_6lane", PairSplit::Never);
         msm_chain(pv_msm_layout(false, job->latency_form));
         j->stages.push_back({"pv_challenge", [j]() { return rt::launch<PvChallenge<C>>(j->stream(), j->a, j->n); }, 0, join_chains});
         j->stages.push_back({"pv_finish", [j]() { return rt::launch<PvFinish>(j->stream(), j->fin, j->n); }, 0, 1});

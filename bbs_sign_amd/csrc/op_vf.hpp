@@ -107,8 +107,7 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     // 1.75 / 1.79 / 1.81 M verify/s against 1.64 / 1.71 / 1.81 with the job kept to one stream
     // (profiles/r05_e_verify_var_mul_side_stream.log).  Except batch verification's throughput form, whose jobs are kept alive
     // by the dozen and must own ONE hardware queue each (32 in flight: 4.2 M/s on one stream, 3.1 M/s on two).
-    static const int side_forced = []() { const char* v = getenv("BBS_VF_SIDE"); return v ? atoi(v) : -1; }();      // A/B: 0 never, 1 always
-    const int side = side_forced >= 0 ? (side_forced ? 1 : 0) : ((!KEYED && ctx->batch_verify && !job->latency_form) ? 0 : 1);
+    const int side = (!KEYED && ctx->batch_verify && !job->latency_form) ? 0 : 1;
     j->stages.push_back({"vf_var_mul", [j, side]() { return rt::launch<VfVarMul<C>>(side ? j->stream_aux(1) : j->stream(), j->a, j->n); }, side, 0});
     if constexpr (KEYED)
         j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});

@@ -1149,36 +1149,32 @@ inline int launch_pip_windows(Stream& s, const PipCoopArgs<C>& a) {
 }  // namespace rt
 #endif
 
-// one pairing product check as stages on the job's main (aux = 0) or second stream.  split: the two Miller loops of an
-// item on separate wavefronts and the final exponentiation as its own stage (the job's latency form; always for the
-// sixteen combined checks of batch verification, which are the narrow tail of their job)
+// one pairing product check as stages on the job's main (aux = 0) or second stream.  Split: the two Miller loops of an
+// item on separate wavefronts and the final exponentiation as its own stage; fused: one kernel.  (The host twin runs its
+// one-lane pair of stages whatever is asked: it uses neither nm_dist nor split, hence [[maybe_unused]].)
+enum class PairSplit {
+    ByJobForm,   // split in the job's latency form, fused in the throughput form
+    Always,      // the sixteen combined checks of batch verification, which are the narrow tail of their job
+    Never,       // proof_verify (see op_pv.hpp)
+};
 template <class C, class J>
-void add_pairing_stages(J* j, PairArgs<C>* pargs, int aux, const char* nm_miller, const char* nm_final, const char* nm_dist, bool force_split = false,
-                        int join_first = 0,         // join_first: the (main-stream) first stage waits for the second stream
-                        bool allow_split = true) {  // false: one fused kernel also in the latency form (see op_pv.hpp)
-    (void)nm_miller; (void)nm_final; (void)nm_dist; (void)force_split; (void)allow_split;
+void add_pairing_stages(J* j, PairArgs<C>* pargs, int aux, const char* nm_miller, const char* nm_final, [[maybe_unused]] const char* nm_dist,
+                        [[maybe_unused]] PairSplit split = PairSplit::ByJobForm,
+                        int join_first = 0) {       // join_first: the (main-stream) first stage waits for the second stream
     const size_t first = j->stages.size();
     struct JoinFirst { J* j; size_t first; int join; ~JoinFirst() { if (join && j->stages.size() > first) j->stages[first].join = 1; } } jf{j, first, join_first};
 #ifdef BBS_HOST_TWIN
     j->stages.push_back({nm_miller, [j, pargs, aux]() { return rt::launch<PairMiller<C>>(aux ? j->stream_aux() : j->stream(), *pargs, pargs->n * 2); }, aux, 0});
     j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pargs, pargs->n); }, aux, 0});
 #else
-    if ((j->latency_form && allow_split) || force_split) {
+    pargs->single = 0;      // always (stages.hpp PairArgs)
+    if (split == PairSplit::Always || (split == PairSplit::ByJobForm && j->latency_form)) {
         // the two Miller loops of every item on separate wavefronts, then product + final exponentiation (stages.hpp)
-        pargs->single = 0;
         j->stages.push_back({nm_miller, [j, pargs, aux]() { return rt::launch<PairMillerHalf<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 128); }, aux, 0});
         j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinalDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
         return;
     }
-#if BBS_PAIR_SPLIT2
-    // both Miller loops on one six-lane group (the whole register file), then the final exponentiation two wavefronts per SIMD
-    pargs->single = 1;
-    j->stages.push_back({"pair_miller_both", [j, pargs, aux]() { return rt::launch<PairMillerBoth<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
-    j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinalDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
-#else
-    pargs->single = 0;
     j->stages.push_back({nm_dist, [j, pargs, aux]() { return rt::launch<PairDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
-#endif
 #endif
 }
 
@@ -1240,14 +1236,14 @@ int add_batch_combination(J* j, BvState<C>* bv, Ctx<C>* ctx, size_t n, const Ctx
     if (!co.out_aff)
         j->stages.push_back({"pip_tile_sums", [bv, strm]() { return rt::launch<PipTileSums<C>>(strm(), bv->tsum, (size_t)bv->tsum.M * bv->tsum.NW); }, aux, 0});
 #endif
-    add_pairing_stages<C>(j, &bv->pa_sum, aux, "rlc_pair_miller", "rlc_pair_final_exp", "rlc_pairing_6lane", true);
+    add_pairing_stages<C>(j, &bv->pa_sum, aux, "rlc_pair_miller", "rlc_pair_final_exp", "rlc_pairing_6lane", PairSplit::Always);
     return BBS_OK;
 }
 template <class C, class J>
 void add_batch_decision(J* j, BvState<C>* bv, PairArgs<C>* fallback, int joins_aux) {
     // no kernel of its own: the per-item kernel's lanes read the 16 verdicts first -- all passed: write Ok(true) and leave
     fallback->batch_ok = bv->batch_ok; fallback->n_checks = bv->n_checks;
-    add_pairing_stages<C>(j, fallback, 0, "fallback_pair_miller", "fallback_pair_final_exp", "fallback_pairing_6lane", false, joins_aux);
+    add_pairing_stages<C>(j, fallback, 0, "fallback_pair_miller", "fallback_pair_final_exp", "fallback_pairing_6lane", PairSplit::ByJobForm, joins_aux);
 }
 
 // =============================================================================================

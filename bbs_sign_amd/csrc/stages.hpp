@@ -36,44 +36,18 @@ constexpr int MAX_DST = 255;
 // them and bbs_job_fetch_status / bbs_job_wait then fail with BBS_E_STATE instead of reporting Ok(true) (fail closed).
 constexpr int8_t ST_PENDING = -128;   // accepted by validation, nothing computed yet
 constexpr int8_t ST_PAIRING = -127;   // every check before the pairing passed: the pairing product decides
-#ifndef BBS_PAIR_WAVES
-#define BBS_PAIR_WAVES 1
-#endif
-// A/B knobs (round 4): the throughput form of a per-item pairing check as TWO kernels -- PairMillerBoth (both Miller loops of
-// an item on one six-lane group, shared squarings: the first half of PairDist) and PairFinalDist (the final exponentiation)
-// -- so that the final exponentiation, which alone fits 256 registers with 6 spilled and the same instruction count
-// (profiles/r04_c_occupancy_resource_usage.txt), can run TWO wavefronts per SIMD (BBS_PAIRFINAL_WAVES = 2) while the Miller
-// loop (277 spills under that cap) keeps the whole register file.  Measured (profiles/r04_d_ab.log, two alternating repeats,
-// 96 steps): fused 1.511 / 1.513 M proof_verify/s, split with one wavefront per SIMD 1.511 / 1.513, split with two 1.490 /
-// 1.483 -- and a batch that is alone gets SLOWER (final exponentiation 2.45 -> 3.1 - 4.0 ms: the dispatcher packs two
-// wavefronts onto one SIMD while others idle).  Two co-resident wavefronts do not issue faster here: in time units the
-// kernels already run at 2.28 ns per wave-instruction per SIMD against 2.18 ns for this opcode mix at two wavefronts per
-// SIMD (tools/ubench, profiles/r03_p_ubench_valu_int.csv; the chip clocks down as more wavefronts issue).  Hence: fused.
-#ifndef BBS_PAIR_SPLIT2
-#define BBS_PAIR_SPLIT2 0
-#endif
-#ifndef BBS_PAIRFINAL_WAVES
-#define BBS_PAIRFINAL_WAVES 1
-#endif
-#ifndef BBS_MSM_WAVES
-#define BBS_MSM_WAVES 1          // multi-scalar-multiplication stages (2 and 3 measured: no gain, spills)
-#endif
+// Wavefronts per SIMD the kernels are compiled for (register caps).  Decided values: the retired alternatives -- the pairing
+// check as two kernels with two wavefronts per SIMD for the final exponentiation (profiles/r04_d_ab_split_pairing_two_waves.log),
+// MSM stages at 2 and 3 (no gain, spills) -- are listed in DESIGN.md "Retired experiments".
+constexpr int PAIR_WAVES = 1;         // every six-lane pairing kernel, PairFinalDist included (its own value was the retired experiment)
+constexpr int MSM_WAVES = 1;          // multi-scalar-multiplication stages
 // The doubling-chain kernels of proof_verify capped at 256 registers, so that two of their wavefronts -- or one and a
-// wavefront of a fixed-base chunk kernel (246) -- share a SIMD.  They are 64 wavefronts of 3 - 5 ms each per batch: alone on a
-// SIMD they keep the other 212 registers of it idle for that long.  Round 5, measured on the headline loop (profiles/r05_i_*,
-// three alternating repeats): BLS12-381 T1 chain 300 -> 256 registers (97 spilled) long_region 1.581 -> 1.606 M/s; the
-// single multiplication 354 -> 256 as well (251 spilled) no further gain (1.60 M) -- it stays at one.  BN254's three kernels
-// need 244 / 264 / 266: capped, 0 / 10 / 26 spilled; likewise BN254's PvChallenge(Bv), VfVarMul, MsmVarMul (264 - 268).
-#ifndef BBS_T1_WAVES
-#define BBS_T1_WAVES 2
-#endif
-#ifndef BBS_VARMUL_WAVES
-#define BBS_VARMUL_WAVES 1       // BLS12-381; BN254: 2 (chain_waves below)
-#endif
-#ifndef BBS_BN_CHAIN_WAVES
-#define BBS_BN_CHAIN_WAVES 2
-#endif
-template <class C> constexpr int chain_waves(int bls_default) { return C::FpP::N <= 10 ? BBS_BN_CHAIN_WAVES : bls_default; }
+// wavefront of a fixed-base chunk kernel (246) -- share a SIMD (profiles/r05_i_*): BLS12-381 T1 chain 300 -> 256 (97 spilled)
+// gains, the single multiplication (354, 251 spilled) does not and stays at one; BN254's kernels (244 - 268) are all capped.
+constexpr int T1_WAVES = 2;
+constexpr int VARMUL_WAVES = 1;       // BLS12-381; BN254: 2 (chain_waves below)
+constexpr int BN_CHAIN_WAVES = 2;
+template <class C> constexpr int chain_waves(int bls_default) { return C::FpP::N <= 10 ? BN_CHAIN_WAVES : bls_default; }
 
 // ---- context constants resident in HBM ------------------------------------------------------
 struct HashCtx {
@@ -105,12 +79,9 @@ struct CtxConsts {
 // padded to 128 (round 5): the tables are read at random, one entry per mixed addition, and an unaligned 112-byte entry
 // straddles two 128-byte lines in 7 cases of 8 -- the counters showed 2 x 205 MB fetched per 4096-item batch for 203 MB of
 // entries (profiles/r05_p_pmc.csv before the change).  Aligned, an entry is one line and seven 16-byte loads.  BN254's 80
-// bytes stay packed (16-byte aligned; padding them to 128 would cost 60 % more table memory).
-#ifndef BBS_FIX_TAB_PACKED
-#define BBS_FIX_TAB_PACKED 0     // A/B knob: 1 = entries packed at 2N words as before round 5
-#endif
+// bytes stay packed (16-byte aligned; padding them to 128 would cost 60 % more table memory).  A/B: profiles/r05_h_ab_table_entries_padded.log.
 template <class C>
-constexpr int fix_tab_stride() { return (!BBS_FIX_TAB_PACKED && 2 * C::FpP::N == 28) ? 32 : 2 * C::FpP::N; }
+constexpr int fix_tab_stride() { return 2 * C::FpP::N == 28 ? 32 : 2 * C::FpP::N; }
 // one entry (16-byte loads: every entry starts on a 16-byte boundary)
 template <class C>
 BBS_HD void fix_tab_load(const uint32_t* e, G1Aff<C>& q) {
@@ -647,7 +618,7 @@ struct PvScalars {
 // compute for such an item is never read (PvChallenge runs behind all three and skips it).
 template <class C>
 struct PvT1Chain {
-    static constexpr int WAVES_PER_EU = chain_waves<C>(BBS_T1_WAVES);
+    static constexpr int WAVES_PER_EU = chain_waves<C>(T1_WAVES);
     static BBS_HD void run(const PvArgs<C>& a, size_t i) {
         constexpr int N = C::FpP::N;
         constexpr int NC = C::FpP::NC;
@@ -706,7 +677,7 @@ struct PvT1Chain {
 // queues is a budget: DESIGN.md 5 rule 6).  Reads the points in canonical form, as the ingest stage left them.
 template <class C>
 struct PvVarMul {
-    static constexpr int WAVES_PER_EU = chain_waves<C>(BBS_VARMUL_WAVES);
+    static constexpr int WAVES_PER_EU = chain_waves<C>(VARMUL_WAVES);
     static __host__ __device__ int first_part(const PvArgs<C>& a) { return a.nvar == PV_NVAR ? 1 : 0; }
     static BBS_HD void run(const PvArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
@@ -732,7 +703,7 @@ struct PvVarMul {
 // everything on one stream (batch verification's throughput form), where two launches would run one after the other
 template <class C>
 struct PvChains {
-    static constexpr int WAVES_PER_EU = chain_waves<C>(BBS_T1_WAVES < BBS_VARMUL_WAVES ? BBS_T1_WAVES : BBS_VARMUL_WAVES);
+    static constexpr int WAVES_PER_EU = chain_waves<C>(T1_WAVES < VARMUL_WAVES ? T1_WAVES : VARMUL_WAVES);
     static __host__ __device__ size_t units(const PvArgs<C>& a) { return (size_t)1 + (size_t)(a.nvar - PvVarMul<C>::first_part(a)); }
     static BBS_HD void run(const PvArgs<C>& a, size_t t) {
         if (t < a.n) PvT1Chain<C>::run(a, t);
@@ -856,7 +827,7 @@ struct PairArgs {
     int gate;
     int8_t* out;              // result 1 / 0 per item (may alias the status array)
     uint32_t* fmiller;        // [2][12N][n]
-    int single;               // fmiller holds ONE value per item (PairMillerBoth), not one per pair (PairMillerHalf)
+    int single;               // always 0 (the one-value form was retired): fmiller holds one value per pair (PairMillerHalf)
     // batch verification: this launch is the per-item FALLBACK behind the combined checks -- if all n_checks of them passed
     // (batch_ok[k] == 1), every gated item's product is 1 (error 2^-128) and the lane only writes that; null otherwise
     const int8_t* batch_ok;
@@ -1311,7 +1282,7 @@ struct SgScalars {
 
 template <class C>
 struct SgMsmPart {
-    static constexpr int WAVES_PER_EU = BBS_MSM_WAVES;
+    static constexpr int WAVES_PER_EU = MSM_WAVES;
     static __host__ __device__ void run(const SgArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
         const size_t n = a.n;
@@ -1618,7 +1589,7 @@ struct PgBCombine {
 // degenerate step -- leaves comb_ok = 0 and the item's lanes take the joint chains instead: same group elements either way.
 template <class C>
 struct PgTables {
-    static constexpr int WAVES_PER_EU = BBS_MSM_WAVES;
+    static constexpr int WAVES_PER_EU = MSM_WAVES;
     static __host__ __device__ void run(const PgArgs<C>& a, size_t t) {
         using P = typename C::FpP;
         constexpr int N = P::N;
@@ -2018,7 +1989,7 @@ struct PairPrep {
 // =============================================================================================
 template <class C>
 struct PairDist {
-    static constexpr int WAVES_PER_EU = BBS_PAIR_WAVES;      // 1: the whole register file for one wavefront (measured best)
+    static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
         const int lane = (int)(t & 63);
         const int grp = lane / GRP;
@@ -2059,48 +2030,6 @@ struct PairDist {
     }
 };
 
-// ---- throughput form in two kernels (round 4, BBS_PAIR_SPLIT2): PairDist up to the end of the Miller loops; the value is
-// handed to PairFinalDist in HBM ([coefficient][2N][n], coalesced over the items' lanes m: 1.3 KB per item each way)
-template <class C>
-struct PairMillerBoth {
-    static constexpr int WAVES_PER_EU = BBS_PAIR_WAVES;
-    static __device__ void run(const PairArgs<C>& a, size_t t) {
-        constexpr int N = C::FpP::N;
-        const int lane = (int)(t & 63);
-        const int grp = lane / GRP;
-        if (grp >= GRP_PER_WAVE) return;
-        const size_t i = (t >> 6) * GRP_PER_WAVE + grp;
-        if (i >= a.n) return;
-        if (a.gate_arr[i] != a.gate) return;
-        if (pair_batch_passed<C>(a)) return;                   // PairFinalDist writes the verdict
-        Lane6 L{grp * GRP, lane - grp * GRP};
-        G1Aff<C> Pa = pair_load_point<C>(a, a.pa, i);
-        G1Aff<C> Pb = pair_load_point<C>(a, a.pb, i);
-        if (a.negate_b) Pb = g1a_neg<C>(Pb);
-        const CtxConsts<C>* cc = a.cc;
-        const bool skipA = g1a_is_inf<C>(Pa) | (cc->tab_pk.q_is_identity != 0);
-        const bool skipB = g1a_is_inf<C>(Pb) | (cc->tab_bp2.q_is_identity != 0);
-        Fp2<C> m = d_one<C>(L);
-        if (!(skipA & skipB)) {
-            int li = 0;
-            const int nops = cc->sched.n_ops;
-            for (int k = 0; k < nops; k++) {
-                if (cc->sched.op[k] == 0) {
-                    m = d_sqr<C>(L, m);
-                } else {
-                    if (!skipA) m = d_mul_line<C>(L, m, cc->tab_pk.e[li], Pa);
-                    if (!skipB) m = d_mul_line<C>(L, m, cc->tab_bp2.e[li], Pb);
-                    li++;
-                }
-            }
-            if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
-        }
-        uint32_t* o = a.fmiller + (size_t)L.m * 2 * N * a.n + i;
-#pragma unroll
-        for (int j = 0; j < N; j++) { o[(size_t)j * a.n] = m.c0.v[j]; o[(size_t)(N + j) * a.n] = m.c1.v[j]; }
-    }
-};
-
 // ---- latency form (round 3): the two Miller loops of an item on SEPARATE six-lane groups ------------------------------
 // PairDist runs both pairs of an item on one group (63 shared squarings + 2 x 68 line products) and then the final
 // exponentiation: 410 wavefronts of ~4.9 ms for a 4096-item batch on a chip of 1024 SIMDs.  When a batch has the chip to
@@ -2111,7 +2040,7 @@ struct PairMillerBoth {
 // 820 wavefronts x 0.66 + 410 wavefronts x 1 instead of 410 x 2: 17 % more wave-time, a critical path ~0.8 ms shorter.
 template <class C>
 struct PairMillerHalf {
-    static constexpr int WAVES_PER_EU = BBS_PAIR_WAVES;
+    static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
@@ -2146,8 +2075,7 @@ struct PairMillerHalf {
 };
 template <class C>
 struct PairFinalDist {
-    static constexpr int WAVES_PER_EU = BBS_PAIRFINAL_WAVES;      // 2: fits 256 registers, see BBS_PAIR_SPLIT2
-    static constexpr int V = BBS_PAIRFINAL_WAVES > 1 ? 1 : 0;     // its own instances of the non-inlined functions (pairing_dist.hpp d_final_exp)
+    static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
@@ -2168,10 +2096,10 @@ struct PairFinalDist {
             const uint32_t* p1 = a.fmiller + ((size_t)GRP + L.m) * 2 * N * a.n + i;
 #pragma unroll
             for (int j = 0; j < N; j++) { g1.c0.v[j] = p1[(size_t)j * a.n]; g1.c1.v[j] = p1[(size_t)(N + j) * a.n]; }
-            mf = d_mul<C, V>(L, g0, g1);
+            mf = d_mul<C>(L, g0, g1);
         }
         const Fp2<C> mfc = mf;
-        const Fp2<C> f = d_final_exp<C, V>(L, mfc, &a.cc->frob[0][0][0][0]);
+        const Fp2<C> f = d_final_exp<C>(L, mfc, &a.cc->frob[0][0][0][0]);
         const bool one = d_is_one<C>(L, f);
         if (L.m == 0) a.out[i] = one ? 1 : 0;
     }

@@ -14,7 +14,7 @@ curve = os.environ.get("CURVE", "bls12_381")
 suite, eng, gens, sk, msgs, disclosed, rnds = pc.bench_workload(curve, n, 32, 8, None, 16)
 if os.environ.get("VOUCH"):
     eng.set_points_in_subgroup(True)          # BLS12-381: the GLV split (BN254 has it always)
-print("curve", curve, "vouched", bool(os.environ.get("VOUCH")), "BBS_PG_COMB", os.environ.get("BBS_PG_COMB", "1"), flush=True)
+print("curve", curve, "vouched", bool(os.environ.get("VOUCH")), flush=True)
 sigs, st = eng.core_sign_batch(msgs)
 for form, name in ((False, "throughput form"),):
     eng.set_latency_mode(form)
