@@ -330,6 +330,58 @@ def check_error_semantics(curve, lib_path=None):
     eng2.close()
 
 
+def check_error_semantics_wire(curve, lib_path=None):
+    """The proof_verify cases of check_error_semantics through the WIRE form (proof octet strings in): the reference's
+    proof_verify_init verdicts -3 / -6 / -1, the duplicate-index panic -22 and the two Ok(false) cases must come out of the
+    wire ingest stage as they come out of the core one.  (Proof::default() has identity points, which octets_to_proof
+    rejects before core_proof_verify runs: the index error and the zero commitments are built on the valid proof's points.)"""
+    from bbs_sign_amd import api
+    rng = random.Random(7)
+    suite = bbs.SUITES[curve]
+    c = suite.curve
+    api_id = suite.api_id
+    L = 10
+    gens = gens_for(suite, L + 1)
+    sk = bbs.key_gen(suite, bytes([1] * 32), b"", b"BBS-SIG-KEYGEN-SALT-")
+    pk = bbs.sk_to_pk(suite, sk)
+    eng = make_engine(curve, gens, api_id, lib_path, sk=sk)
+    msgs = [rng.randrange(c.r) for _ in range(L)]
+    sig = eng.core_sign(b"", msgs)
+    disclosed = [0, 1, 5]
+    rnd = [rng.randrange(1, c.r) for _ in range(5 + L - 3)]
+    proof = eng.core_proof_gen(sig, b"", b"", msgs, disclosed, rnd)
+    dm = [msgs[i] for i in disclosed]
+
+    def with_commitments(cm):
+        return Proof(proof.a_bar, proof.b_bar, proof.d, proof.e_cap, proof.r1_cap, proof.r3_cap, cm, proof.challenge)
+    items = [
+        (proof, dm, disclosed),                                  # valid                                   -> 1
+        (proof, dm + [1], disclosed + [L + 1]),                  # index 11 >= l = 7 commitments + 4 indexes -> Err -3
+        (with_commitments([0] * 7), dm, disclosed),              # 7 zero commitments                      -> Ok(false)
+        (proof, dm, [1, 0, 5]),                                  # caller order matters                    -> Ok(false)
+        (proof, dm[:2], disclosed),                              # messages != indexes                     -> Err -6
+        (proof, dm, [0, 1, 1]),                                  # duplicate -> commitments[i] out of bounds -> panic
+        (with_commitments(proof.commitments[:-1]), dm, disclosed),   # l = 9 != generators - 1             -> Err -1
+    ]
+    octs = [api.proof_to_octets(curve, x[0], lib_path) for x in items]
+    st = eng.proof_verify_octets_batch(octs, [x[1] for x in items], [x[2] for x in items])
+    assert [int(x) for x in st] == [1, -3, 0, 0, -6, -22, -1], list(st)
+    for (p, m, d), s in zip(items, st):
+        op = bbs.Proof(p.a_bar, p.b_bar, p.d, p.e_cap, p.r1_cap, p.r3_cap, list(p.commitments), p.challenge)
+        try:
+            want = int(bbs.core_proof_verify(suite, pk, op, gens, b"", b"", m, d, api_id))
+        except bbs.BbsError as e:
+            want = {"InvalidDisclosedIndex": -3, "InvalidIndicesAndMessagesLength": -6,
+                    "InvalidMessageAndGeneratorsLength": -1}[e.variant]
+        except bbs.BbsPanic:
+            want = -22
+        assert want == int(s), (want, int(s))
+    # the same verdicts from the core form, whose ingest stage shares the checks
+    st_core = eng.core_proof_verify_batch([x[0] for x in items], [x[1] for x in items], [x[2] for x in items])
+    assert [int(x) for x in st_core] == [int(x) for x in st], (list(st_core), list(st))
+    eng.close()
+
+
 def check_empty_batches(curve, lib_path=None):
     """n = 0 through every batched entry point (the reference's functions are per item; an empty batch is the
     degenerate case of the batch boundary), in the per-item and the batch-verification mode."""

@@ -39,6 +39,11 @@ def test_error_semantics(twin, curve):
 
 
 @pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
+def test_error_semantics_wire(twin, curve):
+    pc.check_error_semantics_wire(curve, twin)
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
 def test_primitives(twin, curve):
     pc.check_primitives(curve, twin)
 
