@@ -100,6 +100,11 @@ SIGNATURES = {
     "bbs_verify_wire_batch": (ci, [vp, sz, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
     # keyed verification: the context's key set, item i under key key_index[i] (the argument after n)
     "bbs_ctx_set_public_keys": (ci, [vp, sz, c_u8p, c_i8p, c_i8p]),
+    "bbs_ctx_add_public_keys": (ci, [vp, sz, c_u8p, c_i8p, c_i8p, c_u32p]),
+    "bbs_ctx_add_public_keys_octets": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, c_i8p, c_u32p]),
+    "bbs_ctx_public_key_count": (sz, [vp]),
+    "bbs_selftest_key_entries": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, ci, c_u8p, c_i8p, c_u8p]),
+    "bbs_selftest_key_entry_bytes": (sz, [ci]),
     "bbs_core_proof_verify_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,
                                                 c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_core_proof_verify_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,

@@ -274,3 +274,26 @@ def octets_to_public_key(curve: str, octets: bytes, lib_path: Optional[str] = No
     b = rec.tobytes()
     f = [int.from_bytes(b[i * fpb:(i + 1) * fpb], "little") for i in range(4)]
     return PublicKey(curve, ((f[0], f[1]), (f[2], f[3])), lib_path, device)
+
+
+def register_public_keys(curve: str, octets: Sequence[bytes], L: int = 0, lib_path: Optional[str] = None,
+                         device: int = 0) -> Tuple[int, List[PublicKey]]:
+    """Decode, check and register many issuer keys as they travel (compressed octets) in ONE call: they are appended to the key
+    set of the (curve, L) engine (bbs_ctx_add_public_keys_octets), ready for the keyed verification entry points.  Returns
+    ``(first_index, keys)``: keys[k] is what octets_to_public_key returns for octets[k] and has index first_index + k in the set.
+    A refused key raises BbsError with the code octets_to_public_key raises for it (the first refused key's).  The call is one
+    pass over the keys, so the set HAS GROWN by len(octets) entries when it raises -- the accepted keys are registered, a
+    refused key occupies an index that no item can use -- and the exception carries ``first_index`` and ``statuses`` (one per
+    key: 1, -40, -41).  Only a string of the wrong length (-42) is refused before anything is registered."""
+    lib = _lib.load_library(lib_path)
+    fpb = int(lib.bbs_fp_bytes(_curve_id(curve)))
+    if any(len(o) != 2 * fpb for o in octets):
+        raise BbsError(-42)
+    eng = _engine(curve, L, device=device, lib_path=lib_path)
+    first, st, keys = eng.add_public_keys_octets(list(octets))
+    for code in st:
+        if code != 1:
+            e = BbsError(int(code))
+            e.first_index, e.statuses = first, [int(x) for x in st]
+            raise e
+    return first, [PublicKey(curve, k, lib_path, device) for k in keys]

@@ -664,10 +664,23 @@ int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, con
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_submit(ctx, n, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
-// keyed verification (keyed.hpp)
+// keyed verification (keyed.hpp); registration of the key set: runtime.hpp add_keys, op_key.hpp
 int bbs_ctx_set_public_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* pk, const int8_t* is_identity, int8_t* key_status) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_public_keys(n_keys, pk, is_identity, key_status); });
+}
+int bbs_ctx_add_public_keys(bbs_ctx* ctx, size_t n, const uint8_t* pk, const int8_t* is_identity, int8_t* key_status, uint32_t* first_index) {
+    if (!ctx || !first_index || (n && (!pk || !key_status))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->add_keys(false, n, pk, is_identity, nullptr, key_status, nullptr, nullptr, first_index); });
+}
+int bbs_ctx_add_public_keys_octets(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int8_t* key_status, uint8_t* pk_affine_out,
+                                   int8_t* is_identity_out, uint32_t* first_index) {
+    if (!ctx || !first_index || (n && (!pk_octets || !key_status))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->add_keys(false, n, nullptr, nullptr, pk_octets, key_status, pk_affine_out, is_identity_out, first_index); });
+}
+size_t bbs_ctx_public_key_count(const bbs_ctx* ctx) {
+    if (!ctx) return 0;
+    return ctx->curve == BBS_CURVE_BLS12_381 ? static_cast<const Ctx<BlsCurve>*>(ctx)->public_key_count() : static_cast<const Ctx<BnCurve>*>(ctx)->public_key_count();
 }
 int bbs_core_proof_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* pf, const uint8_t* cm,
                                        const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di, const uint64_t* dio,
@@ -1063,6 +1076,16 @@ int bbs_public_key_from_octets(int curve, const uint8_t* octets, uint8_t* pk_aff
 int bbs_selftest_f12(bbs_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* out_single, uint8_t* out_dist) {
     if (!ctx || !a || !b || !out_single || !out_dist) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return selftest_f12(c, op, a, b, out_single, out_dist); });
+}
+
+int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, const int8_t* is_identity, const uint8_t* pk_octets, int path,
+                             uint8_t* entries_out, int8_t* status_out, uint8_t* pk_affine_out) {
+    if (!ctx || (path != 0 && path != 1) || (n && ((!pk_affine && !pk_octets) || !entries_out || !status_out))) return BBS_E_ARG;
+    if (pk_octets) { pk_affine = nullptr; is_identity = nullptr; }
+    return with_curve(ctx, [&](auto* c) { return selftest_key_entries(c, n, pk_affine, is_identity, pk_octets, path, entries_out, status_out, pk_affine_out); });
+}
+size_t bbs_selftest_key_entry_bytes(int curve) {
+    return curve == BBS_CURVE_BLS12_381 ? sizeof(KeyEntry<BlsCurve>) : curve == BBS_CURVE_BN254 ? sizeof(KeyEntry<BnCurve>) : 0;
 }
 
 int bbs_selftest_inv(int curve, int scalar_field, const uint8_t* x, uint8_t* out_safegcd, uint8_t* out_fermat) {

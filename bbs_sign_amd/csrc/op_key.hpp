@@ -1,0 +1,169 @@
+// Host orchestration of key registration (template over the curve); instantiated by tu_key_*.hip.  runtime.hpp Ctx has the
+// contract of add_keys, stages_key.hpp the device stage.
+#pragma once
+#include "runtime.hpp"
+#include "host_codec.hpp"
+#include "stages_key.hpp"
+
+// One key by the host functions (host_g2.hpp, host_codec.hpp): the reference the device stage is compared with, and the path
+// of every registration call (runtime.hpp KEY_BUILD_ON_DEVICE).  e is filled completely (zero behind the lines); the status is the stage's.  The line
+// entries are stored as the representatives in [0, p), as the stage stores them.
+template <class C>
+int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out) const {
+    using P = typename C::FpP;
+    std::memset(&e, 0, sizeof(e));
+    e.hash = key_hash0();
+    e.tab.q_is_identity = 1;
+    if (rec_out) std::memset(rec_out, 0, 4 * FPB);
+    if (inf_out) *inf_out = 0;
+    G2Aff<C> q{};
+    if (oct) {
+        const int rc = codec::g2_decompress<C>(oct, q);
+        if (rc == -1) return (int8_t)BBS_ST_NONCANONICAL;
+        if (rc) return (int8_t)BBS_ST_NOT_ON_CURVE;
+    } else {
+        q.inf = is_inf;
+        if (q.inf) { q.x = f2_zero<C>(); q.y = f2_zero<C>(); }
+        else if (!fe_from_le_bytes<P>(rec, q.x.c0) || !fe_from_le_bytes<P>(rec + FPB, q.x.c1) ||
+                 !fe_from_le_bytes<P>(rec + 2 * FPB, q.y.c0) || !fe_from_le_bytes<P>(rec + 3 * FPB, q.y.c1)) return (int8_t)BBS_ST_NOT_ON_CURVE;
+    }
+    if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q) || !build_line_table<C>(q, e.tab)) {
+        std::memset(&e.tab, 0, sizeof(e.tab));
+        e.tab.q_is_identity = 1;
+        return (int8_t)BBS_ST_NOT_ON_CURVE;
+    }
+    for (int s = 0; s < e.tab.n_lines; s++) { e.tab.e[s].c = f2_canon<C>(e.tab.e[s].c); e.tab.e[s].nl = f2_canon<C>(e.tab.e[s].nl); }
+    domain_midstate(q, e.hash);
+    if (oct) {
+        if (inf_out) *inf_out = q.inf ? 1 : 0;
+        if (rec_out && !q.inf) {
+            fe_to_le_bytes<P>(q.x.c0, rec_out); fe_to_le_bytes<P>(q.x.c1, rec_out + FPB);
+            fe_to_le_bytes<P>(q.y.c0, rec_out + 2 * FPB); fe_to_le_bytes<P>(q.y.c1, rec_out + 3 * FPB);
+        }
+    }
+    return 1;
+}
+
+// n entries into d_out (device memory of the context's device): by the KeyBuild stage, or on host threads and one upload.
+// Synchronises the context's stream.  status / rec_out / inf_out: host arrays, the last two may be null.
+template <class C>
+int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
+                      int8_t* status, uint8_t* rec_out, int8_t* inf_out) {
+    if (!n) return BBS_OK;
+    if (!on_device) {
+        std::vector<KeyEntry<C>> host(n);
+        auto one = [&](size_t k) {
+            status[k] = host_key_entry(rec ? rec + k * 4 * FPB : nullptr, !oct && is_inf && is_inf[k] != 0, oct ? oct + k * 2 * FPB : nullptr,
+                                       host[k], rec_out ? rec_out + k * 4 * FPB : nullptr, inf_out ? inf_out + k : nullptr);
+        };
+        const size_t nt = std::min<size_t>({(size_t)16, n, (size_t)std::max(1u, std::thread::hardware_concurrency())});
+        if (nt <= 1) { for (size_t k = 0; k < n; k++) one(k); }
+        else {
+            std::vector<std::thread> th;
+            for (size_t t = 0; t < nt; t++) th.emplace_back([&, t]() { for (size_t k = t; k < n; k += nt) one(k); });
+            for (auto& x : th) x.join();
+        }
+        if (rt::h2d(d_out, host.data(), n * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
+        return BBS_OK;
+    }
+    // what follows the key in the domain prefix, the same for every key: built once (domain_midstate hashes the same bytes)
+    std::vector<uint8_t> blob(sizeof(HashCtx));
+    {
+        const HashCtx h0 = key_hash0();
+        std::memcpy(blob.data(), &h0, sizeof(h0));
+        for (int k = 7; k >= 0; k--) blob.push_back((uint8_t)((uint64_t)L >> (8 * k)));
+        uint8_t buf[FPB];
+        for (const auto& g : gens) { g1_compress_host<C>(g, buf); blob.insert(blob.end(), buf, buf + FPB); }
+        blob.insert(blob.end(), api_id.begin(), api_id.end());
+    }
+    const size_t in_bytes = n * (oct ? 2 : 4) * FPB;
+    DevBuf d_in, d_inf, d_st, d_rec, d_io, d_ws, d_blob;
+    const std::vector<int> bits = miller_bits<C>();
+    size_t n_steps = bits.size() + (C::ID == 1 ? 2 : 0);
+    for (int b : bits) n_steps += b ? 1 : 0;
+    if (bits.size() > (size_t)KEY_MAX_BITS || n_steps > (size_t)MAX_LINES) return BBS_E_STATE;
+    if (d_in.alloc(in_bytes) || d_st.alloc(n) || d_blob.alloc(blob.size()) || d_ws.alloc(key_build_ws_words<C>(n_steps) * n * 4)) return BBS_E_NOMEM;
+    if (oct ? (d_rec.alloc(n * 4 * FPB) || d_io.alloc(n)) : (is_inf && d_inf.alloc(n))) return BBS_E_NOMEM;
+    auto fail = [&](int rc) { (void)rt::sync(stream); return rc; };      // the buffers must not go back while the stream uses them
+    if (rt::h2d_async(d_in.p, oct ? oct : rec, in_bytes, stream) || rt::h2d_async(d_blob.p, blob.data(), blob.size(), stream)) return fail(BBS_E_HIP);
+    if (d_inf.p && rt::h2d_async(d_inf.p, is_inf, n, stream)) return fail(BBS_E_HIP);
+    if (rt::dmemset(d_out, 0, n * sizeof(KeyEntry<C>), stream)) return fail(BBS_E_HIP);
+    KeyBuildArgs<C> a{};
+    a.n = n;
+    a.rec = oct ? nullptr : d_in.as<uint32_t>();
+    a.is_inf = d_inf.as<int8_t>();
+    a.oct = oct ? d_in.as<uint32_t>() : nullptr;
+    a.out = d_out;
+    a.status = d_st.as<int8_t>();
+    a.rec_out = d_rec.as<uint32_t>();
+    a.inf_out = d_io.as<int8_t>();
+    a.ws = d_ws.as<uint32_t>();
+    a.hash0 = d_blob.as<HashCtx>();
+    a.suffix = d_blob.as<uint8_t>() + sizeof(HashCtx);
+    a.suffix_len = (uint32_t)(blob.size() - sizeof(HashCtx));
+    a.b2 = g2_b<C>();
+    const G2Aff<C> gen = g2_generator<C>();
+    a.gen_x = gen.x; a.gen_y = gen.y;
+    a.frob_x = f2_from_consts<C>(C::K::FROB[0][2][0], C::K::FROB[0][2][1]);
+    a.frob_y = f2_from_consts<C>(C::K::FROB[0][3][0], C::K::FROB[0][3][1]);
+    a.n_bits = (int)bits.size();
+    for (size_t k = 0; k < bits.size(); k++) a.bits[k] = (uint8_t)bits[k];
+    if (rt::launch<KeyBuild<C>>(stream, a, n)) return fail(BBS_E_HIP);
+    if (rt::d2h_async(status, d_st.p, n, stream)) return fail(BBS_E_HIP);
+    if (oct && rec_out && rt::d2h_async(rec_out, d_rec.p, n * 4 * FPB, stream)) return fail(BBS_E_HIP);
+    if (oct && inf_out && rt::d2h_async(inf_out, d_io.p, n, stream)) return fail(BBS_E_HIP);
+    return rt::sync(stream) ? BBS_E_HIP : BBS_OK;       // (the workspace and the inputs go back with the locals, behind the synchronisation)
+}
+
+template <class C>
+int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, int8_t* key_status,
+                     uint8_t* rec_out, int8_t* inf_out, uint32_t* first_index) {
+    if (n && !rec && !oct) return BBS_E_ARG;
+    if (!gens_set) return BBS_E_STATE;
+    if (use()) return BBS_E_HIP;
+    const std::shared_ptr<const KeySet> old = replace ? nullptr : keys;
+    const size_t n_old = old ? old->n : 0;
+    if (n_old + n > 0xFFFFFFF0u) return BBS_E_ARG;
+    if (!n) { if (first_index) *first_index = (uint32_t)n_old; return BBS_OK; }
+    std::shared_ptr<KeySet> ks(new KeySet());
+    ks->n = n_old + n;
+    ks->status.assign(ks->n, (int8_t)BBS_ST_NOT_ON_CURVE);
+    if (ks->d.alloc(ks->n * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
+    if (n_old) {
+        std::copy(old->status.begin(), old->status.end(), ks->status.begin());
+        if (rt::d2d_async(ks->d.p, old->d.p, n_old * sizeof(KeyEntry<C>), stream)) return BBS_E_HIP;
+    }
+    if (const int rc = key_build(ks->d.template as<KeyEntry<C>>() + n_old, n, rec, is_inf, oct, KEY_BUILD_ON_DEVICE,
+                                 ks->status.data() + n_old, rec_out, inf_out)) {
+        (void)rt::sync(stream);      // (the copy of the old entries must not outlive the buffer it writes)
+        return rc;
+    }
+    if (key_status) std::memcpy(key_status, ks->status.data() + n_old, n);
+    if (first_index) *first_index = (uint32_t)n_old;
+    keys = std::move(ks);
+    return BBS_OK;
+}
+
+// bbs_selftest_key_entries: the entries, statuses and (octet form) decoded records of n keys by path 0 = the host functions,
+// one key at a time, or path 1 = the KeyBuild stage whatever the key count; the context's key set is not touched
+template <class C>
+int selftest_key_entries(Ctx<C>* ctx, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, int path,
+                         uint8_t* entries_out, int8_t* status_out, uint8_t* rec_out) {
+    constexpr size_t FPB = Ctx<C>::FPB;
+    if (!ctx->gens_set) return BBS_E_STATE;
+    if (ctx->use()) return BBS_E_HIP;
+    if (path == 0) {
+        KeyEntry<C> e;
+        for (size_t k = 0; k < n; k++) {
+            status_out[k] = ctx->host_key_entry(rec ? rec + k * 4 * FPB : nullptr, !oct && is_inf && is_inf[k] != 0, oct ? oct + k * 2 * FPB : nullptr,
+                                                e, oct && rec_out ? rec_out + k * 4 * FPB : nullptr, nullptr);
+            std::memcpy(entries_out + k * sizeof(e), &e, sizeof(e));
+        }
+        return BBS_OK;
+    }
+    DevBuf d;
+    if (d.alloc(n * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
+    if (const int rc = ctx->key_build(d.as<KeyEntry<C>>(), n, rec, is_inf, oct, true, status_out, oct ? rec_out : nullptr, nullptr)) return rc;
+    if (rt::d2h(entries_out, d.p, n * sizeof(KeyEntry<C>), ctx->stream) || rt::sync(ctx->stream)) return BBS_E_HIP;
+    return BBS_OK;
+}

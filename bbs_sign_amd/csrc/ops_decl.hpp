@@ -79,6 +79,7 @@ template <class C> int msm_pippenger(Ctx<C>*, size_t, const uint8_t*, const uint
 template <class C> int g1_decompress_batch(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*);
 template <class C> int signatures_from_octets_batch(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*);
 template <class C> int proofs_from_octets_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, uint8_t*, uint8_t*, uint64_t*, int8_t*);
+template <class C> int selftest_key_entries(Ctx<C>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);
 extern template int pv_upload<BlsCurve>(Ctx<BlsCurve>*, size_t, const PvIn&, bbs_job**);
 extern template int pv_upload<BlsCurve, true>(Ctx<BlsCurve>*, size_t, const PvIn&, bbs_job**);
 extern template int pv_upload<BnCurve>(Ctx<BnCurve>*, size_t, const PvIn&, bbs_job**);
@@ -109,3 +110,7 @@ extern template int signatures_from_octets_batch<BnCurve>(Ctx<BnCurve>*, size_t,
 extern template int proofs_from_octets_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, uint8_t*, uint8_t*, uint64_t*, int8_t*);
 extern template int selftest_f12<BlsCurve>(Ctx<BlsCurve>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 extern template int selftest_f12<BnCurve>(Ctx<BnCurve>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+extern template int Ctx<BlsCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
+extern template int selftest_key_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);
+extern template int Ctx<BnCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
+extern template int selftest_key_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);

@@ -695,48 +695,34 @@ struct Ctx : bbs_ctx {
         sk_set = false;
         return set_pk_internal(q);
     }
-    // bbs_ctx_set_public_keys: every key is checked as set_public_key checks it and gets its W line table and domain
-    // midstate on the host (the subgroup check and the line table: 16 host threads; 4096 BLS12-381 keys in 0.52 s),
-    // then the whole set is ONE device array.  Needs the generators (set_generators drops the set: its midstates would
-    // be stale).  On failure the previous set stays.
+    // Key registration (op_key.hpp; stages_key.hpp has the device stage).  A set grows by APPENDING: add_keys builds a new
+    // immutable KeySet of n_old + n entries -- exactly that many, nothing is over-allocated -- copies the old entries device to
+    // device on the context's stream, prepares the n new entries in place behind them and swaps the pointer; jobs in flight keep
+    // the set they hold, a failure leaves the old set.  bbs_ctx_set_public_keys is "new empty set + add".  Needs the generators
+    // (set_generators drops the set: its midstates would be stale).
+    // Every call prepares its new keys on up to 16 host threads (host_key_entry), as every registration did before.  The device
+    // stage KeyBuild (stages_key.hpp) computes the same entries, byte for byte, but it has NOT BEEN TIMED against the host
+    // threads, so no call of the library uses it yet: it is reachable through bbs_selftest_key_entries (path 1) only.
+    // tools/keyed_bench.py --reg-only times both; a threshold belongs here once that table exists (DESIGN.md 8 "Registration").
+    static constexpr bool KEY_BUILD_ON_DEVICE = false;
+    HashCtx key_hash0() const {      // what every entry's HashCtx starts from: dst_h2s of the context, dom_* zero
+        HashCtx h;
+        std::memset(&h, 0, sizeof(h));
+        std::memcpy(h.dst_h2s, hc.hash.dst_h2s, sizeof(h.dst_h2s));
+        h.dst_h2s_len = hc.hash.dst_h2s_len;
+        return h;
+    }
+    int8_t host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out) const;
+    int key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
+                  int8_t* status, uint8_t* rec_out, int8_t* inf_out);
+    int add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, int8_t* key_status,
+                 uint8_t* rec_out, int8_t* inf_out, uint32_t* first_index);
     int set_public_keys(size_t n_keys, const uint8_t* b, const int8_t* is_identity, int8_t* key_status) {
         if (n_keys && !b) return BBS_E_ARG;
         if (!n_keys) { keys.reset(); return BBS_OK; }
-        if (!gens_set) return BBS_E_STATE;
-        if (use()) return BBS_E_HIP;
-        std::shared_ptr<KeySet> ks(new KeySet());
-        ks->n = n_keys;
-        ks->status.assign(n_keys, (int8_t)BBS_ST_NOT_ON_CURVE);
-        std::vector<KeyEntry<C>> host(n_keys);
-        auto one = [&](size_t k) {
-            KeyEntry<C>& e = host[k];
-            std::memset(&e, 0, sizeof(e));
-            e.hash = hc.hash;                           // dst_h2s of the context
-            e.tab.q_is_identity = 1;
-            G2Aff<C> q{};
-            q.inf = is_identity && is_identity[k] != 0;
-            const uint8_t* p = b + k * 4 * FPB;
-            using P = typename C::FpP;
-            if (q.inf) { q.x = f2_zero<C>(); q.y = f2_zero<C>(); }
-            else if (!fe_from_le_bytes<P>(p, q.x.c0) || !fe_from_le_bytes<P>(p + FPB, q.x.c1) ||
-                     !fe_from_le_bytes<P>(p + 2 * FPB, q.y.c0) || !fe_from_le_bytes<P>(p + 3 * FPB, q.y.c1)) return;
-            if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q) || !build_line_table<C>(q, e.tab)) { e.tab.q_is_identity = 1; e.tab.n_lines = 0; return; }
-            domain_midstate(q, e.hash);
-            ks->status[k] = 1;
-        };
-        const size_t nt = std::min<size_t>({(size_t)16, n_keys, (size_t)std::max(1u, std::thread::hardware_concurrency())});
-        if (nt <= 1) { for (size_t k = 0; k < n_keys; k++) one(k); }
-        else {
-            std::vector<std::thread> th;
-            for (size_t t = 0; t < nt; t++) th.emplace_back([&, t]() { for (size_t k = t; k < n_keys; k += nt) one(k); });
-            for (auto& x : th) x.join();
-        }
-        if (ks->d.alloc(n_keys * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
-        if (rt::h2d(ks->d.p, host.data(), n_keys * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
-        if (key_status) std::memcpy(key_status, ks->status.data(), n_keys);
-        keys = std::move(ks);
-        return BBS_OK;
+        return add_keys(true, n_keys, b, is_identity, nullptr, key_status, nullptr, nullptr, nullptr);
     }
+    size_t public_key_count() const { const auto ks = keys; return ks ? ks->n : 0; }
     int set_secret_key(const uint8_t* sk32) {
         if (!sk32) return BBS_E_ARG;
         uint32_t l[8];

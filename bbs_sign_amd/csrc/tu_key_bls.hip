@@ -1,0 +1,6 @@
+// explicit instantiation: key registration for BlsCurve
+#include "op_key.hpp"
+template int8_t Ctx<BlsCurve>::host_key_entry(const uint8_t*, bool, const uint8_t*, KeyEntry<BlsCurve>&, uint8_t*, int8_t*) const;
+template int Ctx<BlsCurve>::key_build(KeyEntry<BlsCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, bool, int8_t*, uint8_t*, int8_t*);
+template int Ctx<BlsCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
+template int selftest_key_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);

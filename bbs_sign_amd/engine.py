@@ -205,6 +205,62 @@ class Engine:
                                                    st.ctypes.data_as(_lib.c_i8p)), "bbs_ctx_set_public_keys")
         return st[:n]
 
+    def _key_records(self, keys):
+        n = len(keys)
+        rec = 4 * self.fpb
+        buf = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        ident = np.zeros(max(n, 1), dtype=np.int8)
+        for k, pk in enumerate(keys):
+            if pk is None:
+                ident[k] = 1
+                continue
+            (x0, x1), (y0, y1) = pk
+            buf[k * rec:(k + 1) * rec] = np.frombuffer(self._fp(x0) + self._fp(x1) + self._fp(y0) + self._fp(y1), dtype=np.uint8)
+        return buf, ident
+
+    def add_public_keys(self, keys):
+        """bbs_ctx_add_public_keys: append ``keys`` (as for set_public_keys) to the context's key set; the keys already there keep
+        their indexes.  Returns ``(first_index, statuses)``: key k of the call has index first_index + k, refused keys (-41)
+        included."""
+        n = len(keys)
+        buf, ident = self._key_records(keys)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        first = ctypes.c_uint32(0)
+        self._chk(self.lib.bbs_ctx_add_public_keys(self.h, n, _u8(buf), ident.ctypes.data_as(_lib.c_i8p), st.ctypes.data_as(_lib.c_i8p),
+                                                   ctypes.byref(first)), "bbs_ctx_add_public_keys")
+        return int(first.value), st[:n]
+
+    def add_public_keys_octets(self, octets):
+        """bbs_ctx_add_public_keys_octets: append keys given as compressed octet strings (2 * fp_bytes each).  Returns
+        ``(first_index, statuses, keys)``: statuses 1 / -40 / -41 as octets_to_public_key decides them, ``keys[k]`` the decoded
+        key as set_public_keys takes it (None for the identity and for a refused key)."""
+        n = len(octets)
+        ob = 2 * self.fpb
+        for o in octets:
+            if len(o) != ob:
+                raise ValueError("public key octets: %d bytes, expected %d" % (len(o), ob))
+        buf = _bytes_arr(b"".join(bytes(o) for o in octets))
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        rec = np.zeros(max(n, 1) * 2 * ob, dtype=np.uint8)
+        ident = np.zeros(max(n, 1), dtype=np.int8)
+        first = ctypes.c_uint32(0)
+        self._chk(self.lib.bbs_ctx_add_public_keys_octets(self.h, n, _u8(buf), st.ctypes.data_as(_lib.c_i8p), _u8(rec),
+                                                          ident.ctypes.data_as(_lib.c_i8p), ctypes.byref(first)),
+                  "bbs_ctx_add_public_keys_octets")
+        b = rec.tobytes()
+        keys = []
+        for k in range(n):
+            if st[k] != 1 or ident[k]:
+                keys.append(None)
+                continue
+            f = [int.from_bytes(b[k * 2 * ob + i * self.fpb:k * 2 * ob + (i + 1) * self.fpb], "little") for i in range(4)]
+            keys.append(((f[0], f[1]), (f[2], f[3])))
+        return int(first.value), st[:n], keys
+
+    def public_key_count(self) -> int:
+        """bbs_ctx_public_key_count: keys in the context's key set, refused ones included."""
+        return int(self.lib.bbs_ctx_public_key_count(self.h))
+
     @staticmethod
     def _key_index(key_index, n):
         ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint32).reshape(-1))

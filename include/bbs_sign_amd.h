@@ -313,15 +313,37 @@ int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* signature_octet
  * (src/verify.rs:18-50, src/proof_verify.rs:19-61); here a context holds a KEY SET beside its generators and every item of a
  * keyed batch names its key by index.  The fixed-base tables, which depend only on the generators and api_id, are shared by
  * all keys; a key costs its W line table and its domain midstate (~30 KB of device memory on BLS12-381).
+ * A key set GROWS BY APPENDING (bbs_ctx_add_public_keys*): keys already in the set keep their index and their bytes, so a
+ * verifier that meets its issuers one after another prepares every key once.  A key is prepared -- decoded, checked to be on
+ * the twist and of order r, its line table and midstate built -- on up to 16 host threads, then uploaded.  (A device stage
+ * that prepares a key per lane exists and gives the same entries byte for byte -- bbs_selftest_key_entries -- but no call
+ * uses it until it has been timed against the host threads.)  What is allocated: one device array of exactly (keys in the
+ * set) entries of bbs_selftest_key_entry_bytes(curve) bytes, nothing spare; an append allocates the new array, copies the old
+ * entries device to device and frees the old array with its last holder.
  * ------------------------------------------------------------------------------------------ */
 /* n_keys issuer public keys (affine records as bbs_ctx_set_public_key; is_identity may be NULL = none).  key_status[k] (may
  * be NULL): 1, or BBS_ST_NOT_ON_CURVE for a key bbs_ctx_set_public_key would refuse (not on the twist / not of order r).
- * Replaces the context's previous key set; n_keys = 0 clears it.  Independent of bbs_ctx_set_public_key.  Needs the
- * generators (BBS_E_STATE); bbs_ctx_set_generators clears the key set.  A set is immutable once built and every keyed job
- * holds the set it was created with: replacing it while jobs are in flight does not change their results.  BBS_E_NOMEM if
- * the set does not fit on the device (the previous set stays). */
+ * Replaces the context's previous key set (a new empty set, then an append); n_keys = 0 clears it.  Independent of
+ * bbs_ctx_set_public_key.  Needs the generators (BBS_E_STATE); bbs_ctx_set_generators clears the key set.  A set is immutable
+ * once built and every keyed job holds the set it was created with: replacing it or appending to it while jobs are in flight
+ * does not change their results.  BBS_E_NOMEM if the set does not fit on the device (the previous set stays). */
 int bbs_ctx_set_public_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* pk_affine, const int8_t* is_identity,
                             int8_t* key_status);
+/* Append n keys to the context's key set (to an empty set when there is none); their indexes are [*first_index, *first_index
+ * + n).  Entries already in the set keep their index and their bytes.  Jobs in flight keep the set they were created with.
+ * Refused keys still occupy an index (key_status as bbs_ctx_set_public_keys; items naming them get BBS_ST_UNKNOWN_KEY).  n = 0
+ * only reports the set's size in *first_index.  BBS_E_ARG for a NULL first_index, or a NULL pk_affine or key_status with n >
+ * 0; BBS_E_STATE without generators; on any failure the set stays as it was. */
+int bbs_ctx_add_public_keys(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, const int8_t* is_identity,
+                            int8_t* key_status, uint32_t* first_index);
+/* The same for keys as they travel: n compressed octet strings of 2 * fp_bytes each, the format bbs_public_key_to_octets
+ * writes.  key_status[k]: 1, BBS_ST_NONCANONICAL or BBS_ST_NOT_ON_CURVE -- what bbs_public_key_from_octets returns for that
+ * string (with 1 for BBS_OK); the identity encoding is an accepted identity key.  pk_affine_out (n records, may be NULL) and
+ * is_identity_out (n flags, may be NULL) receive the decoded keys, zero for a refused key. */
+int bbs_ctx_add_public_keys_octets(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int8_t* key_status,
+                                   uint8_t* pk_affine_out, int8_t* is_identity_out, uint32_t* first_index);
+/* keys in the context's key set, refused ones included (0: no set) */
+size_t bbs_ctx_public_key_count(const bbs_ctx* ctx);
 /* Keyed forms of bbs_core_proof_verify_*, bbs_proof_verify_wire_*, bbs_core_verify_* and bbs_verify_wire_*: the arguments
  * of the un-keyed form plus key_index (n entries) after n.  For an item whose key_index names an accepted key the status is
  * what the un-keyed form gives on a context with the same generators, api_id, window bits and modes and that key set by
@@ -685,6 +707,15 @@ int bbs_proofs_from_octets_batch(bbs_ctx* ctx, size_t n, const uint8_t* octets, 
 int bbs_public_key_to_octets(int curve, const uint8_t* pk_affine, int is_identity, uint8_t* out /* 2 * fp_bytes */);
 int bbs_public_key_from_octets(int curve, const uint8_t* octets, uint8_t* pk_affine_out, int* is_identity_out);
 
+/* Key registration self-test: the key-set entries of n keys by two implementations; the caller compares the outputs.  Keys as
+ * bbs_ctx_add_public_keys takes them, or, when pk_octets is not NULL, as bbs_ctx_add_public_keys_octets does (pk_affine and
+ * is_identity are then ignored).  path 0: the host functions, one key at a time; path 1: the device stage, whatever the key
+ * count, read back from the device (with a workspace of ~15 KB per key on BLS12-381, released before the call returns).  entries_out: n x bbs_selftest_key_entry_bytes(curve) bytes; status_out: n; pk_affine_out
+ * (octet form only, may be NULL): the decoded records.  Needs the generators; does not touch the context's key set. */
+int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, const int8_t* is_identity,
+                             const uint8_t* pk_octets, int path, uint8_t* entries_out, int8_t* status_out,
+                             uint8_t* pk_affine_out);
+size_t bbs_selftest_key_entry_bytes(int curve);
 /* GPU self-test: one Fp12 operation (12 Fp values a, b, canonical LE, tower order) computed by the
  * one-lane code and by the six-lane wavefront-cooperative code; the caller compares the outputs.
  * op: 0 mul, 1..3 Frobenius^k, 4 inverse, 5 conjugate, 6 line multiplication, 7 final

@@ -287,14 +287,13 @@ inline std::vector<Result<bool>> proof_verify_batch(const PublicKey& pk, const s
 // ---- many issuers: one PublicKey per item (the reference's per-call key, src/verify.rs:18-50, src/proof_verify.rs:19-61) ----
 namespace detail {
 // one context per (curve, message count, device) holding a KEY SET (bbs_ctx_set_public_keys) instead of one key: the
-// fixed-base tables are built once for every issuer.  The set is the distinct keys of the last call; a call that brings a
-// key the set lacks registers the union (keys are never dropped while the context lives).
+// fixed-base tables are built once for every issuer.  The set is the distinct keys of all calls so far; a call that brings
+// keys the set lacks APPENDS them (bbs_ctx_add_public_keys): every key is prepared once and keeps its index, keys are never
+// dropped while the context lives.
 struct KeyedCtx {
     CtxPtr ctx;
     std::mutex mu;                                    // one call at a time per context (the C ABI's rule)
     std::map<std::string, uint32_t> index;            // key record (+ identity flag) -> position in the set
-    Bytes records;                                    // the set, n x 4 fp_bytes
-    std::vector<int8_t> identity;
 };
 inline std::shared_ptr<KeyedCtx> keyed_context(Curve c, size_t L, int device = 0) {
     static std::mutex mu;
@@ -315,33 +314,40 @@ inline std::shared_ptr<KeyedCtx> keyed_context(Curve c, size_t L, int device = 0
     cache[k] = kc;
     return kc;
 }
-// (under kc.mu) the key index of every item; registers the keys the set lacks.  A key bbs_ctx_set_public_key would
-// refuse throws, as the single-key functions do.
+// (under kc.mu) the key index of every item; appends the keys the set lacks.  A key bbs_ctx_set_public_key would
+// refuse throws, as the single-key functions do (and the set is cleared: a refused key must not keep an index).
 inline std::vector<uint32_t> key_indexes(KeyedCtx& kc, Curve c, const std::vector<const PublicKey*>& pks) {
     const size_t rec = 4 * bbs_fp_bytes((int)c);
     std::vector<uint32_t> ki(pks.size());
-    const size_t before = kc.identity.size();
+    const uint32_t before = (uint32_t)bbs_ctx_public_key_count(kc.ctx.get());
+    Bytes records;                                    // the keys this call brings, n_new x 4 fp_bytes
+    std::vector<int8_t> identity;
+    for (const PublicKey* pk : pks)                   // (before anything is entered into the index)
+        if (pk->curve != c || (!pk->identity && pk->pk.size() != rec)) throw std::runtime_error("public key of another curve or size");
     for (size_t i = 0; i < pks.size(); i++) {
         const PublicKey& pk = *pks[i];
-        if (pk.curve != c || (!pk.identity && pk.pk.size() != rec)) throw std::runtime_error("public key of another curve or size");
         std::string id(1, pk.identity ? 'i' : 'p');
         if (!pk.identity) id.append(pk.pk.begin(), pk.pk.end());
         auto it = kc.index.find(id);
         if (it == kc.index.end()) {
-            it = kc.index.emplace(id, (uint32_t)kc.identity.size()).first;
-            if (pk.identity) kc.records.insert(kc.records.end(), rec, 0);
-            else kc.records.insert(kc.records.end(), pk.pk.begin(), pk.pk.end());
-            kc.identity.push_back(pk.identity ? 1 : 0);
+            it = kc.index.emplace(id, before + (uint32_t)identity.size()).first;
+            if (pk.identity) records.insert(records.end(), rec, 0);
+            else records.insert(records.end(), pk.pk.begin(), pk.pk.end());
+            identity.push_back(pk.identity ? 1 : 0);
         }
         ki[i] = it->second;
     }
-    if (kc.identity.size() != before) {
-        std::vector<int8_t> st(kc.identity.size());
-        const int rc = bbs_ctx_set_public_keys(kc.ctx.get(), kc.identity.size(), kc.records.data(), kc.identity.data(), st.data());
-        if (rc != BBS_OK) { kc.index.clear(); kc.records.clear(); kc.identity.clear(); check(rc, "bbs_ctx_set_public_keys"); }
-        for (int8_t x : st)
-            if (x != 1) { kc.index.clear(); kc.records.clear(); kc.identity.clear(); bbs_ctx_set_public_keys(kc.ctx.get(), 0, nullptr, nullptr, nullptr);
-                          check(BBS_E_PUBLIC_KEY, "bbs_ctx_set_public_keys"); }
+    if (!identity.empty()) {
+        std::vector<int8_t> st(identity.size());
+        uint32_t first = 0;
+        int rc = bbs_ctx_add_public_keys(kc.ctx.get(), identity.size(), records.data(), identity.data(), st.data(), &first);
+        if (rc == BBS_OK && first != before) rc = BBS_E_STATE;          // (the set was changed behind this wrapper)
+        for (int8_t x : st) if (rc == BBS_OK && x != 1) rc = BBS_E_PUBLIC_KEY;
+        if (rc != BBS_OK) {
+            kc.index.clear();
+            bbs_ctx_set_public_keys(kc.ctx.get(), 0, nullptr, nullptr, nullptr);
+            check(rc, "bbs_ctx_add_public_keys");
+        }
     }
     return ki;
 }

@@ -15,12 +15,27 @@ Legs (items/s, host-inclusive as bench.py's value):
   vf_*          the same keyed legs for core_verify (and the single-key reference)
   reg_ms        bbs_ctx_set_public_keys for 64 and 4096 keys (the 4096 are the 64 keys repeated: registration cost is per entry)
 The workload is generated untimed by 64 single-key contexts at 8-bit windows (sign, proof_gen of their share).
+
+    python tools/keyed_bench.py --reg-only [--lib PATH]
+
+runs only the registration legs, with 1, 16, 64, 256, 1024 and 4096 keys (64 distinct keys repeated), the C call alone (the
+records are packed before the clock starts), median of 5 with min and max, in milliseconds:
+  set           bbs_ctx_set_public_keys of n keys; also of 4097 and 4112 keys -- the only way to add 1 or 16 keys to a
+                4096-key set without bbs_ctx_add_public_keys
+  add           bbs_ctx_add_public_keys of n keys onto a 4096-key set (rebuilt, untimed, before every repetition)
+  add_octets    bbs_ctx_add_public_keys_octets of the same keys onto a 4096-key set
+  stage         bbs_selftest_key_entries path 1 of n keys: the device stage whatever n is, with the read-back of the n entries
+                (29 KB each) -- what preparing n keys costs on the device (no call of the library uses the stage yet: this leg
+                against `set` is the comparison that decides whether, and from how many keys, it should)
+--lib PATH times another build of the library (an older one lacks the add exports: its line has the set legs only).
 """
 import os
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 import argparse
+import ctypes
 import json
+import statistics
 import sys
 import time
 
@@ -90,14 +105,93 @@ def packed(eng, fn, n, args, keep, key_index=None):
     return submit
 
 
+REG_SIZES = (1, 16, 64, 256, 1024, 4096)
+REG_BASE = 4096                                     # the set the add legs append to
+REG_NEW_EXPORTS = ("bbs_ctx_add_public_keys", "bbs_ctx_add_public_keys_octets", "bbs_ctx_public_key_count", "bbs_selftest_key_entries",
+                   "bbs_selftest_key_entry_bytes")
+
+
+def reg_only(lib_path):
+    """The registration legs (module docstring): one JSON line."""
+    if lib_path:
+        os.environ["BBS_SIGN_AMD_LIB"] = os.path.abspath(lib_path)
+        os.environ["BBS_SIGN_AMD_LIB_OPTIONAL"] = ",".join(REG_NEW_EXPORTS)
+    import parity_cases as pc
+    from bbs_sign_amd import Engine, _lib
+    from oracle import bbs
+    suite = bbs.SUITES["bls12_381"]
+    c = suite.curve
+    gens = pc.gens_for(suite, 5)
+    eng = Engine("bls12_381", device=0, window_bits=8)
+    eng.set_generators(gens, suite.api_id)
+    has_add = hasattr(eng.lib, "bbs_ctx_add_public_keys")
+    fpb = eng.fpb
+    distinct, q = [], bbs.sk_to_pk(suite, 0x1234567)
+    for _ in range(64):
+        distinct.append(q)
+        q = c.g2_add(q, c.g2)
+    recs = [b"".join(int(v).to_bytes(fpb, "little") for v in (k[0][0], k[0][1], k[1][0], k[1][1])) for k in distinct]
+    octs = [bbs.g2_compress(c, k) for k in distinct]
+    nmax = REG_BASE + 16
+    rec_buf = np.frombuffer(b"".join(recs[k % 64] for k in range(nmax)), dtype=np.uint8).copy()
+    oct_buf = np.frombuffer(b"".join(octs[k % 64] for k in range(nmax)), dtype=np.uint8).copy()
+    ident = np.zeros(nmax, dtype=np.int8)
+    st = np.zeros(nmax, dtype=np.int8)
+    first = ctypes.c_uint32(0)
+    u8, i8 = _lib.c_u8p, _lib.c_i8p
+
+    def timed(call, n, before=None):
+        ms = []
+        for _ in range(5):
+            if before:
+                before()
+            st[:] = 0
+            t0 = time.perf_counter()
+            rc = call(n)
+            ms.append((time.perf_counter() - t0) * 1e3)
+            assert rc == 0 and (st[:n] == 1).all(), rc
+        return [round(statistics.median(ms), 3), round(min(ms), 3), round(max(ms), 3)]
+
+    set_n = lambda n: eng.lib.bbs_ctx_set_public_keys(eng.h, n, rec_buf.ctypes.data_as(u8), ident.ctypes.data_as(i8), st.ctypes.data_as(i8))
+    add_n = lambda n: eng.lib.bbs_ctx_add_public_keys(eng.h, n, rec_buf.ctypes.data_as(u8), ident.ctypes.data_as(i8), st.ctypes.data_as(i8),
+                                                      ctypes.byref(first))
+    add_o = lambda n: eng.lib.bbs_ctx_add_public_keys_octets(eng.h, n, oct_buf.ctypes.data_as(u8), st.ctypes.data_as(i8), None, None,
+                                                             ctypes.byref(first))
+
+    def base_set():
+        assert set_n(REG_BASE) == 0
+
+    eb = int(eng.lib.bbs_selftest_key_entry_bytes(0)) if has_add else 0
+    ent = np.zeros(max(REG_SIZES) * eb + 1, dtype=np.uint8)
+    stage_n = lambda n: eng.lib.bbs_selftest_key_entries(eng.h, n, rec_buf.ctypes.data_as(u8), ident.ctypes.data_as(i8), None, 1,
+                                                         ent.ctypes.data_as(u8), st.ctypes.data_as(i8), None)
+
+    out = {"metric": "key_registration_ms_median_min_max", "curve": "bls12_381", "lib": lib_path or "product", "has_add": has_add,
+           "set": {}, "add": {}, "add_octets": {}, "stage": {}}
+    set_n(64)                                           # (first call: the kernel's code object, the pools)
+    for n in REG_SIZES + (REG_BASE + 1, REG_BASE + 16):
+        out["set"][str(n)] = timed(set_n, n)
+    if has_add:
+        for n in REG_SIZES:
+            out["add"][str(n)] = timed(add_n, n, base_set)
+            assert first.value == REG_BASE
+            out["add_octets"][str(n)] = timed(add_o, n, base_set)
+            out["stage"][str(n)] = timed(stage_n, n)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reg-only", action="store_true", help="only the registration legs (see the module docstring)")
+    ap.add_argument("--lib", default="", help="with --reg-only: time this build of the library instead of the product library")
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--keys", type=int, default=64)
     ap.add_argument("--skip-verify", action="store_true")
     ap.add_argument("--legs", default="", help="comma-separated subset of pv_a_single, pv_b_k1, pv_d_k64_mix, ... (profiling runs)")
     a = ap.parse_args()
+    if a.reg_only:
+        return reg_only(a.lib)
     from bbs_sign_amd import Engine
     K = a.keys
     out = {"metric": "keyed_verify_items_per_s", "curve": "bls12_381", "batch": N, "messages": L, "disclosed": R,
