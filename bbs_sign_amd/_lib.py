@@ -178,6 +178,8 @@ SIGNATURES = {
     "bbs_hash_to_g1": (ci, [ci, c_u8p, sz, c_u8p, sz, c_u8p]),
     "bbs_scalar_from_okm": (ci, [ci, c_u8p, c_u8p]),
     "bbs_key_gen": (ci, [ci, c_u8p, sz, c_u8p, sz, c_u8p, sz, c_u8p]),
+    "bbs_key_gen_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, sz, c_u8p, c_u8p, c_u8p, c_i8p]),
+    "bbs_sk_to_pk_batch": (ci, [vp, sz, c_u8p, c_u8p, c_i8p, c_u8p, c_i8p]),
     "bbs_signature_to_octets": (ci, [ci, c_u8p, c_u8p]),
     "bbs_signature_from_octets": (ci, [ci, c_u8p, c_u8p]),
     "bbs_proof_to_octets": (ci, [ci, c_u8p, c_u8p, sz, c_u8p]),

@@ -136,6 +136,43 @@ class SecretKey:
         return eng.core_sign(header, msg_to_scalars(eng, self.curve, messages))
 
 
+def key_gen_batch(curve: str, key_materials: Sequence[bytes], key_infos: Sequence[bytes], key_dst: bytes,
+                  lib_path: Optional[str] = None, device: int = 0) -> list:
+    """SecretKey::key_gen followed by sk_to_pk (src/key_gen.rs:46-90) for many keys in ONE device call (bbs_key_gen_batch).
+    Entry k of the result is ``(SecretKey, PublicKey)``, or the exception SecretKey.key_gen would raise for item k (returned,
+    not raised: the other items stand): a BbsError with the same ``.variant``."""
+    eng = _engine(curve, 0, device=device, lib_path=lib_path)
+    sks, pks, _, st = eng.key_gen_batch(list(key_materials), list(key_infos), key_dst)
+    out = []
+    for k in range(len(sks)):
+        rc = int(st[k])
+        if rc == 1:
+            out.append((SecretKey(curve, sks[k], lib_path, device), PublicKey(curve, pks[k], lib_path, device)))
+        elif rc in KEYGEN_ERRORS:
+            e = BbsError(rc)
+            e.variant = KEYGEN_ERRORS[rc]
+            out.append(e)
+        else:
+            out.append(BbsRuntimeError(rc, "bbs_key_gen"))
+    return out
+
+
+def sk_to_pk_batch(secret_keys: Sequence[SecretKey]) -> List[PublicKey]:
+    """SecretKey::sk_to_pk (src/key_gen.rs:83-90) for many keys in one device call per (curve, library, device)."""
+    out: List[Optional[PublicKey]] = [None] * len(secret_keys)
+    groups: Dict[tuple, List[int]] = {}
+    for k, s in enumerate(secret_keys):
+        groups.setdefault((s.curve, s.lib_path, s.device), []).append(k)
+    for (curve, lib_path, device), idx in groups.items():
+        eng = _engine(curve, 0, device=device, lib_path=lib_path)
+        pks, _, st = eng.sk_to_pk_batch([secret_keys[k].sk for k in idx])
+        for k, pk, rc in zip(idx, pks, st):
+            if rc != 1:
+                raise BbsRuntimeError(-100, "bbs_sk_to_pk_batch (secret key %d is not below the group order)" % k)
+            out[k] = PublicKey(curve, pk, lib_path, device)
+    return out
+
+
 def hash_to_g1(curve: str, msg: bytes, dst: bytes, lib_path: Optional[str] = None):
     """The suite's hash-to-G1 (src/utils/interface_utilities.rs:24-44), host side of the library."""
     lib = _lib.load_library(lib_path)

@@ -917,6 +917,17 @@ int bbs_key_gen(int curve, const uint8_t* key_material, size_t km_len, const uin
     for (int i = 0; i < 8; i++) put_le32(sk32_out + 4 * i, w[i]);
     return BBS_OK;
 }
+// key_gen and sk_to_pk (src/key_gen.rs:46-90) for n items on the device (op_kg.hpp)
+int bbs_key_gen_batch(bbs_ctx* ctx, size_t n, const uint8_t* key_material, const uint64_t* km_off, const uint8_t* key_info, const uint64_t* ki_off,
+                      const uint8_t* key_dst, size_t key_dst_len, uint8_t* sk32_out, uint8_t* pk_affine_out, uint8_t* pk_octets_out, int8_t* status) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return key_gen_batch(c, n, key_material, km_off, key_info, ki_off, key_dst, key_dst_len, sk32_out,
+                                                               pk_affine_out, pk_octets_out, status); });
+}
+int bbs_sk_to_pk_batch(bbs_ctx* ctx, size_t n, const uint8_t* sk32, uint8_t* pk_affine_out, int8_t* is_identity_out, uint8_t* pk_octets_out, int8_t* status) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return sk_to_pk_batch(c, n, sk32, pk_affine_out, is_identity_out, pk_octets_out, status); });
+}
 
 // ---- wire codec (host) ---------------------------------------------------------------------------
 }  // extern "C"

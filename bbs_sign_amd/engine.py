@@ -770,6 +770,63 @@ class Engine:
         b = out.tobytes()
         return [int.from_bytes(b[32 * i:32 * (i + 1)], "little") for i in range(n)]
 
+    def _pk_dec(self, b: bytes):
+        f = [int.from_bytes(b[i * self.fpb:(i + 1) * self.fpb], "little") for i in range(4)]
+        return ((f[0], f[1]), (f[2], f[3]))
+
+    def key_gen_batch(self, key_materials: Sequence[bytes], key_infos: Sequence[bytes], key_dst: bytes, public_keys: bool = True):
+        """bbs_key_gen_batch: key_gen and sk_to_pk (key_gen.rs:46-90) for n items on the device.  Returns ``(sks, pks, octets,
+        statuses)``: sks[i] the secret key, pks[i] = ((x0, x1), (y0, y1)), octets[i] the compressed public key; all three None
+        for a refused item, whose status is the code bbs_key_gen returns for it.  ``public_keys=False`` derives the secret
+        keys only (pks and octets are then all None).  Needs no generators and no key, and touches neither."""
+        n = len(key_materials)
+        if len(key_infos) != n:
+            raise ValueError("key_infos: %d items, expected %d" % (len(key_infos), n))
+        kb, ko = _ragged_bytes(key_materials)
+        ib, io = _ragged_bytes(key_infos)
+        d = _bytes_arr(key_dst)
+        rec, ob = 4 * self.fpb, 2 * self.fpb
+        sk = np.zeros(max(n, 1) * 32, dtype=np.uint8)
+        pk = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        oc = np.zeros(max(n, 1) * ob, dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        try:
+            self._chk(self.lib.bbs_key_gen_batch(self.h, n, _u8(kb), _u64(ko), _u8(ib), _u64(io), _u8(d), len(key_dst), _u8(sk),
+                                                 _u8(pk) if public_keys else None, _u8(oc) if public_keys else None,
+                                                 st.ctypes.data_as(_lib.c_i8p)), "bbs_key_gen_batch")
+            s, p, o = sk.tobytes(), pk.tobytes(), oc.tobytes()
+        finally:
+            kb[:] = 0                                   # (the flattened copy of the key material made here)
+            sk[:] = 0
+        ok = [st[i] == 1 for i in range(n)]
+        sks = [int.from_bytes(s[32 * i:32 * (i + 1)], "little") if ok[i] else None for i in range(n)]
+        pks = [self._pk_dec(p[rec * i:rec * (i + 1)]) if ok[i] and public_keys else None for i in range(n)]
+        octets = [o[ob * i:ob * (i + 1)] if ok[i] and public_keys else None for i in range(n)]
+        return sks, pks, octets, st[:n]
+
+    def sk_to_pk_batch(self, sks: Sequence[int]):
+        """bbs_sk_to_pk_batch: ``(pks, octets, statuses)`` for n secret keys; pks[i] is None for sk = 0 (the identity key, whose
+        octets are the identity's encoding) and for a refused scalar (>= r: status -40, octets None)."""
+        n = len(sks)
+        for s in sks:
+            if not 0 <= int(s) < 1 << 256:
+                raise ValueError("secret key out of range")
+        buf = _bytes_arr(b"".join(self._fr(s) for s in sks))
+        rec, ob = 4 * self.fpb, 2 * self.fpb
+        pk = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        oc = np.zeros(max(n, 1) * ob, dtype=np.uint8)
+        ident = np.zeros(max(n, 1), dtype=np.int8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        try:
+            self._chk(self.lib.bbs_sk_to_pk_batch(self.h, n, _u8(buf), _u8(pk), ident.ctypes.data_as(_lib.c_i8p), _u8(oc),
+                                                  st.ctypes.data_as(_lib.c_i8p)), "bbs_sk_to_pk_batch")
+        finally:
+            buf[:] = 0
+        p, o = pk.tobytes(), oc.tobytes()
+        pks = [self._pk_dec(p[rec * i:rec * (i + 1)]) if st[i] == 1 and not ident[i] else None for i in range(n)]
+        octets = [o[ob * i:ob * (i + 1)] if st[i] == 1 else None for i in range(n)]
+        return pks, octets, st[:n]
+
     def g1_msm_batch(self, fixed_scalars, var_points, var_scalars):
         n = len(fixed_scalars)
         nf = len(fixed_scalars[0]) if n else 0

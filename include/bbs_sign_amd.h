@@ -670,6 +670,28 @@ int bbs_scalar_from_okm(int curve, const uint8_t* okm48, uint8_t* scalar_out);
 /* SecretKey::key_gen (src/key_gen.rs:46-81): returns 0 or the KeyGenError code. */
 int bbs_key_gen(int curve, const uint8_t* key_material, size_t key_material_len, const uint8_t* key_info,
                 size_t key_info_len, const uint8_t* key_dst, size_t key_dst_len, uint8_t* sk32_out);
+/* key_gen and sk_to_pk (src/key_gen.rs:46-90) for n keys in one call ON THE DEVICE, one lane per key.  The context gives the
+ * curve, the device and the stream only: no generators and no key are needed, and its key, key set and tables are not
+ * touched.  key_material / key_info: ragged bytes with n + 1 byte offsets each (item i = bytes[off[i] .. off[i + 1]); the
+ * offsets need not start at zero); key_info and ki_off may both be NULL when every key_info is empty; one key_dst for the call.
+ * status[i]: 1, or what the one-key call returns for item i, decided in its order -- BBS_ST_INVALID_KEY_MATERIAL_LENGTH,
+ * BBS_ST_INVALID_KEY_INFO_LENGTH, BBS_ST_PANIC_DST_TOO_LONG (a key_dst of more than 255 bytes: every item that passed the two
+ * length checks), BBS_ST_INVALID_SECRET_KEY.  sk32_out: n x 32 bytes LE; pk_affine_out: n records x.c0 || x.c1 || y.c0 ||
+ * y.c1 as bbs_ctx_get_public_key gives them; pk_octets_out: n strings as bbs_public_key_to_octets gives them; either or
+ * both may be NULL (both NULL: only the secret keys are derived).  Every output of a refused item is zero.  Synchronous.
+ * n = 0 is BBS_OK; BBS_E_ARG for a NULL key_material, km_off, sk32_out or status with n > 0; BBS_E_STATE, and zeroed outputs,
+ * if an item was left undecided (fail closed).  Device and staging memory that held key material or secret keys is cleared
+ * before it is released; the input is const, clearing the caller's copy is the caller's business.  Nothing is claimed about
+ * timing side channels. */
+int bbs_key_gen_batch(bbs_ctx* ctx, size_t n, const uint8_t* key_material, const uint64_t* km_off,
+                      const uint8_t* key_info, const uint64_t* ki_off, const uint8_t* key_dst, size_t key_dst_len,
+                      uint8_t* sk32_out, uint8_t* pk_affine_out, uint8_t* pk_octets_out, int8_t* status);
+/* sk_to_pk for n secret keys (32 B LE each) by the same device stage.  status[i]: 1, or BBS_ST_NONCANONICAL for a scalar >= r
+ * (zero outputs).  sk = 0 gives the identity key (PublicKey::default()): is_identity_out[i] = 1, a zero record and the
+ * identity's compressed encoding.  pk_affine_out, is_identity_out, pk_octets_out may be NULL, but not both key outputs.
+ * BBS_E_ARG for a NULL sk32 or status with n > 0. */
+int bbs_sk_to_pk_batch(bbs_ctx* ctx, size_t n, const uint8_t* sk32, uint8_t* pk_affine_out, int8_t* is_identity_out,
+                       uint8_t* pk_octets_out, int8_t* status);
 
 /* ------------------------------------------------------------------------------------------
  * Wire codec (host side).  Octet strings as in the reference's vectors (src/tests/test_vector.rs:

@@ -113,6 +113,25 @@ inline Bytes msg_to_scalars(bbs_ctx* ctx, Curve c, const std::vector<Bytes>& msg
 }
 inline const uint8_t* ptr(const Bytes& b) { static const uint8_t z = 0; return b.empty() ? &z : b.data(); }
 
+// one context per (curve, device) without generators or key: what the batched key generation needs
+inline CtxPtr bare_context(Curve c, int device = 0) {
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, CtxPtr> cache;
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cache.find({(int)c, device});
+    if (it != cache.end()) return it->second;
+    bbs_ctx* raw = nullptr;
+    check(bbs_ctx_create((int)c, device, &raw), "bbs_ctx_create");
+    CtxPtr ctx(raw, CtxDeleter());
+    cache[{(int)c, device}] = ctx;
+    return ctx;
+}
+// zeroes that the compiler may not drop (key_material.zeroize(), key_gen.rs:73)
+inline void zeroize(uint8_t* p, size_t n) {
+    volatile uint8_t* v = p;
+    for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
 }  // namespace detail
 
 class PublicKey {                                     // src/key_gen.rs:12-15
@@ -159,6 +178,68 @@ public:
         detail::check(bbs_ctx_get_public_key(ctx.get(), p.pk.data(), &inf), "bbs_ctx_get_public_key");
         p.identity = inf != 0;
         return p;
+    }
+    // key_gen followed by sk_to_pk for many keys in ONE device call (bbs_key_gen_batch): item k is Ok((sk, pk)) or the Err
+    // variant key_gen returns for it.  Like the reference's key_gen (key_gen.rs:47, :73) it takes the key material by mutable
+    // reference and zeroes it -- every item's, in place, whatever the item's result
+    static std::vector<Result<std::pair<SecretKey, PublicKey>>> key_gen_batch(Curve c, std::vector<Bytes>& key_materials,
+                                                                              const std::vector<Bytes>& key_infos, const Bytes& key_dst,
+                                                                              int device = 0) {
+        const size_t n = key_materials.size(), fpb = bbs_fp_bytes((int)c);
+        if (key_infos.size() != n) throw std::invalid_argument("key_gen_batch: one key_info per key_material");
+        Bytes km, ki;
+        std::vector<uint64_t> kmo{0}, kio{0};
+        for (size_t k = 0; k < n; k++) {
+            km.insert(km.end(), key_materials[k].begin(), key_materials[k].end()); kmo.push_back(km.size());
+            ki.insert(ki.end(), key_infos[k].begin(), key_infos[k].end()); kio.push_back(ki.size());
+            detail::zeroize(key_materials[k].data(), key_materials[k].size());
+        }
+        Bytes sk(32 * n + 1), pk(4 * fpb * n + 1);
+        std::vector<int8_t> st(n + 1);
+        auto ctx = detail::bare_context(c, device);
+        const int rc = bbs_key_gen_batch(ctx.get(), n, detail::ptr(km), kmo.data(), detail::ptr(ki), kio.data(), detail::ptr(key_dst), key_dst.size(),
+                                         sk.data(), pk.data(), nullptr, st.data());
+        detail::zeroize(km.data(), km.size());
+        std::vector<Result<std::pair<SecretKey, PublicKey>>> out;
+        int thrown = rc;                               // what key_gen throws on: a batch-level failure, a key_dst of more than 255 bytes
+        for (size_t k = 0; k < n && !thrown; k++) {
+            if (st[k] == 1) {
+                std::pair<SecretKey, PublicKey> kp;
+                kp.first.curve = kp.second.curve = c;
+                std::memcpy(kp.first.sk.data(), sk.data() + 32 * k, 32);
+                kp.second.pk.assign(pk.begin() + 4 * fpb * k, pk.begin() + 4 * fpb * (k + 1));
+                out.push_back(Result<std::pair<SecretKey, PublicKey>>::ok(std::move(kp)));
+            } else if (st[k] == BBS_ST_INVALID_KEY_MATERIAL_LENGTH || st[k] == BBS_ST_INVALID_KEY_INFO_LENGTH || st[k] == BBS_ST_INVALID_SECRET_KEY) {
+                out.push_back(Result<std::pair<SecretKey, PublicKey>>::err(st[k]));
+            } else thrown = st[k];
+        }
+        detail::zeroize(sk.data(), sk.size());
+        detail::check(thrown, "bbs_key_gen_batch");
+        return out;
+    }
+    // sk_to_pk for many keys of one curve in one device call (bbs_sk_to_pk_batch)
+    static std::vector<PublicKey> sk_to_pk_batch(const std::vector<SecretKey>& sks, int device = 0) {
+        std::vector<PublicKey> out(sks.size());
+        if (sks.empty()) return out;
+        const Curve c = sks[0].curve;
+        const size_t n = sks.size(), fpb = bbs_fp_bytes((int)c);
+        Bytes sk(32 * n), pk(4 * fpb * n);
+        std::vector<int8_t> st(n), inf(n);
+        for (size_t k = 0; k < n; k++) {
+            if (sks[k].curve != c) throw std::invalid_argument("sk_to_pk_batch: keys of one curve per call");
+            std::memcpy(sk.data() + 32 * k, sks[k].sk.data(), 32);
+        }
+        auto ctx = detail::bare_context(c, device);
+        const int rc = bbs_sk_to_pk_batch(ctx.get(), n, sk.data(), pk.data(), inf.data(), nullptr, st.data());
+        detail::zeroize(sk.data(), sk.size());
+        detail::check(rc, "bbs_sk_to_pk_batch");
+        for (size_t k = 0; k < n; k++) {
+            if (st[k] != 1) throw std::runtime_error("bbs_sk_to_pk_batch: secret key " + std::to_string(k) + ": status " + std::to_string((int)st[k]));
+            out[k].curve = c;
+            out[k].pk.assign(pk.begin() + 4 * fpb * k, pk.begin() + 4 * fpb * (k + 1));
+            out[k].identity = inf[k] != 0;
+        }
+        return out;
     }
     // SecretKey::sign (src/sign.rs:32-60)
     Result<Signature> sign(const std::vector<Bytes>& msgs, const Bytes& header) const {
