@@ -146,6 +146,7 @@ SIGNATURES = {
     "bbs_pool_job_wait": (ci, [vp]),
     "bbs_pool_job_free": (None, [vp]),
     "bbs_runtime_queue_budget": (ci, [ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(sz)]),
+    "bbs_runtime_queue_report": (ci, [ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "bbs_device_free_bytes": (sz, [ci]),
     "bbs_ctx_table_bytes": (sz, [vp]),
     "bbs_issuer_set_budget": (ci, [vp, sz, sz]),

@@ -12,7 +12,27 @@
 // the library at 1.8 KB the scratch budget allows 25 hardware queues (runtime.hpp queue_budget; DESIGN.md 5 rule 6) --
 // 1.48 / 1.53 / 1.55 / 1.53 M proof_verify/s at 14 / 18 / 20 / 24 (profiles/r05_a_ab_split_msm_layouts.log).  Takes effect only if
 // this library is loaded before the process makes its first HIP call; an explicit setting in the environment wins.
-__attribute__((constructor)) static void bbs_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "20", 0); }
+// What was found is recorded first (runtime.hpp load_state): whether the variable was there, and whether the runtime had already
+// started -- the HSA runtime underneath HIP answers "not initialised" to a query until the process's first HIP call.  A process
+// in which it had (any torch user) keeps the pool it started with, whatever is written here afterwards; there the job streams
+// get hardware queues of their own instead (runtime.hpp stream_create, queue_policy.hpp).
+#include <dlfcn.h>
+__attribute__((constructor)) static void bbs_default_hw_queues() {
+    rt::LoadState& ls = rt::load_state();
+    const char* v = getenv("GPU_MAX_HW_QUEUES");
+    ls.variable_was_set = v != nullptr;
+    ls.value_found = v ? atoi(v) : 0;
+    ls.runtime_at_load = qpolicy::RT_UNKNOWN;
+    using get_info_t = int (*)(int, void*);              // hsa_status_t hsa_system_get_info(hsa_system_info_t, void*)
+    if (auto get_info = reinterpret_cast<get_info_t>(dlsym(RTLD_DEFAULT, "hsa_system_get_info"))) {
+        uint16_t major = 0;
+        const int st = get_info(0 /* HSA_SYSTEM_INFO_VERSION_MAJOR */, &major);
+        if (st == 0) ls.runtime_at_load = qpolicy::RT_STARTED;
+        else if (st == 0x100B /* HSA_STATUS_ERROR_NOT_INITIALIZED */) ls.runtime_at_load = qpolicy::RT_NOT_STARTED;
+    }
+    ls.recorded = true;
+    setenv("GPU_MAX_HW_QUEUES", "20", 0);
+}
 // what the process environment says now (0 = unset): a service can log it at start-up and, when it reads 4 or was set
 // after the first HIP call, prefer larger batches (two 16384-item batches in flight fill the chip: DESIGN.md 6a)
 extern "C" __attribute__((visibility("default"))) int bbs_runtime_hw_queues(void) {
@@ -20,13 +40,24 @@ extern "C" __attribute__((visibility("default"))) int bbs_runtime_hw_queues(void
     return v ? atoi(v) : 0;
 }
 
-// Job streams with hardware queues of their own (runtime.hpp stream_create): k = 0 off, k > 0 at most k per device (at most
-// 16); takes effect for streams created afterwards (streams are pooled: call it before the first context is created).
+// Job streams with hardware queues of their own (runtime.hpp stream_create): k = 0 off -- the library then never creates one --
+// k > 0 at most k per device (at most 16); never called and no BBS_DEDICATED_QUEUES: the library decides (queue_policy.hpp).
+// Takes effect for streams created afterwards (streams are pooled: call it before the first context is created).
 extern "C" __attribute__((visibility("default"))) int bbs_runtime_set_dedicated_queues(int k) {
-    if (k < 0 || k > 16) return BBS_E_ARG;
-#ifndef BBS_HOST_TWIN
-    rt::dedicated_queues().store(k);      // a wish: runtime.hpp stream_create grants min(k, what the scratch budget leaves beside the pool)
-#endif
+    if (k < 0 || k > qpolicy::MAX_DEDICATED) return BBS_E_ARG;
+    rt::dedicated_queues().store(k);      // a wish: runtime.hpp stream_create grants what the scratch budget leaves beside the queues in use
+    return BBS_OK;
+}
+// What was decided and granted on a device: the setting (-1 the library decides, 0 off, k asked for), the pool the runtime most
+// probably uses (runtime.hpp load_state), and the streams of either kind made so far.  Any pointer may be null.
+extern "C" __attribute__((visibility("default"))) int bbs_runtime_queue_report(int device_id, int* mode, int* effective_pool, int* dedicated_made, int* pooled_made) {
+    if (device_id < 0 || device_id >= rt::device_count()) return BBS_E_NO_DEVICE;
+    int d = 0, p = 0;
+    rt::queue_counts(device_id, &d, &p);
+    if (mode) *mode = rt::dedicated_setting();
+    if (effective_pool) *effective_pool = rt::effective_pool();
+    if (dedicated_made) *dedicated_made = d;
+    if (pooled_made) *pooled_made = p;
     return BBS_OK;
 }
 // The hardware-queue budget of a device (runtime.hpp): scratch bytes per lane of the library's largest kernel frame, the

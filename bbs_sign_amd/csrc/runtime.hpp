@@ -29,6 +29,7 @@
 #include "host_g2.hpp"
 #include "codec_dev.hpp"
 #include "keyed.hpp"
+#include "queue_policy.hpp"
 
 using namespace bbs;
 
@@ -36,6 +37,29 @@ using namespace bbs;
 // runtime layer
 // =============================================================================================
 namespace rt {
+// What the library found when it was loaded (capi.hip's constructor records it before it writes its own GPU_MAX_HW_QUEUES): was
+// the variable there, and had the HIP runtime -- which reads it once, at its own initialisation -- already started.  From the
+// two, the pool the runtime most probably uses (queue_policy.hpp load_pool); never recorded = the runtime's default.
+struct LoadState { bool recorded = false, variable_was_set = false; int value_found = 0, runtime_at_load = qpolicy::RT_UNKNOWN; };
+inline LoadState& load_state() { static LoadState s; return s; }
+inline int effective_pool() {
+    const LoadState& s = load_state();
+    return s.recorded ? qpolicy::load_pool(s.variable_was_set, s.value_found, s.runtime_at_load) : qpolicy::RUNTIME_POOL;
+}
+// The dedicated-queue setting of the process: -2 not decided yet (BBS_DEDICATED_QUEUES is read when it is first needed),
+// qpolicy::AUTO (-1) nothing was asked for, 0 off, k > 0 up to k job streams per device
+inline std::atomic<int>& dedicated_queues() { static std::atomic<int> v{-2}; return v; }
+inline int dedicated_setting() {
+    int want = dedicated_queues().load();
+    if (want < qpolicy::AUTO) {
+        const char* e = getenv("BBS_DEDICATED_QUEUES");
+        want = e && *e ? atoi(e) : qpolicy::AUTO;
+        if (e && *e) { if (want == 1) want = 12; if (want < 0) want = 0; if (want > qpolicy::MAX_DEDICATED) want = qpolicy::MAX_DEDICATED; }
+        int undecided = -2;
+        if (!dedicated_queues().compare_exchange_strong(undecided, want)) want = undecided;      // bbs_runtime_set_dedicated_queues came first
+    }
+    return want;
+}
 #ifdef BBS_HOST_TWIN
 struct Stream {};
 inline int set_device(int) { return 0; }
@@ -44,6 +68,7 @@ inline int stream_create(Stream*) { return 0; }
 inline void stream_destroy(Stream&) {}
 struct QueueBudget { int total = 0, pool = 0, dedicated_cap = 0; size_t scratch = 0; };
 inline QueueBudget queue_budget(int) { return QueueBudget{}; }
+inline void queue_counts(int, int* dedicated, int* pooled) { *dedicated = 0; *pooled = 0; }
 inline size_t size_class(size_t b) { return b; }
 inline int dmalloc(void** p, size_t b) { *p = std::calloc(b ? b : 1, 1); return *p ? 0 : -1; }
 inline void dfree(void* p, size_t, int) { std::free(p); }
@@ -122,6 +147,7 @@ struct Pools {
     std::map<int, int> dedicated_made;                         // streams with a hardware queue of their own, per device
     std::map<int, int> pooled_made;                            // streams drawn from the runtime's GPU_MAX_HW_QUEUES pool, per device (alive or recycled here)
     std::set<hipStream_t> dedicated;                           // which of the recycled streams are the dedicated ones
+    bool closing = false;                                      // the process is exiting: dedicated streams are destroyed, not recycled
     static Pools& get() { static Pools* p = new Pools(); return *p; }      // lives as long as the process
 };
 inline int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
@@ -287,8 +313,30 @@ inline QueueBudget queue_budget(int dev) {
     cache[dev] = b;
     return b;
 }
-// -1: not decided yet (the environment is read at the first stream); 0: off; k > 0: up to k job streams per device
-inline std::atomic<int>& dedicated_queues() { static std::atomic<int> v{-1}; return v; }
+// Dedicated streams do not outlive the process's exit handlers.  The runtime's own teardown destroys the hardware queues of
+// its pool but not those of streams with a compute-unit mask that nobody destroyed, and a queue left behind is still known to
+// whatever intercepts the queues of the process: under rocprofv3's kernel trace the profiler's exit-time destructor waited on
+// the signal of each such queue after the runtime had gone -- a segmentation fault at the very end of a run whose output was
+// complete.  So the first dedicated stream registers this handler (after the runtime's initialisation, hence run before its
+// teardown): the dedicated streams waiting in the pool are destroyed, and those still in use are when they come back.
+inline void release_dedicated_streams_at_exit() {
+    Pools& P = Pools::get();
+    std::vector<hipStream_t> gone;
+    {
+        std::lock_guard<std::mutex> g(P.mu);
+        P.closing = true;
+        for (auto& dv : P.streams) {
+            for (auto it = dv.second.begin(); it != dv.second.end();) {
+                if (!P.dedicated.erase(it->second)) { ++it; continue; }
+                gone.push_back(it->second);
+                P.stream_index.erase(it->second);
+                P.dedicated_made[dv.first]--;
+                it = dv.second.erase(it);
+            }
+        }
+    }
+    for (hipStream_t s : gone) if (hipStreamDestroy(s) != hipSuccess) (void)hipGetLastError();      // (waits for the stream's work)
+}
 // 0: a stream; -1: the runtime failed; -2: no stream left within the queue budget (the caller shares one it has)
 inline int stream_create(Stream* s) {
     Pools& P = Pools::get();
@@ -297,40 +345,53 @@ inline int stream_create(Stream* s) {
     std::lock_guard<std::mutex> g(P.mu);
     auto& v = P.streams[dev];
     if (!v.empty()) { *s = v.begin()->second; v.erase(v.begin()); return 0; }
-    // Dedicated hardware queues (bbs_runtime_set_dedicated_queues / BBS_DEDICATED_QUEUES=k): the runtime gives a stream
-    // created with a compute-unit mask (here: all ones, no restriction) a hardware queue of its own instead of a share of
-    // the GPU_MAX_HW_QUEUES pool.  For a process whose first HIP call came BEFORE this library was loaded (any torch user):
-    // the pool is then fixed at the runtime's default of 4, several jobs share a queue and a long narrow kernel blocks the
-    // others (measured: 1.30 M proof_verify/s instead of 1.50 M; with dedicated queues 1.50 M whatever the pool,
-    // profiles/r04_f_dedicated_queues.log).  At most min(k, what the scratch budget leaves beside the pool) streams per
-    // device are created this way; further streams come from the pool.  Such streams are BLOCKING with respect to the legacy
-    // default stream (the runtime offers no flags for them): off unless asked for.
-    int want = dedicated_queues().load();
-    if (want < 0) { const char* e = getenv("BBS_DEDICATED_QUEUES"); want = e ? atoi(e) : 0; if (want == 1) want = 12; if (want < 0) want = 0; if (want > 16) want = 16; dedicated_queues().store(want); }
-    if (qb.total > 0) want = std::min(want, qb.dedicated_cap);
-    bool made = false;
-    if (want > 0 && P.dedicated_made[dev] < want) {
+    // Dedicated hardware queues: the runtime gives a stream created with a compute-unit mask (here: all ones, no restriction)
+    // a hardware queue of its own instead of a share of the GPU_MAX_HW_QUEUES pool.  For a process whose first HIP call came
+    // BEFORE this library was loaded (any torch user) the pool is fixed at the runtime's default of 4, several jobs share a
+    // queue and a long narrow kernel blocks the others (1.30 M proof_verify/s instead of 1.50 M; with dedicated queues 1.50 M
+    // whatever the pool, profiles/r04_f_dedicated_queues.log; on the present library profiles/auto_queues_ab.log).  How many:
+    // queue_policy.hpp -- bbs_runtime_set_dedicated_queues / BBS_DEDICATED_QUEUES=k asks for k, 0 switches them off, and with
+    // nothing set the library makes up what the effective pool (load_state above) lacks of its own 20; always within the
+    // scratch budget, counted in queues actually touched.  Such streams are BLOCKING with respect to the legacy default stream
+    // (the runtime offers no flags for them): a host that runs its own kernels on stream 0 beside the jobs sets 0.
+    const int setting = dedicated_setting();
+    qpolicy::Kind kind = qpolicy::next_stream(effective_pool(), qb.pool, qb.total, setting, P.dedicated_made[dev], P.pooled_made[dev]);
+    if (kind == qpolicy::DEDICATED) {
         uint32_t mask[16];
         for (auto& m : mask) m = 0xFFFFFFFFu;
-        if (hipExtStreamCreateWithCUMask(s, 16, mask) == hipSuccess) { made = true; P.dedicated_made[dev]++; P.dedicated.insert(*s); }
-        else (void)hipGetLastError();
+        if (hipExtStreamCreateWithCUMask(s, 16, mask) == hipSuccess) {
+            P.dedicated_made[dev]++;
+            P.dedicated.insert(*s);
+            static std::once_flag at_exit;
+            std::call_once(at_exit, []() { (void)std::atexit(release_dedicated_streams_at_exit); });
+        } else {                                           // the runtime has none to give: as if none had been wished for
+            (void)hipGetLastError();
+            kind = qpolicy::next_stream(effective_pool(), qb.pool, qb.total, 0, P.dedicated_made[dev], P.pooled_made[dev]);
+        }
     }
-    if (!made) {
-        // the pool alone may be over budget (an explicit GPU_MAX_HW_QUEUES): streams map onto its queues round robin, so the
-        // number of pooled streams this library creates bounds the number of pooled queues it touches
-        if (qb.total > 0 && qb.pool > qb.total - P.dedicated_made[dev] && P.pooled_made[dev] >= std::max(1, qb.total - P.dedicated_made[dev])) return -2;
+    // the pool alone may be over budget (an explicit GPU_MAX_HW_QUEUES): streams map onto its queues round robin, so the number
+    // of pooled streams this library creates bounds the number of pooled queues it touches
+    if (kind == qpolicy::NONE) return -2;
+    if (kind == qpolicy::POOLED) {
         if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return -1; }
         P.pooled_made[dev]++;
     }
     P.stream_index[*s] = P.next_stream_index++;
     return 0;
 }
+// streams of the device made so far and not destroyed (alive or recycled here), by kind
+inline void queue_counts(int dev, int* dedicated, int* pooled) {
+    Pools& P = Pools::get();
+    std::lock_guard<std::mutex> g(P.mu);
+    *dedicated = P.dedicated_made[dev];
+    *pooled = P.pooled_made[dev];
+}
 inline void stream_destroy(Stream& s) {                  // callers synchronise the stream first
     Pools& P = Pools::get();
     std::lock_guard<std::mutex> g(P.mu);
     auto& v = P.streams[current_device()];
     auto it = P.stream_index.find(s);
-    if (it != P.stream_index.end() && v.size() < 256) { v.insert({it->second, s}); return; }
+    if (it != P.stream_index.end() && v.size() < 256 && !(P.closing && P.dedicated.count(s))) { v.insert({it->second, s}); return; }
     if (it != P.stream_index.end()) P.stream_index.erase(it);
     if (P.dedicated.erase(s)) P.dedicated_made[current_device()]--; else P.pooled_made[current_device()]--;
     (void)hipStreamDestroy(s);

@@ -99,6 +99,21 @@ def _ragged_bytes(items: Sequence[bytes]):
     return _bytes_arr(b"".join(bytes(x) for x in items)), off
 
 
+def queue_report(device: int = 0, lib_path: Optional[str] = None) -> dict:
+    """What the library decided and granted in hardware queues on a device so far (bbs_runtime_queue_report): the
+    dedicated-queue setting ("auto", or the number asked for; 0 = off), the pool the runtime is taken to use, and the streams
+    with a hardware queue of their own / from the runtime's pool created so far."""
+    return _queue_report(_lib.load_library(lib_path), device)
+
+
+def _queue_report(lib, device: int) -> dict:
+    m, e, d, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = lib.bbs_runtime_queue_report(device, ctypes.byref(m), ctypes.byref(e), ctypes.byref(d), ctypes.byref(p))
+    if rc:
+        raise BbsRuntimeError(rc, "bbs_runtime_queue_report")
+    return {"mode": "auto" if m.value < 0 else m.value, "effective_pool": e.value, "dedicated_made": d.value, "pooled_made": p.value}
+
+
 class Engine:
     """One context: (curve, GPU, generator set + api_id, issuer key)."""
 
@@ -112,8 +127,13 @@ class Engine:
             raise BbsRuntimeError(rc, "bbs_ctx_create")
         self.h = h
         self.L = None
+        self.device = device
         if window_bits is not None:
             self._chk(self.lib.bbs_ctx_set_window_bits(self.h, window_bits), "bbs_ctx_set_window_bits")
+
+    def queue_report(self) -> dict:
+        """queue_report() of this engine's device."""
+        return _queue_report(self.lib, self.device)
 
     def close(self):
         if getattr(self, "h", None):

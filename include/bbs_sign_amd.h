@@ -98,15 +98,22 @@ int bbs_runtime_hw_queues(void);
  * library is loaded: the runtime's pool is then 4 hardware queues, several jobs share one, 1.30 M proof_verify/s instead
  * of 1.50 M): up to k job streams per device get a hardware queue OF THEIR OWN (streams created with an all-ones
  * compute-unit mask, which the runtime does not draw from the pool) -- 1.50 M/s whatever GPU_MAX_HW_QUEUES says
- * (profiles/r04_f_dedicated_queues.log).  k = 0: off (the default); 12 is a good value, 16 the most accepted.  k is a WISH:
- * every hardware queue reserves scratch memory for the largest kernel frame it has run, pool + dedicated queues x that frame
- * is a budget, and past it the runtime first collapses and then ABORTS the process -- so the library grants
- * min(k, bbs_runtime_queue_budget's dedicated_cap) and serves further streams from the pool (round 5; before that, 16 on top of
- * a pool of 14 could abort).
+ * (profiles/r04_f_dedicated_queues.log; on the present library profiles/auto_queues_ab.log).
+ * THE DEFAULT IS AUTOMATIC: if this function is never called and BBS_DEDICATED_QUEUES is not in the environment, the
+ * library makes up what the runtime's pool lacks of its own 20, at most 12 -- a pool of 4 gives 12, 14 gives 6, 20 or
+ * more none.  The pool it goes by is the EFFECTIVE one, from what it found when it was loaded: a GPU_MAX_HW_QUEUES somebody
+ * else had set counts as set; its own 20 counts only if the runtime had not started yet, otherwise -- and when that cannot
+ * be told -- the runtime's default of 4 (bbs_runtime_queue_report shows what was assumed and granted).
+ * k = 0: OFF, never overridden; k >= 1: at most k (12 is a good value, 16 the most accepted).  k, asked for or automatic, is a
+ * WISH: every hardware queue reserves scratch memory for the largest kernel frame it has run, pooled + dedicated queues x
+ * that frame is a budget, and past it the runtime first collapses and then ABORTS the process -- so per device the library
+ * keeps   dedicated streams + min(GPU_MAX_HW_QUEUES as the environment has it, pooled streams) <= bbs_runtime_queue_budget's
+ * total,   counted in streams it has really created, grants a dedicated stream only where room is left for the effective pool
+ * beside it, and serves further streams from the pool.  A wrong guess of the pool costs speed, never the abort.
  * Call before the first context is created (streams are recycled); BBS_DEDICATED_QUEUES=k in the environment does the same
  * (1 means 12).  Caveat: such streams synchronise with the legacy default stream (the runtime offers no non-blocking flag
- * for them): a process that also runs its own kernels on stream 0 -- torch and RCCL work on the default stream -- serialises
- * them with the jobs. */
+ * for them): a process that also runs its own kernels on stream 0 BESIDE the jobs -- torch and RCCL work on the default
+ * stream -- serialises them with the jobs.  Such a host sets 0 and loads this library before its first HIP call instead. */
 int bbs_runtime_set_dedicated_queues(int k);
 /* The hardware-queue budget of a device, as the library enforces it: *scratch_bytes_per_lane = the largest kernel frame of
  * this library (every kernel is asked at start-up), *total = hardware queues (pooled + dedicated) that frame allows within
@@ -117,6 +124,12 @@ int bbs_runtime_set_dedicated_queues(int k);
  * BBS_E_NO_RESOURCES once even the context's stream cannot be had -- slower or refused, never the runtime's abort.  Any
  * pointer may be NULL.  BBS_E_NO_DEVICE for a device that does not exist. */
 int bbs_runtime_queue_budget(int device_id, int* total, int* pool, int* dedicated_cap, size_t* scratch_bytes_per_lane);
+/* What the library decided and granted on a device so far: *mode = the dedicated-queue setting (-1 automatic, 0 off, k >= 1
+ * asked for), *effective_pool = the pool the runtime is taken to use (see bbs_runtime_set_dedicated_queues), *dedicated_made /
+ * *pooled_made = streams with a hardware queue of their own / from the runtime's pool that the library has created on the
+ * device and not destroyed (in use or waiting to be reused).  Any pointer may be NULL.  BBS_E_NO_DEVICE for a device that does
+ * not exist. */
+int bbs_runtime_queue_report(int device_id, int* mode, int* effective_pool, int* dedicated_made, int* pooled_made);
 int bbs_device_count(void);
 size_t bbs_device_free_bytes(int device_id);          /* device memory free right now (0: no such device) */
 

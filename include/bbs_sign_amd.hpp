@@ -134,6 +134,17 @@ inline void zeroize(uint8_t* p, size_t n) {
 
 }  // namespace detail
 
+// hardware queues on a device: what the library decided and granted so far (bbs_runtime_queue_report)
+struct QueueReport {
+    int mode = 0;                                     // -1 automatic, 0 off, k >= 1 dedicated streams asked for
+    int effective_pool = 0, dedicated_made = 0, pooled_made = 0;
+};
+inline QueueReport queue_report(int device = 0) {
+    QueueReport r;
+    detail::check(bbs_runtime_queue_report(device, &r.mode, &r.effective_pool, &r.dedicated_made, &r.pooled_made), "bbs_runtime_queue_report");
+    return r;
+}
+
 class PublicKey {                                     // src/key_gen.rs:12-15
 public:
     Curve curve = Curve::Bls12_381;
