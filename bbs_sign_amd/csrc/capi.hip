@@ -1119,6 +1119,11 @@ int bbs_selftest_f12(bbs_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, u
     if (!ctx || !a || !b || !out_single || !out_dist) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return selftest_f12(c, op, a, b, out_single, out_dist); });
 }
+int bbs_selftest_f12_batch(bbs_ctx* ctx, int op, size_t n, const uint8_t* a, const uint8_t* b, const int8_t* active, int line_table,
+                           int line_index, uint8_t* out_single, uint8_t* out_dist, int8_t* flag_out) {
+    if (!ctx || (n && (!a || !b || !out_dist || !flag_out))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return selftest_f12_batch(c, op, n, a, b, active, line_table, line_index, out_single, out_dist, flag_out); });
+}
 
 int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, const int8_t* is_identity, const uint8_t* pk_octets, int path,
                              uint8_t* entries_out, int8_t* status_out, uint8_t* pk_affine_out) {

@@ -371,14 +371,14 @@ int pairing_batch(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, i
 // tower code compiled for the host (tower.hpp / pairing.hpp, validated against the oracle by the
 // host-twin tests); only the six-lane version runs on the device.
 template <class C, int OP>
-static Fp12<C> selftest_ref(const Fp12<C>& x, const Fp12<C>& y, const CtxConsts<C>& hc, const G1Aff<C>& P) {
+static Fp12<C> selftest_ref(const Fp12<C>& x, const Fp12<C>& y, const LineEntry<C>& le, const G1Aff<C>& P) {
     if constexpr (OP == 0) return f12_mul<C>(x, y);
     else if constexpr (OP == 1) return f12_frob<C, 1>(x);
     else if constexpr (OP == 2) return f12_frob<C, 2>(x);
     else if constexpr (OP == 3) return f12_frob<C, 3>(x);
     else if constexpr (OP == 4) return f12_inv<C>(x);
     else if constexpr (OP == 5) return f12_conj<C>(x);
-    else if constexpr (OP == 6) return f12_mul_line<C>(x, hc.tab_bp2.e[3], P);
+    else if constexpr (OP == 6) return f12_mul_line<C>(x, le, P);
     else if constexpr (OP == 7) return final_exponentiation<C>(x);
     else if constexpr (OP == 10) return f12_sqr<C>(x);
     else if constexpr (OP == 8) return f12_sqr<C>(x);
@@ -386,54 +386,101 @@ static Fp12<C> selftest_ref(const Fp12<C>& x, const Fp12<C>& y, const CtxConsts<
     else return x;
 }
 
+// n items, laid out over the wavefronts as the pairing kernels lay theirs out (stages_prim.hpp SelfTestDist).  The device
+// buffers of an item that is not active are compared with what was uploaded: a lane that wrote for a gated item is
+// BBS_E_STATE.  Such an item's out_single, out_dist and flag_out are left as the caller passed them.
 template <class C>
-int selftest_f12(Ctx<C>* ctx, int op, const uint8_t* a_le, const uint8_t* b_le, uint8_t* out_single, uint8_t* out_dist) {
+int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const uint8_t* b_le, const int8_t* active, int line_table,
+                       int line_index, uint8_t* out_single, uint8_t* out_dist, int8_t* flag_out) {
 #ifdef BBS_HOST_TWIN
-    (void)ctx; (void)op; (void)a_le; (void)b_le; (void)out_single; (void)out_dist;
+    (void)ctx; (void)op; (void)n; (void)a_le; (void)b_le; (void)active; (void)line_table; (void)line_index; (void)out_single; (void)out_dist;
+    (void)flag_out;
     return BBS_E_ARG;
 #else
     constexpr int N = C::FpP::N;
     constexpr int FPB = 4 * C::FpP::NC;
+    constexpr int8_t UNWRITTEN = -128;
     using P = typename C::FpP;
-    if (ctx->use()) return BBS_E_HIP;
-    Fp<C> xe[12], ye[12];
-    for (int k = 0; k < 12; k++)
-        if (!fe_from_le_bytes<P>(a_le + k * FPB, xe[k]) || !fe_from_le_bytes<P>(b_le + k * FPB, ye[k])) return BBS_E_ARG;
-    Fp12<C> x = f12_from_array<C>(xe), y = f12_from_array<C>(ye);
-    if (op >= 10) {   // cyclotomic input
-        x = f12_mul<C>(f12_conj<C>(x), f12_inv<C>(x));
-        x = f12_mul<C>(f12_frob<C, 2>(x), x);
+    if (op < 0 || op > 12 || op == 9) return BBS_E_ARG;
+    if (!n) return BBS_OK;
+    LineEntry<C> le{};
+    if (op == 6) {
+        if (line_table != 0 && line_table != 1) return BBS_E_ARG;
+        if (line_table == 0 && !ctx->pk_set) return BBS_E_STATE;
+        const LineTable<C>& tab = line_table ? ctx->hc.tab_bp2 : ctx->hc.tab_pk;
+        if (line_index < 0 || line_index >= tab.n_lines) return BBS_E_ARG;
+        le = tab.e[line_index];
     }
-    G1Aff<C> Pt = {ye[0], ye[1]};
-    Fp12<C> rs;
-    int lrc = -1;
-    std::vector<uint32_t> X(12 * N), B(12 * N);
-    f12_to_array<C>(x, xe);
-    for (int k = 0; k < 12; k++) for (int j = 0; j < N; j++) { X[k * N + j] = xe[k].v[j]; B[k * N + j] = ye[k].v[j]; }
-    DevBuf dB, dD;
-    if (dB.alloc(B.size() * 4) || dD.alloc(X.size() * 4)) return BBS_E_NOMEM;
-    if (rt::h2d(dB.p, B.data(), B.size() * 4, ctx->stream) || rt::h2d(dD.p, X.data(), X.size() * 4, ctx->stream)) return BBS_E_HIP;
+    if (ctx->use()) return BBS_E_HIP;
+    std::vector<uint32_t> X(n * 12 * N), B(n * 12 * N);
+    std::vector<int8_t> act(n, 1);
+    std::vector<Fp12<C>> ref(out_single ? n : 0);
+    for (size_t i = 0; i < n; i++) {
+        if (active) act[i] = active[i] ? 1 : 0;
+        Fp<C> xe[12], ye[12];
+        for (int k = 0; k < 12; k++)
+            if (!fe_from_le_bytes<P>(a_le + (i * 12 + k) * FPB, xe[k]) || !fe_from_le_bytes<P>(b_le + (i * 12 + k) * FPB, ye[k])) return BBS_E_ARG;
+        Fp12<C> x = f12_from_array<C>(xe), y = f12_from_array<C>(ye);
+        if (op == 10 || op == 11) {   // cyclotomic input
+            x = f12_mul<C>(f12_conj<C>(x), f12_inv<C>(x));
+            x = f12_mul<C>(f12_frob<C, 2>(x), x);
+        }
+        const G1Aff<C> Pt = {ye[0], ye[1]};
+        f12_to_array<C>(x, xe);
+        for (int k = 0; k < 12; k++) for (int j = 0; j < N; j++) { X[(i * 12 + k) * N + j] = xe[k].v[j]; B[(i * 12 + k) * N + j] = ye[k].v[j]; }
+        if (!out_single || !act[i]) continue;
+#define BBS_ST_CASE(K) case K: ref[i] = selftest_ref<C, K>(x, y, le, Pt); break;
+        switch (op) {
+            BBS_ST_CASE(0) BBS_ST_CASE(1) BBS_ST_CASE(2) BBS_ST_CASE(3) BBS_ST_CASE(4) BBS_ST_CASE(5)
+            BBS_ST_CASE(6) BBS_ST_CASE(7) BBS_ST_CASE(8) BBS_ST_CASE(10) BBS_ST_CASE(11) BBS_ST_CASE(12)
+            default: return BBS_E_ARG;
+        }
+#undef BBS_ST_CASE
+    }
+    DevBuf dB, dD, dAct, dFlag;
+    if (dB.alloc(B.size() * 4) || dD.alloc(X.size() * 4) || dAct.alloc(n + 4) || dFlag.alloc(n + 4)) return BBS_E_NOMEM;
+    std::vector<int8_t> flag(n, UNWRITTEN);
+    if (rt::h2d(dB.p, B.data(), B.size() * 4, ctx->stream) || rt::h2d(dD.p, X.data(), X.size() * 4, ctx->stream) ||
+        rt::h2d(dAct.p, act.data(), n, ctx->stream) || rt::h2d(dFlag.p, flag.data(), n, ctx->stream)) return BBS_E_HIP;
     int rc = ctx->sync_consts();
     if (rc) return rc;
-    SelfTestArgs<C> a{op, ctx->d_consts.template as<CtxConsts<C>>(), nullptr, dB.as<uint32_t>(), nullptr, dD.as<uint32_t>()};
-#define BBS_ST_CASE(K) case K: rs = selftest_ref<C, K>(x, y, ctx->hc, Pt); lrc = rt::launch<SelfTestDist<C, K>>(ctx->stream, a, 64); break;
+    SelfTestArgs<C> a{op, n, ctx->d_consts.template as<CtxConsts<C>>(), dB.as<uint32_t>(), dAct.as<int8_t>(), line_table, line_index,
+                      dD.as<uint32_t>(), dFlag.as<int8_t>()};
+    const size_t nthreads = ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
+    int lrc = -1;
+#define BBS_ST_CASE(K) case K: lrc = rt::launch<SelfTestDist<C, K>>(ctx->stream, a, nthreads); break;
     switch (op) {
         BBS_ST_CASE(0) BBS_ST_CASE(1) BBS_ST_CASE(2) BBS_ST_CASE(3) BBS_ST_CASE(4) BBS_ST_CASE(5)
-        BBS_ST_CASE(6) BBS_ST_CASE(7) BBS_ST_CASE(8) BBS_ST_CASE(10) BBS_ST_CASE(11)
+        BBS_ST_CASE(6) BBS_ST_CASE(7) BBS_ST_CASE(8) BBS_ST_CASE(10) BBS_ST_CASE(11) BBS_ST_CASE(12)
         default: return BBS_E_ARG;
     }
 #undef BBS_ST_CASE
     if (lrc || rt::sync(ctx->stream)) return BBS_E_HIP;
-    std::vector<uint32_t> D(12 * N);
-    if (rt::d2h(D.data(), dD.p, D.size() * 4, ctx->stream)) return BBS_E_HIP;
-    Fp<C> se[12];
-    f12_to_array<C>(rs, se);
-    for (int k = 0; k < 12; k++) {
-        Fe<P> yv;
-        for (int j = 0; j < N; j++) yv.v[j] = D[k * N + j];
-        fe_to_le_bytes<P>(se[k], out_single + k * FPB);
-        fe_to_le_bytes<P>(yv, out_dist + k * FPB);
+    std::vector<uint32_t> D(X.size());
+    if (rt::d2h(D.data(), dD.p, D.size() * 4, ctx->stream) || rt::d2h(flag.data(), dFlag.p, n, ctx->stream)) return BBS_E_HIP;
+    for (size_t i = 0; i < n; i++) {
+        if (!act[i]) {
+            if (flag[i] != UNWRITTEN || std::memcmp(&D[i * 12 * N], &X[i * 12 * N], (size_t)12 * N * 4) != 0) return BBS_E_STATE;
+            continue;
+        }
+        Fp<C> se[12];
+        if (out_single) f12_to_array<C>(ref[i], se);
+        for (int k = 0; k < 12; k++) {
+            Fe<P> yv;
+            for (int j = 0; j < N; j++) yv.v[j] = D[(i * 12 + k) * N + j];
+            if (out_single) fe_to_le_bytes<P>(se[k], out_single + (i * 12 + k) * FPB);
+            fe_to_le_bytes<P>(yv, out_dist + (i * 12 + k) * FPB);
+        }
+        flag_out[i] = flag[i];
     }
     return BBS_OK;
 #endif
+}
+
+template <class C>
+int selftest_f12(Ctx<C>* ctx, int op, const uint8_t* a_le, const uint8_t* b_le, uint8_t* out_single, uint8_t* out_dist) {
+    if (op == 12) return BBS_E_ARG;                     // (the boolean has no place in this entry's outputs)
+    int8_t flag = 0;
+    const int rc = selftest_f12_batch<C>(ctx, op, 1, a_le, b_le, nullptr, 1, 3, out_single, out_dist, &flag);
+    return (rc == BBS_OK && flag != 1) ? BBS_E_STATE : rc;
 }

@@ -158,34 +158,42 @@ struct MsmCombine {
 };
 
 #if !defined(BBS_HOST_TWIN)
-// self-test: one Fp12 operation computed by the one-lane code and by the six-lane code
+// self-test: one Fp12 operation per item computed by the one-lane code (on the host) and by the six-lane code, the items laid
+// out over the wavefronts as PairDist lays them out: wave = t / 64, group = (t % 64) / 6, item = wave * 10 + group
 template <class C>
 struct SelfTestArgs {
     int op;
+    size_t n;
     const CtxConsts<C>* cc;
-    const uint32_t* a;      // 12 Fp (tower order c0.c0.c0, c0.c0.c1, c0.c1.c0 ... ), Montgomery
-    const uint32_t* b;
-    uint32_t* out_single;   // 12 Fp
-    uint32_t* out_dist;     // 12 Fp
+    const uint32_t* b;      // [n][12] Fp (tower order c0.c0.c0, c0.c0.c1, c0.c1.c0 ... ), Montgomery; OP 6: the point (b[0], b[1])
+    const int8_t* active;   // [n]: an item that is not active is left by its six lanes before any exchange (a gated item of PairDist)
+    int line_table;         // OP 6: 0 = tab_pk, 1 = tab_bp2
+    int line_index;         //       the entry of that table
+    uint32_t* out_dist;     // [n][12] Fp: the operand x as prepared by the host (already cyclotomic for OP 10, 11), then the result
+    int8_t* flag;           // [n]: 1 once the item's result is stored; OP 12: the boolean of d_is_one
 };
-// six-lane version; input x = out_dist as prepared by the host (already cyclotomic for OP >= 10)
 template <class C, int OP>
 struct SelfTestDist {
     static __device__ void run(const SelfTestArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
         const int grp = lane / GRP;
-        if (grp >= 1) return;
+        if (grp >= GRP_PER_WAVE) return;
+        const size_t i = (t >> 6) * GRP_PER_WAVE + grp;
+        if (i >= a.n) return;
+        if (!a.active[i]) return;
         Lane6 L{grp * GRP, lane - grp * GRP};
         // w-basis coefficient m of a tower-ordered array: g_m = (e[2k], e[2k+1]) with k = (m & 1) * 3 + (m >> 1)
         const int k = (L.m & 1) * 3 + (L.m >> 1);
+        uint32_t* xd = a.out_dist + i * 12 * N;
+        const uint32_t* yd = a.b + i * 12 * N;
         Fp2<C> gx, gy;
         for (int j = 0; j < N; j++) {
-            gx.c0.v[j] = a.out_dist[(2 * k) * N + j]; gx.c1.v[j] = a.out_dist[(2 * k + 1) * N + j];
-            gy.c0.v[j] = a.b[(2 * k) * N + j]; gy.c1.v[j] = a.b[(2 * k + 1) * N + j];
+            gx.c0.v[j] = xd[(2 * k) * N + j]; gx.c1.v[j] = xd[(2 * k + 1) * N + j];
+            gy.c0.v[j] = yd[(2 * k) * N + j]; gy.c1.v[j] = yd[(2 * k + 1) * N + j];
         }
         G1Aff<C> P;
-        for (int j = 0; j < N; j++) { P.x.v[j] = a.b[j]; P.y.v[j] = a.b[N + j]; }
+        for (int j = 0; j < N; j++) { P.x.v[j] = yd[j]; P.y.v[j] = yd[N + j]; }
         const uint32_t* ft = &a.cc->frob[0][0][0][0];
         Fp2<C> rd;
         if constexpr (OP == 0) rd = d_mul<C>(L, gx, gy);
@@ -194,13 +202,16 @@ struct SelfTestDist {
         else if constexpr (OP == 3) rd = d_frob<C, 3>(L, gx, ft);
         else if constexpr (OP == 4) rd = d_inv<C>(L, gx);
         else if constexpr (OP == 5) rd = d_conj<C>(L, gx);
-        else if constexpr (OP == 6) rd = d_mul_line<C>(L, gx, a.cc->tab_bp2.e[3], P);
+        else if constexpr (OP == 6) rd = d_mul_line<C>(L, gx, (a.line_table ? a.cc->tab_bp2 : a.cc->tab_pk).e[a.line_index], P);
         else if constexpr (OP == 7) rd = d_final_exp<C>(L, gx, ft);
         else if constexpr (OP == 10) rd = d_cyclo_sqr<C>(L, gx);
         else if constexpr (OP == 8) rd = d_sqr<C>(L, gx);
         else if constexpr (OP == 11) rd = d_pow_x<C>(L, gx);
         else rd = gx;
-        for (int j = 0; j < N; j++) { a.out_dist[(2 * k) * N + j] = rd.c0.v[j]; a.out_dist[(2 * k + 1) * N + j] = rd.c1.v[j]; }
+        int8_t flag = 1;
+        if constexpr (OP == 12) flag = d_is_one<C>(L, gx) ? 1 : 0;
+        for (int j = 0; j < N; j++) { xd[(2 * k) * N + j] = rd.c0.v[j]; xd[(2 * k + 1) * N + j] = rd.c1.v[j]; }
+        if (L.m == 0) a.flag[i] = flag;
     }
 };
 #endif

@@ -751,10 +751,23 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
                              const uint8_t* pk_octets, int path, uint8_t* entries_out, int8_t* status_out,
                              uint8_t* pk_affine_out);
 size_t bbs_selftest_key_entry_bytes(int curve);
-/* GPU self-test: one Fp12 operation (12 Fp values a, b, canonical LE, tower order) computed by the
- * one-lane code and by the six-lane wavefront-cooperative code; the caller compares the outputs.
- * op: 0 mul, 1..3 Frobenius^k, 4 inverse, 5 conjugate, 6 line multiplication, 7 final
- * exponentiation, 10 cyclotomic square, 11 power by the curve parameter. */
+/* GPU self-test: one Fp12 operation per item (12 Fp values a, b per item, canonical LE, tower order) computed by the
+ * one-lane code (on the host) and by the six-lane wavefront-cooperative code; the caller compares the outputs.
+ * op: 0 mul, 1..3 Frobenius^k, 4 inverse, 5 conjugate, 6 line multiplication (the point is (b[0], b[1]), any pair of field
+ * elements), 7 final exponentiation, 8 square, 10 cyclotomic square, 11 power by the curve parameter (for 10 and 11 the host
+ * first maps a into the cyclotomic subgroup: a^((p^6-1)(p^2+1))), 12 is_one (the six-lane comparison with one; out_dist
+ * and out_single return the operand).
+ * The n items are laid out as the pairing kernels lay theirs out: six lanes per item, ten items per wavefront (item
+ * i = wavefront * 10 + group, lanes 60..63 idle), ceil(n / 10) wavefronts, so items 0..9 exercise every group position
+ * and n % 10 != 0 a ragged last wavefront.  active (n entries, or NULL = all active): the lanes of an item with active[i] = 0
+ * leave before any exchange, as those of a gated item do in the pairing kernels; such an item's out_single, out_dist and
+ * flag_out entries are left untouched, and BBS_E_STATE is returned if the device wrote anything for it.
+ * line_table / line_index (op 6 only): 0 = the public key's line table (needs a key), 1 = BP2's; the entry, below the
+ * table's line count.  out_single: n x 12 Fp, may be NULL; out_dist: n x 12 Fp; flag_out: n entries, 1 for an item whose
+ * result the device stored, for op 12 the boolean.  The CPU test build has no six-lane code: BBS_E_ARG. */
+int bbs_selftest_f12_batch(bbs_ctx* ctx, int op, size_t n, const uint8_t* a, const uint8_t* b, const int8_t* active,
+                           int line_table, int line_index, uint8_t* out_single, uint8_t* out_dist, int8_t* flag_out);
+/* The same for one item (ops 0..11) in group 0 of one wavefront, line entry 3 of BP2's table. */
 int bbs_selftest_f12(bbs_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* out_single,
                      uint8_t* out_dist);
 /* Host arithmetic self-test (no GPU): out = sum_k w_k * a_k * b_k in Fp2 computed by the lazily reduced column

@@ -80,6 +80,20 @@ def test_misuse_is_refused(twin, curve):
     assert lib.bbs_job_fetch_signatures(job, _u8(sigs)) == E_ARG
     assert lib.bbs_job_fetch_proofs(job, _u8(pf), none8, none64) == E_ARG
     lib.bbs_job_free(job)
+    # the six-lane self-test entries: the CPU build has no six-lane code, so every call is BBS_E_ARG here whatever its arguments
+    # (NULL or in order) -- this only pins that no call crashes or computes; the argument checks of the real build are tested on
+    # the GPU (test_selftest_gpu.py::test_selftest_entries_check_their_arguments)
+    f12 = np.zeros(2 * 12 * fpb, dtype=np.uint8)
+    act = np.ones(2, dtype=np.int8)
+    ai8 = act.ctypes.data_as(_lib.c_i8p)
+    assert lib.bbs_selftest_f12(None, 0, _u8(f12), _u8(f12), _u8(f12), _u8(f12)) == E_ARG
+    assert lib.bbs_selftest_f12(h, 0, _u8(f12), _u8(f12), _u8(f12), _u8(f12)) == E_ARG
+    assert lib.bbs_selftest_f12_batch(None, 0, 2, _u8(f12), _u8(f12), ai8, 1, 3, none8, _u8(f12), i8) == E_ARG
+    assert lib.bbs_selftest_f12_batch(h, 0, 2, none8, _u8(f12), ai8, 1, 3, none8, _u8(f12), i8) == E_ARG
+    assert lib.bbs_selftest_f12_batch(h, 0, 2, _u8(f12), none8, ai8, 1, 3, none8, _u8(f12), i8) == E_ARG
+    assert lib.bbs_selftest_f12_batch(h, 0, 2, _u8(f12), _u8(f12), ai8, 1, 3, none8, none8, i8) == E_ARG
+    assert lib.bbs_selftest_f12_batch(h, 0, 2, _u8(f12), _u8(f12), ai8, 1, 3, none8, _u8(f12), ctypes.cast(None, _lib.c_i8p)) == E_ARG
+    assert lib.bbs_selftest_f12_batch(h, 12, 2, _u8(f12), _u8(f12), ctypes.cast(None, _lib.c_i8p), 1, 3, none8, _u8(f12), i8) == E_ARG
     # The verify family: each single-key export and its keyed twin refuse a NULL context, status or job_out with
     # BBS_E_ARG, and do so before they look at the context's state (this one has no key set: BBS_E_STATE for the keyed
     # forms, which also comes before the NULL key_index is looked at).
