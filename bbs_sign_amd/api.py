@@ -214,6 +214,64 @@ def proof_verify(pk: PublicKey, proof: Proof, header: bytes, ph: bytes, disclose
     return eng.core_proof_verify(proof, header, ph, msg_to_scalars(eng, pk.curve, disclosed_messages), disclosed_indexes)
 
 
+# ------------------------------------------------------------------ many items, any lengths
+def _mixed_engine(pk: PublicKey, L: int) -> Engine:
+    """A cached engine of this key with bbs_ctx_set_mixed_lengths on, made for L messages or more: its own cache entries, so
+    that the one-item functions above keep their fixed-length engines."""
+    who = (pk.curve, None if pk.pk is None else tuple(map(tuple, pk.pk)), pk.device, pk.lib_path)
+    # any cached mixed engine of this key made for at least L messages serves (the smallest such): one copy of the tables
+    fits = [k for k in _eng_cache if k[0] == "mixed" and k[2:] == who and k[1] >= L]
+    if fits:
+        return _eng_cache[min(fits, key=lambda k: k[1])]
+    eng = Engine(pk.curve, device=pk.device, lib_path=pk.lib_path, window_bits=4 if pk.lib_path is not None else None)
+    eng.set_generators(create_generators(pk.curve, L + 1, pk.lib_path), api_id(pk.curve))
+    eng.set_public_key(pk.pk)
+    eng.set_mixed_lengths(True)
+    for k in [k for k in _eng_cache if k[0] == "mixed" and k[2:] == who]:      # the shorter ones it replaces
+        _eng_cache.pop(k).close()
+    _eng_cache[("mixed", L) + who] = eng
+    return eng
+
+
+def _many(items, to_octets, run):
+    """Shared tail of verify_many / proof_verify_many: items whose object cannot be written as octets keep the codec's
+    BbsError, the others run in ONE device call; statuses become booleans or BbsError objects."""
+    out: list = [None] * len(items)
+    octs, idx = [], []
+    for i, it in enumerate(items):
+        try:
+            octs.append(to_octets(it[0]))
+            idx.append(i)
+        except BbsError as e:
+            out[i] = e
+    if idx:
+        for i, s in zip(idx, run(octs, [items[i] for i in idx])):
+            out[i] = BbsError(int(s)) if s < 0 else bool(s)
+    return out
+
+
+def verify_many(pk: PublicKey, items: Sequence[tuple]) -> list:
+    """PublicKey.verify for many items ``(signature, header, messages)`` whose message counts may differ, in ONE device call:
+    one cached engine whose L is the largest count present, with mixed lengths on, through the wire form.  Entry i is the
+    boolean ``pk.verify(*items[i])`` returns, or the BbsError it raises (returned, not raised: the other items stand)."""
+    if not items:
+        return []
+    eng = _mixed_engine(pk, max(len(it[2]) for it in items))
+    return _many(items, lambda sig: signature_to_octets(pk.curve, sig, pk.lib_path),
+                 lambda octs, its: eng.verify_wire_batch(octs, [list(it[2]) for it in its], [it[1] for it in its]))
+
+
+def proof_verify_many(pk: PublicKey, items: Sequence[tuple]) -> list:
+    """proof_verify for many items ``(proof, header, ph, disclosed_messages, disclosed_indexes)`` of any message counts
+    (commitments + disclosed indexes each), in ONE device call, as verify_many."""
+    if not items:
+        return []
+    eng = _mixed_engine(pk, max(len(it[0].commitments) + len(it[4]) for it in items))
+    return _many(items, lambda proof: proof_to_octets(pk.curve, proof, pk.lib_path),
+                 lambda octs, its: eng.proof_verify_wire_batch(octs, [list(it[3]) for it in its], [list(it[4]) for it in its],
+                                                               [it[1] for it in its], [it[2] for it in its]))
+
+
 # ---------------------------------------------------------------------------------- wire codec
 def _curve_id(curve: str) -> int:
     return 0 if curve == "bls12_381" else 1

@@ -212,10 +212,12 @@ struct PvOctDecode {
         soa_st<2 * NC>(a.pts + (size_t)p * 2 * NC * a.n, a.n, i, o);
     }
 };
-template <class C>
-struct PvOctIngest {
+// MIXED (bbs_ctx_set_mixed_lengths, PvOctIngestMixed below): as PvIngest's -- the item's own count l = commitments + disclosed
+// indexes in 0 .. L, recorded in len[i]; l != L becomes l > L
+template <class C, bool MIXED>
+struct PvOctIngestBody {
     static __host__ __device__ void be32(const uint8_t* b, uint32_t* w) { be32_words(b, w); }
-    static __host__ __device__ void run(const PvOctArgs<C>& a, size_t i) {
+    static BBS_HD void run(const PvOctArgs<C>& a, size_t i, uint32_t* len) {
         using R = typename C::FrP;
         constexpr size_t NB = 4 * C::FpP::NC;
         const size_t n = a.n;
@@ -226,6 +228,7 @@ struct PvOctIngest {
         const int MW = ((a.L > 1 ? a.L : 1) + 31) / 32;
         for (int w = 0; w < MW; w++) a.dmask[(size_t)w * n + i] = 0;
         a.rcount[i] = 0;
+        if constexpr (MIXED) len[i] = 0;
         size_t u;
         if (!pv_oct_shape<C>(a, i, u)) { a.status0[i] = -42; return; }
         int8_t verdict = ST_PENDING;
@@ -254,9 +257,10 @@ struct PvOctIngest {
         int8_t st = ST_PENDING;
         if (bad) st = -3;
         else if (rm != r) st = -6;
-        else if (l != (uint64_t)a.L) st = -1;
+        else if (MIXED ? l > (uint64_t)a.L : l != (uint64_t)a.L) st = -1;
         else if (a.dst_too_long) st = -23;
         else {
+            if constexpr (MIXED) len[i] = (uint32_t)l;
             uint64_t distinct = 0;
             for (uint64_t k = 0; k < r; k++) {
                 const size_t j = (size_t)idx[k];
@@ -284,6 +288,14 @@ struct PvOctIngest {
         a.rcount[i] = (uint32_t)r;
         a.status0[i] = ok ? ST_PENDING : (int8_t)-40;
     }
+};
+template <class C>
+struct PvOctIngest {
+    static __host__ __device__ void run(const PvOctArgs<C>& a, size_t i) { PvOctIngestBody<C, false>::run(a, i, nullptr); }
+};
+template <class C>
+struct PvOctIngestMixed {
+    static __host__ __device__ void run(const MixedIngestArgs<PvOctArgs<C>>& m, size_t i) { PvOctIngestBody<C, true>::run(m.a, i, m.len); }
 };
 
 // ---- verify from the wire: signature OCTET strings compress(A) || e (32 bytes big-endian) --------------------------

@@ -43,14 +43,14 @@ template <class C>
 struct PvScalarsKeyed {
     static __host__ __device__ void run(const KeyedScalarArgs<C, PvArgs<C>>& k, size_t i) {
         if (k.a.status[i] != ST_PENDING) return;
-        pv_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash);
+        pv_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
     }
 };
 template <class C>
 struct VfScalarsKeyed {
     static __host__ __device__ void run(const KeyedScalarArgs<C, VfArgs<C>>& k, size_t i) {
         if (k.a.status[i] != ST_PENDING) return;
-        vf_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash);
+        vf_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
     }
 };
 

@@ -14,6 +14,7 @@ struct VfJob : JobBase<C> {
     MsgHashArgs mh{};                 // raw-message form only
     BvState<C> bv{};                  // batch verification only
     KeyedJob<C> kj{};                 // keyed form only
+    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths)
 };
 
 // KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
@@ -25,6 +26,7 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int FPB = 4 * NC;
     if constexpr (KEYED) {
         if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
+        if (ctx->mixed_lengths) return BBS_E_STATE;       // a prefix per (key, length) is not built: keyed.hpp
         if (n && !in.key_index) return BBS_E_ARG;
     } else {
         if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
@@ -94,7 +96,13 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     }
     ia.sig_a = sig_a; ia.sig_e = sig_e; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
-    if (rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
+    const bool mixed = !KEYED && ctx->mixed_lengths;
+    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if constexpr (!KEYED) {
+        if (mixed && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+    }
+    if (!mixed && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
     if constexpr (KEYED) {
         if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
     }
@@ -111,6 +119,8 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     j->stages.push_back({"vf_var_mul", [j, side]() { return rt::launch<VfVarMul<C>>(side ? j->stream_aux(1) : j->stream(), j->a, j->n); }, side, 0});
     if constexpr (KEYED)
         j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+    else if (mixed)
+        j->stages.push_back({"vf_scalars_mixed", [j]() { return rt::launch<VfScalarsMixed<C>>(j->stream(), MixedScalarArgs<VfArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
     else
         j->stages.push_back({"vf_scalars", [j]() { return rt::launch<VfScalars<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"vf_fixed_chunks", [j]() { return rt::launch<VfFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});

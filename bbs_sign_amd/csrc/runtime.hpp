@@ -624,6 +624,16 @@ struct Ctx : bbs_ctx {
         DevBuf d;                    // [n] KeyEntry<C>
     };
     std::shared_ptr<const KeySet> keys;
+    // mixed message counts (bbs_ctx_set_mixed_lengths): off by default.  On: the single-key verify / proof_verify jobs created
+    // from now on accept item i with its own count l_i <= L; the only data of a context that depend on the count are the domain
+    // prefixes, one HashCtx per length 0 .. L (prefix l = the first l + 1 generators: create_generators is prefix-consistent).
+    // The host mirror is rebuilt by rebuild_hash like hc.hash and uploaded by sync_lengths when the next job is created; the
+    // device array is immutable once built and a job holds a reference, so a change of key or generators never reaches a job
+    // that exists (the rule of the key set above).
+    bool mixed_lengths = false;
+    struct LenSet { DevBuf d; };     // [L + 1] HashCtx
+    std::vector<HashCtx> len_hash;   // host mirror; empty unless the switch is on and generators and key are set
+    std::shared_ptr<const LenSet> len_set;      // null: to be uploaded from len_hash
     // batch verification (pippenger.hpp): off by default = every item gets its own pairing product
     bool batch_verify = false;
     // caller vouches that every G1 input is in the prime-order subgroup: variable-base multiplications of the
@@ -691,7 +701,9 @@ struct Ctx : bbs_ctx {
     }
 
     int use() { return rt::set_device(device) ? BBS_E_HIP : BBS_OK; }
-    size_t table_bytes() const { return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes; }
+    size_t table_bytes() const {
+        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (mixed_lengths ? len_hash.size() * sizeof(HashCtx) : 0);
+    }
 
     // domain prefix:  Z_pad || compress(pk) || I2OSP(L,8) || compress(Q1) || compress(H_i).. || api_id
     void rebuild_hash() {
@@ -702,19 +714,35 @@ struct Ctx : bbs_ctx {
         dst.insert(dst.end(), suf, suf + 4);
         dst_too_long = dst.size() > 255;
         if (!dst_too_long) { std::memcpy(h.dst_h2s, dst.data(), dst.size()); h.dst_h2s_len = (uint32_t)dst.size(); }
+        len_hash.clear();
+        len_set.reset();
         if (!(gens_set && pk_set)) { consts_dirty = true; return; }
         domain_midstate(pk, h);
+        if (mixed_lengths) {
+            // every generator is compressed ONCE; prefix l hashes the first l + 1 of them
+            const std::vector<uint8_t> cg = compressed_gens();
+            len_hash.assign((size_t)L + 1, key_hash0());
+            for (int l = 0; l <= L; l++) domain_midstate(pk, len_hash[(size_t)l], l, cg.data());
+        }
         consts_dirty = true;
     }
-    // the key-dependent part of the domain prefix (needs the generators): dom_* of h for key q
-    void domain_midstate(const G2Aff<C>& q, HashCtx& h) const {
+    std::vector<uint8_t> compressed_gens() const {      // compress(Q1) || compress(H_1) || .. || compress(H_L)
+        std::vector<uint8_t> cg(gens.size() * FPB);
+        for (size_t k = 0; k < gens.size(); k++) g1_compress_host<C>(gens[k], cg.data() + k * FPB);
+        return cg;
+    }
+    // the key-dependent part of the domain prefix (needs the generators): dom_* of h for key q and the first l message
+    // generators (l < 0: all L of them); cg: compressed_gens() of the caller, where it builds many prefixes
+    void domain_midstate(const G2Aff<C>& q, HashCtx& h, int l = -1, const uint8_t* cg = nullptr) const {
+        if (l < 0) l = L;
         Sha256 s;
         xmd48_begin(s);
         uint8_t buf[4 * FPB];
         g2_compress<C>(q, buf);
         sha256_bytes(s, buf, 2 * FPB);
-        sha256_u64be(s, (uint64_t)L);
-        for (const auto& g : gens) { g1_compress_host<C>(g, buf); sha256_bytes(s, buf, FPB); }
+        sha256_u64be(s, (uint64_t)l);
+        if (cg) sha256_bytes(s, cg, (uint32_t)((size_t)(l + 1) * FPB));
+        else for (int k = 0; k <= l; k++) { g1_compress_host<C>(gens[(size_t)k], buf); sha256_bytes(s, buf, FPB); }
         sha256_bytes(s, api_id.data(), (uint32_t)api_id.size());
         for (int k = 0; k < 8; k++) h.dom_mid[k] = s.h[k];
         h.dom_mid_total = s.total - s.fill;
@@ -728,6 +756,28 @@ struct Ctx : bbs_ctx {
         hc.tables = d_tables.as<uint32_t>();
         if (rt::h2d(d_consts.p, &hc, sizeof(hc), stream)) return BBS_E_HIP;
         consts_dirty = false;
+        return BBS_OK;
+    }
+
+    int set_mixed_lengths(int enabled) {
+        std::lock_guard<std::mutex> g(mu);
+        if (mixed_lengths == (enabled != 0)) return BBS_OK;
+        mixed_lengths = enabled != 0;
+        rebuild_hash();
+        return BBS_OK;
+    }
+    // the per-length prefixes on the device, for a job that is being created (uploaded once per rebuild_hash)
+    int sync_lengths(std::shared_ptr<const LenSet>& out) {
+        std::lock_guard<std::mutex> g(mu);
+        if (!mixed_lengths || len_hash.empty()) return BBS_E_STATE;
+        if (!len_set) {
+            std::shared_ptr<LenSet> ls(new LenSet());
+            const size_t b = len_hash.size() * sizeof(HashCtx);
+            if (ls->d.alloc(b)) return BBS_E_NOMEM;
+            if (rt::h2d(ls->d.p, len_hash.data(), b, stream)) return BBS_E_HIP;
+            len_set = std::move(ls);
+        }
+        out = len_set;
         return BBS_OK;
     }
 
@@ -978,6 +1028,7 @@ struct JobBase : bbs_job {
     std::vector<std::pair<void*, size_t>> zero_on_reset;   // device arrays cleared before every run (fail closed)
     std::vector<std::unique_ptr<DevBuf>> bufs;
     std::shared_ptr<const void> key_set;     // keyed jobs: the context's key set at upload (released after the streams synchronised)
+    std::shared_ptr<const void> len_set;     // mixed-length jobs: the context's per-length domain prefixes at upload (likewise)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};
     rt::Event ev_fork[bbs_job::N_AUX]{}, ev_join[bbs_job::N_AUX]{};
@@ -1370,4 +1421,22 @@ void add_keyed_pairing_stages(J* j, KeyedJob<C>* kj, const PairArgs<C>* pa, int 
         return rt::launch<PairDistKeyed<C>>(aux ? j->stream_aux() : j->stream(), kj->pair, ((kj->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64);
     }, aux, 0});
 #endif
+}
+
+// =============================================================================================
+// mixed-length jobs (bbs_ctx_set_mixed_lengths): the per-item length array and the context's prefixes per length
+// =============================================================================================
+struct MixedJob {
+    const HashCtx* pref = nullptr;           // [L + 1] domain prefix of length l (the context's LenSet, held by the job)
+    uint32_t* len = nullptr;                 // [n] written by the ingest stage
+};
+template <class C, class J>
+int mixed_bind(J* j, Ctx<C>* ctx, size_t nn, MixedJob& mx) {
+    std::shared_ptr<const typename Ctx<C>::LenSet> ls;
+    if (const int rc = ctx->sync_lengths(ls)) return rc;
+    j->len_set = ls;
+    mx.pref = ls->d.template as<HashCtx>();
+    int rc = BBS_OK;
+    mx.len = j->template scratch<uint32_t>(nn, rc);
+    return rc;
 }

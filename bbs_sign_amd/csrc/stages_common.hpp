@@ -146,6 +146,20 @@ BBS_HD void g1j_store(uint32_t* base, size_t n, size_t i, const G1Jac<C>& p) {
     soa_st<N>(base + (size_t)2 * N * n, n, i, p.z.v);
 }
 
+// ---- mixed message counts (bbs_ctx_set_mixed_lengths) -----------------------------------------
+// The stages of a mixed-length job take the arguments of their fixed-length neighbours plus the job's per-item length array
+// (written by the ingest stage: the item's count l <= L, 0 for an item that is decided before or by the length check) and,
+// for the scalar stage, the context's domain prefixes per length (runtime.hpp LenSet).
+template <class A>
+struct MixedIngestArgs { A a; uint32_t* len; };
+template <class A>
+struct MixedScalarArgs { A a; const HashCtx* pref; const uint32_t* len; };   // pref: [L + 1]
+// the scalars of the bases H_{l+1} .. H_L of an item with l messages: written as zero, never assumed
+BBS_HD void mixed_zero_scalars(uint32_t* fscal, size_t n, size_t i, int l, int L) {
+    const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = l; j < L; j++) soa_st<8>(fscal + (size_t)(2 + j) * 8 * n, n, i, z);
+}
+
 // ---- hashing helpers ------------------------------------------------------------------------
 // ark-serialize compressed G1 absorbed into a hash (core_utilities.rs:39-47, proof_gen.rs:304-311)
 template <class C>

@@ -64,9 +64,11 @@ struct PvIngestArgs {
     int8_t* status0;                      // ST_PENDING or the reference's Err / panic / a non-canonical input
 };
 
-template <class C>
-struct PvIngest {
-    static __host__ __device__ void run(const PvIngestArgs<C>& a, size_t i) {
+// MIXED (bbs_ctx_set_mixed_lengths, PvIngestMixed below): the item's own count l = commitments + disclosed indexes may be
+// anything in 0 .. L and is recorded in len[i]; every check is made against l as before, only l != L becomes l > L
+template <class C, bool MIXED>
+struct PvIngestBody {
+    static BBS_HD void run(const PvIngestArgs<C>& a, size_t i, uint32_t* len) {
         using P = typename C::FpP;
         using R = typename C::FrP;
         constexpr int NC = P::NC;
@@ -78,6 +80,7 @@ struct PvIngest {
         a.ph_len[i] = (uint32_t)(a.ph_off64[i + 1] - a.ph_off64[i]);
         const uint64_t u = a.cm_off[i + 1] - a.cm_off[i], r = a.di_off[i + 1] - a.di_off[i], rm = a.dm_off[i + 1] - a.dm_off[i];
         const uint64_t l = u + r;
+        if constexpr (MIXED) len[i] = l > (uint64_t)a.L ? 0u : (uint32_t)l;
         const uint64_t* idx = a.di + a.di_off[i];
         const int MW = ((a.L > 1 ? a.L : 1) + 31) / 32;
         for (int w = 0; w < MW; w++) a.dmask[(size_t)w * n + i] = 0;
@@ -87,7 +90,7 @@ struct PvIngest {
         for (uint64_t k = 0; k < r; k++) bad |= idx[k] >= l;
         if (bad) st = -3;                                      // InvalidDisclosedIndex
         else if (rm != r) st = -6;                             // InvalidIndicesAndMessagesLength
-        else if (l != (uint64_t)a.L) st = -1;                  // InvalidMessageAndGeneratorsLength
+        else if (MIXED ? l > (uint64_t)a.L : l != (uint64_t)a.L) st = -1;   // InvalidMessageAndGeneratorsLength
         else if (a.dst_too_long) st = -23;
         else {
             // duplicates make the undisclosed set larger than `commitments`: the reference indexes
@@ -139,11 +142,19 @@ struct PvIngest {
         a.status0[i] = ok ? ST_PENDING : (int8_t)-40;
     }
 };
+template <class C>
+struct PvIngest {
+    static __host__ __device__ void run(const PvIngestArgs<C>& a, size_t i) { PvIngestBody<C, false>::run(a, i, nullptr); }
+};
+template <class C>
+struct PvIngestMixed {
+    static __host__ __device__ void run(const MixedIngestArgs<PvIngestArgs<C>>& m, size_t i) { PvIngestBody<C, true>::run(m.a, i, m.len); }
+};
 
 // stage 1 (lane per item): domain, fixed-base scalars.  h: the domain prefix of the item's key (the context's, or its key-set
-// entry in a keyed job: keyed.hpp PvScalarsKeyed)
+// entry in a keyed job: keyed.hpp PvScalarsKeyed); l: the item's message count (a.L unless the job is a mixed-length one)
 template <class C>
-BBS_HD void pv_scalars_item(const PvArgs<C>& a, size_t i, const HashCtx& h) {
+BBS_HD void pv_scalars_item(const PvArgs<C>& a, size_t i, const HashCtx& h, int l) {
     using R = typename C::FrP;
     const size_t n = a.n;
     Fr<C> dom = domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
@@ -155,7 +166,7 @@ BBS_HD void pv_scalars_item(const PvArgs<C>& a, size_t i, const HashCtx& h) {
     // Q1 * (domain * c) : mont_mul(dom_mont, c_canon) = dom*c canonical... dom is Montgomery:
     Fr<C> dc = fe_mul<R>(dom, c_canon);                 // (dom*R)*c/R = dom*c canonical
     soa_st<8>(a.fscal + (size_t)1 * 8 * n, n, i, dc.v);
-    for (int j = 0; j < a.L; j++) {
+    for (int j = 0; j < l; j++) {
         Fr<C> s = fr_load_canon<C>(a.slots + (size_t)j * 8 * n, n, i);
         const uint32_t m = a.dmask[(size_t)(j >> 5) * n + i];
         if ((m >> (j & 31)) & 1u) s = fe_mul<R>(c_m, s);    // (c*R)*m/R = c*m canonical
@@ -166,7 +177,21 @@ template <class C>
 struct PvScalars {
     static __host__ __device__ void run(const PvArgs<C>& a, size_t i) {
         if (a.status[i] != ST_PENDING) return;
-        pv_scalars_item<C>(a, i, a.cc->hash);
+        pv_scalars_item<C>(a, i, a.cc->hash, a.L);
+    }
+};
+// Mixed lengths (bbs_ctx_set_mixed_lengths): item i has its own count l = len[i] <= L.  Its domain starts from the prefix of
+// ITS length (pref[l]: the context keeps one midstate per length, runtime.hpp LenSet), its scalars fill fscal[2 .. 2 + l) and
+// the scalars of the bases H_{l+1} .. H_L are WRITTEN as zero (the buffers come from the pools and hold anything): a zero
+// scalar biased by K has the digit 0 in every window (fixed_digit), so the fixed-base kernels add nothing for those bases and
+// run unchanged.  DESIGN.md 8 "Mixed message counts".
+template <class C>
+struct PvScalarsMixed {
+    static __host__ __device__ void run(const MixedScalarArgs<PvArgs<C>>& m, size_t i) {
+        if (m.a.status[i] != ST_PENDING) return;
+        const int l = (int)m.len[i];
+        pv_scalars_item<C>(m.a, i, m.pref[l], l);
+        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
     }
 };
 

@@ -44,15 +44,18 @@ struct VfIngestArgs {
     uint32_t *sig_a, *sig_e, *msgs, *hdr_off, *hdr_len;
     int8_t* status0;
 };
-template <class C>
-struct VfIngest {
-    static __host__ __device__ void run(const VfIngestArgs<C>& a, size_t i) {
+// MIXED (bbs_ctx_set_mixed_lengths, VfIngestMixed below; has_sig = 1 only): the item's own message count l may be anything in
+// 0 .. L and is recorded in len[i]; l != L becomes l > L, nothing else changes
+template <class C, bool MIXED>
+struct VfIngestBody {
+    static BBS_HD void run(const VfIngestArgs<C>& a, size_t i, uint32_t* len) {
         using P = typename C::FpP;
         using R = typename C::FrP;
         constexpr int NC = P::NC;
         const size_t n = a.n;
         a.hdr_off[i] = (uint32_t)a.hdr_off64[i];
         a.hdr_len[i] = (uint32_t)(a.hdr_off64[i + 1] - a.hdr_off64[i]);
+        if constexpr (MIXED) len[i] = 0;
         if (a.has_sig && a.oct) {
             // the verdicts of bbs_signature_from_octets come first, in its order: the point's code, the identity, e >= r,
             // e = 0; only a decodable signature reaches core_verify's own checks
@@ -78,7 +81,8 @@ struct VfIngest {
         const uint64_t l = a.m_off[i + 1] - a.m_off[i];
         // raw-message form: msg_to_scalars runs first in the reference's public functions (sign.rs:45, verify.rs:32)
         if (a.msg_dst_too_long && l > 0) { a.status0[i] = -23; return; }
-        if (l != (uint64_t)a.L) { a.status0[i] = -1; return; }            // InvalidMessageAndGeneratorsLength
+        if (MIXED ? l > (uint64_t)a.L : l != (uint64_t)a.L) { a.status0[i] = -1; return; }   // InvalidMessageAndGeneratorsLength
+        if constexpr (MIXED) len[i] = (uint32_t)l;
         if (a.dst_too_long) { a.status0[i] = -23; return; }
         bool ok = true;
         if (a.has_sig && !a.oct) {
@@ -104,10 +108,18 @@ struct VfIngest {
         a.status0[i] = ok ? ST_PENDING : (int8_t)-40;
     }
 };
-
-// h: the domain prefix of the item's key (as pv_scalars_item)
 template <class C>
-BBS_HD void vf_scalars_item(const VfArgs<C>& a, size_t i, const HashCtx& h) {
+struct VfIngest {
+    static __host__ __device__ void run(const VfIngestArgs<C>& a, size_t i) { VfIngestBody<C, false>::run(a, i, nullptr); }
+};
+template <class C>
+struct VfIngestMixed {
+    static __host__ __device__ void run(const MixedIngestArgs<VfIngestArgs<C>>& m, size_t i) { VfIngestBody<C, true>::run(m.a, i, m.len); }
+};
+
+// h: the domain prefix of the item's key (as pv_scalars_item); l: the item's message count (as pv_scalars_item)
+template <class C>
+BBS_HD void vf_scalars_item(const VfArgs<C>& a, size_t i, const HashCtx& h, int l) {
     using R = typename C::FrP;
     const size_t n = a.n;
     Fr<C> dom = fe_to_canonical<R>(domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]));
@@ -115,7 +127,7 @@ BBS_HD void vf_scalars_item(const VfArgs<C>& a, size_t i, const HashCtx& h) {
     one.v[0] = 1;
     soa_st<8>(a.fscal, n, i, one.v);
     soa_st<8>(a.fscal + (size_t)8 * n, n, i, dom.v);
-    for (int j = 0; j < a.L; j++) {
+    for (int j = 0; j < l; j++) {
         uint32_t m[8];
         soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
         soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, m);
@@ -125,7 +137,18 @@ template <class C>
 struct VfScalars {
     static __host__ __device__ void run(const VfArgs<C>& a, size_t i) {
         if (a.status[i] != ST_PENDING) return;
-        vf_scalars_item<C>(a, i, a.cc->hash);
+        vf_scalars_item<C>(a, i, a.cc->hash, a.L);
+    }
+};
+// mixed lengths (bbs_ctx_set_mixed_lengths): as PvScalarsMixed (stages_pv.hpp) -- the prefix of the item's own length, its l
+// messages, and zeros WRITTEN for the bases behind them
+template <class C>
+struct VfScalarsMixed {
+    static __host__ __device__ void run(const MixedScalarArgs<VfArgs<C>>& m, size_t i) {
+        if (m.a.status[i] != ST_PENDING) return;
+        const int l = (int)m.len[i];
+        vf_scalars_item<C>(m.a, i, m.pref[l], l);
+        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
     }
 };
 

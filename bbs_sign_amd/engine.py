@@ -386,6 +386,11 @@ class Engine:
         """bbs_ctx_set_points_in_subgroup: the caller vouches that every G1 input is in the prime-order subgroup."""
         self._chk(self.lib.bbs_ctx_set_points_in_subgroup(self.h, 1 if vouched else 0), "bbs_ctx_set_points_in_subgroup")
 
+    def set_mixed_lengths(self, on: bool):
+        """bbs_ctx_set_mixed_lengths: the single-key verify / proof_verify batches of this engine accept items of any message
+        count 0 .. L, each decided as a context made for its own count would (jobs created afterwards)."""
+        self._chk(self.lib.bbs_ctx_set_mixed_lengths(self.h, 1 if on else 0), "bbs_ctx_set_mixed_lengths")
+
     def set_fixed_base_tree(self, enabled: bool):
         """bbs_ctx_set_fixed_base_tree: fixed-base sums as one tree of affine additions per item (jobs created afterwards)."""
         self._chk(self.lib.bbs_ctx_set_fixed_base_tree(self.h, 1 if enabled else 0), "bbs_ctx_set_fixed_base_tree")

@@ -135,7 +135,8 @@ size_t bbs_device_free_bytes(int device_id);          /* device memory free righ
 
 int bbs_ctx_create(int curve, int device_id, bbs_ctx** out);
 void bbs_ctx_destroy(bbs_ctx* ctx);
-/* device memory of the context's tables (fixed-base window tables, line tables, constants), in bytes */
+/* device memory of the context's tables (fixed-base window tables, line tables, constants, and the per-length domain
+ * prefixes of bbs_ctx_set_mixed_lengths), in bytes */
 size_t bbs_ctx_table_bytes(const bbs_ctx* ctx);
 
 /* window width (bits) of the fixed-base tables, 4..22, or 0 (THE DEFAULT) = chosen at bbs_ctx_set_generators from the
@@ -183,6 +184,22 @@ int bbs_ctx_set_latency_mode(bbs_ctx* ctx, int enabled);
  * form it is not faster (measured); today it covers proof_verify and bbs_g1_msm_batch.  Applies to jobs
  * created afterwards. */
 int bbs_ctx_set_fixed_base_tree(bbs_ctx* ctx, int enabled);
+/* Mixed message counts on ONE context (off by default; with it off nothing changes anywhere).  The reference picks its
+ * generators by the item's own length on every call (create_generators of messages.len + 1, src/verify.rs:30-35; of
+ * commitments + disclosed indexes + 1, src/proof_verify.rs:40-43), and generator i does not depend on the count: the
+ * tables of a context with L message generators contain those of every shorter length.  enabled = 1: every SINGLE-KEY verify
+ * and proof_verify entry point of the context -- core, octets and wire forms; _upload, _submit and _batch -- accepts item i
+ * with its own count l_i, 0 <= l_i <= L (verify: its messages; proof_verify: its commitments + disclosed indexes).  The
+ * status of item i is exactly what a context made with generators[0 .. l_i] (same key, api_id and modes) gives that item
+ * alone: the checks and their order are unchanged, only "l != L" becomes "l > L" (still -1); -3, -6, -22, -23, -40, -41 and
+ * -42 are decided against the item's own l_i.  Composes with both job forms, batch verification, subgroup vouching, the
+ * fixed-base tree and every window width.  Costs L + 1 domain prefixes (about 370 bytes each) of device memory, counted in
+ * bbs_ctx_table_bytes, rebuilt by bbs_ctx_set_generators and the key setters.  Applies to jobs created afterwards; a job keeps
+ * what it was created with.
+ * NOT covered: the keyed entry points of a context with the switch on return BBS_E_STATE and enqueue nothing (a prefix per
+ * (key, length) pair is a follow-up); sign and proof_gen are unchanged and keep deciding l != L as -1 whatever the switch
+ * says; bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
+int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
 
 /* Batch verification for core_proof_verify and core_verify (off by default).  When enabled, the n two-pairing
  * products of a batch (src/proof_verify.rs:112-115, src/verify.rs:88-92) are replaced by 16 products over random

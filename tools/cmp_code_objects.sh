@@ -2,7 +2,8 @@
 # compare the gfx950 code objects of two builds of the library: tools/cmp_code_objects.sh <libA.so> <libB.so>
 #   per code object: .text, .rodata, the symbol table (without the __hip_cuid_<hash> marker) and the llvm-objdump -d output
 #   per kernel     : code size, VGPR, AGPR, SGPR, private-segment (scratch) and LDS bytes from the metadata notes of both
-#                    libraries, every difference flagged; the set of kernel symbols; the largest scratch of each library
+#                    libraries, every difference flagged (a kernel of one library only: its own figures); the set of kernel
+#                    symbols; the largest scratch of each library
 # exit status 0: every code object identical; 1: something differs (resources or bytes); 2: usage / tool failure
 set -e -o pipefail
 [ $# -eq 2 ] || { echo "usage: $0 <libA.so> <libB.so>" >&2; exit 2; }
@@ -99,7 +100,10 @@ for k in range(min(na, nb)):
     differ |= not all(same.values())
     for name in sorted(set(ka) | set(kb)):
         if name not in ka or name not in kb:
+            v = [int((ka.get(name) or kb[name]).get(f, -1)) for _, f in FIELDS]
+            max_scr[0 if name in ka else 1] = max(max_scr[0 if name in ka else 1], v[4])
             print('  ONLY IN %s: %s' % ('A' if name in ka else 'B', name))
+            print('  %-64s %s' % ('', ' '.join('%s=%d' % (lab, x) for (lab, _), x in zip(FIELDS, v))))
             differ = True
             continue
         va = [int(ka[name].get(f, -1)) for _, f in FIELDS]
