@@ -82,6 +82,9 @@ def clear_caches():
     for e in _eng_cache.values():
         e.close()
     _eng_cache.clear()
+    for e in _issuer_cache.values():
+        e.eng.close()
+    _issuer_cache.clear()
     _gen_cache.clear()
 
 
@@ -233,14 +236,15 @@ def _mixed_engine(pk: PublicKey, L: int) -> Engine:
     return eng
 
 
-def _many(items, to_octets, run):
-    """Shared tail of verify_many / proof_verify_many: items whose object cannot be written as octets keep the codec's
-    BbsError, the others run in ONE device call; statuses become booleans or BbsError objects."""
+def _many(items, to_octets, run, at=0):
+    """Shared tail of verify_many / proof_verify_many (and the *_many_issuers forms, whose object is entry 1 of an item): items
+    whose object cannot be written as octets keep the codec's BbsError, the others run in ONE device call; statuses become
+    booleans or BbsError objects."""
     out: list = [None] * len(items)
     octs, idx = [], []
     for i, it in enumerate(items):
         try:
-            octs.append(to_octets(it[0]))
+            octs.append(to_octets(it[at]))
             idx.append(i)
         except BbsError as e:
             out[i] = e
@@ -270,6 +274,95 @@ def proof_verify_many(pk: PublicKey, items: Sequence[tuple]) -> list:
     return _many(items, lambda proof: proof_to_octets(pk.curve, proof, pk.lib_path),
                  lambda octs, its: eng.proof_verify_wire_batch(octs, [list(it[3]) for it in its], [list(it[4]) for it in its],
                                                                [it[1] for it in its], [it[2] for it in its]))
+
+
+# ------------------------------------------------------------------ many items, any issuers, any lengths
+class _IssuerEngine:
+    """One engine per (curve, device, lib_path) with bbs_ctx_set_keyed_mixed_lengths on: made for the largest count seen, its
+    key set grows by appending and a key is registered once (``index``: key -> its index in the set)."""
+
+    def __init__(self, curve, device, lib_path, L, keys=()):
+        self.L = L
+        self.index: Dict[object, int] = {}
+        self.eng = Engine(curve, device=device, lib_path=lib_path, window_bits=4 if lib_path is not None else None)
+        self.eng.set_generators(create_generators(curve, L + 1, lib_path), api_id(curve))
+        self.eng.set_keyed_mixed_lengths(True)
+        self.register(keys)
+
+    @staticmethod
+    def name(pk):
+        return None if pk is None else tuple(map(tuple, pk))
+
+    def register(self, pks):
+        """Appends the keys that are not in the set yet (in one call); returns nothing: ``index`` has them afterwards.  A key
+        the library refuses keeps its index -- its items get BBS_ST_UNKNOWN_KEY, as the keyed entry points decide them."""
+        new, seen = [], set()
+        for pk in pks:
+            if self.name(pk) not in self.index and self.name(pk) not in seen:
+                new.append(pk)
+                seen.add(self.name(pk))
+        if new:
+            first, _ = self.eng.add_public_keys(new)
+            for k, pk in enumerate(new):
+                self.index[self.name(pk)] = first + k
+
+    def keys_in_order(self):
+        by_index = sorted(self.index.items(), key=lambda kv: kv[1])
+        return [None if name is None else tuple(name) for name, _ in by_index]
+
+
+_issuer_cache: Dict[tuple, _IssuerEngine] = {}
+
+
+def _issuer_engine(curve, device, lib_path, L, pks) -> _IssuerEngine:
+    """The cached keyed engine of (curve, device, lib_path), made for L messages or more, with ``pks`` registered.  A list that
+    needs a larger L replaces the engine -- its keys are registered again, in their order -- as _mixed_engine replaces shorter
+    engines."""
+    who = (curve, device, lib_path)
+    ie = _issuer_cache.get(who)
+    if ie is None or ie.L < L:
+        old = ie.keys_in_order() if ie is not None else []
+        if ie is not None:
+            _issuer_cache.pop(who).eng.close()
+        ie = _issuer_cache[who] = _IssuerEngine(curve, device, lib_path, L, old)
+    ie.register(pks)
+    return ie
+
+
+def _many_issuers(items, count, to_octets, run):
+    """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms."""
+    out: list = [None] * len(items)
+    groups: Dict[tuple, List[int]] = {}
+    for i, it in enumerate(items):
+        groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
+    for (curve, device, lib_path), idx in groups.items():
+        its = [items[i] for i in idx]
+        ie = _issuer_engine(curve, device, lib_path, max(count(it) for it in its), [it[0].pk for it in its])
+        got = _many(its, lambda obj: to_octets(curve, obj, lib_path),
+                    lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
+        for i, g in zip(idx, got):
+            out[i] = g
+    return out
+
+
+def verify_many_issuers(items: Sequence[tuple]) -> list:
+    """PublicKey.verify for many items ``(pk, signature, header, messages)`` of ANY issuers and ANY message counts, in ONE
+    device call per (curve, device, lib_path): one cached engine with bbs_ctx_set_keyed_mixed_lengths on, whose L is the
+    largest count seen and whose key set grows by appending (a key is registered once).  Entry i is the boolean
+    ``items[i][0].verify(*items[i][1:])`` returns, or the BbsError it raises (returned, not raised: the other items stand).
+    One divergence: a ``pk`` the library refuses (not on the twist or outside the subgroup -- octets_to_public_key never returns
+    one) is registered as a refused key, and its items get ``BbsError(-44)`` (BBS_ST_UNKNOWN_KEY), where the one-item form
+    fails with a BbsRuntimeError from bbs_ctx_set_public_key."""
+    return _many_issuers(items, lambda it: len(it[3]), signature_to_octets,
+                         lambda eng, kidx, octs, its: eng.verify_wire_keyed_batch(kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]))
+
+
+def proof_verify_many_issuers(items: Sequence[tuple]) -> list:
+    """proof_verify for many items ``(pk, proof, header, ph, disclosed_messages, disclosed_indexes)`` of any issuers and any
+    message counts (commitments + disclosed indexes each), as verify_many_issuers."""
+    return _many_issuers(items, lambda it: len(it[1].commitments) + len(it[5]), proof_to_octets,
+                         lambda eng, kidx, octs, its: eng.proof_verify_wire_keyed_batch(
+                             kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]))
 
 
 # ---------------------------------------------------------------------------------- wire codec

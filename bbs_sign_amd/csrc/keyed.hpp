@@ -54,6 +54,35 @@ struct VfScalarsKeyed {
     }
 };
 
+// Keyed jobs of mixed message counts (bbs_ctx_set_keyed_mixed_lengths): item i under its own key kidx[i] with its own count
+// len[i] <= L (written by the MIXED ingest bodies, which such a job launches where a keyed job launches the fixed-length ones;
+// KeyGate follows unchanged).  The domain starts from the prefix of THAT key and THAT length, pref[kidx * stride + l] (runtime.hpp
+// KeyLenSet, stride = L + 1), the scalars of the bases H_{l+1} .. H_L are written as zero as in PvScalarsMixed.  Everything
+// downstream takes either axis unchanged.  The arguments wrap the existing structs: no other kernel's argument layout changes.
+// Only a pending item is looked at: KEY_NONE (decided by KeyGate) and l > L (decided at ingest, len = 0) never index anything.
+// The index diverges per lane, so the 368 bytes of the HashCtx are read with vector loads through a per-lane pointer -- the
+// struct is passed on by reference, as PvScalarsKeyed does, never copied into a local (368 B of scratch per lane).
+template <class C, class A>
+struct KeyedMixedScalarArgs { A a; const HashCtx* pref; uint32_t stride; const uint32_t* kidx; const uint32_t* len; };
+template <class C>
+struct PvScalarsKeyedMixed {
+    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, PvArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        const int l = (int)k.len[i];
+        pv_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
+        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
+    }
+};
+template <class C>
+struct VfScalarsKeyedMixed {
+    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, VfArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        const int l = (int)k.len[i];
+        vf_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
+        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
+    }
+};
+
 // the keyed pairing step: e(Pa, W_key(i)) * e(+-Pb, BP2) == 1 for the items of the slots [0, n_slots)
 template <class C>
 struct PairKeyedArgs {

@@ -9,7 +9,8 @@
 // of every registration call (runtime.hpp KEY_BUILD_ON_DEVICE).  e is filled completely (zero behind the lines); the status is the stage's.  The line
 // entries are stored as the representatives in [0, p), as the stage stores them.
 template <class C>
-int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out) const {
+int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out,
+                              G2Aff<C>* q_out) const {
     using P = typename C::FpP;
     std::memset(&e, 0, sizeof(e));
     e.hash = key_hash0();
@@ -34,6 +35,7 @@ int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oc
     }
     for (int s = 0; s < e.tab.n_lines; s++) { e.tab.e[s].c = f2_canon<C>(e.tab.e[s].c); e.tab.e[s].nl = f2_canon<C>(e.tab.e[s].nl); }
     domain_midstate(q, e.hash);
+    if (q_out) *q_out = q;
     if (oct) {
         if (inf_out) *inf_out = q.inf ? 1 : 0;
         if (rec_out && !q.inf) {
@@ -48,13 +50,14 @@ int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oc
 // Synchronises the context's stream.  status / rec_out / inf_out: host arrays, the last two may be null.
 template <class C>
 int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
-                      int8_t* status, uint8_t* rec_out, int8_t* inf_out) {
+                      int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out) {
     if (!n) return BBS_OK;
+    if (q_out && on_device) return BBS_E_STATE;         // the host copies of the keys come from the host path only
     if (!on_device) {
         std::vector<KeyEntry<C>> host(n);
         auto one = [&](size_t k) {
             status[k] = host_key_entry(rec ? rec + k * 4 * FPB : nullptr, !oct && is_inf && is_inf[k] != 0, oct ? oct + k * 2 * FPB : nullptr,
-                                       host[k], rec_out ? rec_out + k * 4 * FPB : nullptr, inf_out ? inf_out + k : nullptr);
+                                       host[k], rec_out ? rec_out + k * 4 * FPB : nullptr, inf_out ? inf_out + k : nullptr, q_out ? q_out + k : nullptr);
         };
         const size_t nt = std::min<size_t>({(size_t)16, n, (size_t)std::max(1u, std::thread::hardware_concurrency())});
         if (nt <= 1) { for (size_t k = 0; k < n; k++) one(k); }
@@ -128,19 +131,82 @@ int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* i
     std::shared_ptr<KeySet> ks(new KeySet());
     ks->n = n_old + n;
     ks->status.assign(ks->n, (int8_t)BBS_ST_NOT_ON_CURVE);
+    {
+        G2Aff<C> id{};
+        id.inf = true; id.x = f2_zero<C>(); id.y = f2_zero<C>();
+        ks->pk.assign(ks->n, id);
+    }
     if (ks->d.alloc(ks->n * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
     if (n_old) {
         std::copy(old->status.begin(), old->status.end(), ks->status.begin());
+        std::copy(old->pk.begin(), old->pk.end(), ks->pk.begin());
         if (rt::d2d_async(ks->d.p, old->d.p, n_old * sizeof(KeyEntry<C>), stream)) return BBS_E_HIP;
     }
     if (const int rc = key_build(ks->d.template as<KeyEntry<C>>() + n_old, n, rec, is_inf, oct, KEY_BUILD_ON_DEVICE,
-                                 ks->status.data() + n_old, rec_out, inf_out)) {
+                                 ks->status.data() + n_old, rec_out, inf_out, KEY_BUILD_ON_DEVICE ? nullptr : ks->pk.data() + n_old)) {
         (void)rt::sync(stream);      // (the copy of the old entries must not outlive the buffer it writes)
         return rc;
     }
+    static_assert(!KEY_BUILD_ON_DEVICE, "KeySet::pk is filled by the host path: decode the keys here before KeyBuild registers them");
+    // keyed jobs of mixed counts: the rows of the old keys are copied, only the n new keys are hashed; a failure leaves the old
+    // set and its rows
+    std::shared_ptr<const KeyLenSet> kl;
+    if (keyed_mixed_lengths) {
+        const std::shared_ptr<const KeySet> cks = ks;
+        const std::shared_ptr<const KeyLenSet> okl = key_lens;
+        const bool reuse = n_old && okl && okl->of.get() == old.get() && okl->stride == (size_t)L + 1;
+        if (const int rc = build_key_lens(cks, reuse ? okl : nullptr, reuse ? n_old : 0, kl)) return rc;
+    }
+    key_lens = kl;
     if (key_status) std::memcpy(key_status, ks->status.data() + n_old, n);
     if (first_index) *first_index = (uint32_t)n_old;
     keys = std::move(ks);
+    return BBS_OK;
+}
+
+// The prefixes per (key, length) of the keys [n_old, ks->n) on up to 16 host threads (the generators are compressed once), the
+// rows [0, n_old) copied device to device from `old`; one upload; synchronises the context's stream.  Registration-time work:
+// no device kernel, as key_build's host path (DESIGN.md 8 "Registration").
+template <class C>
+int Ctx<C>::build_key_lens(const std::shared_ptr<const KeySet>& ks, const std::shared_ptr<const KeyLenSet>& old, size_t n_old,
+                           std::shared_ptr<const KeyLenSet>& out) {
+    if (use()) return BBS_E_HIP;
+    std::shared_ptr<KeyLenSet> kl(new KeyLenSet());
+    kl->of = ks;
+    kl->stride = (size_t)L + 1;
+    const size_t S = kl->stride, n_new = ks->n - n_old;
+    if (kl->d.alloc(ks->n * S * sizeof(HashCtx))) return BBS_E_NOMEM;
+    if (n_old && rt::d2d_async(kl->d.p, old->d.p, n_old * S * sizeof(HashCtx), stream)) return BBS_E_HIP;
+    std::vector<HashCtx> host(n_new * S, key_hash0());
+    const std::vector<uint8_t> cg = compressed_gens();
+    auto one = [&](size_t k) {
+        if (ks->status[n_old + k] != 1) return;
+        for (size_t l = 0; l < S; l++) domain_midstate(ks->pk[n_old + k], host[k * S + l], (int)l, cg.data());
+    };
+    const size_t nt = std::min<size_t>({(size_t)16, n_new, (size_t)std::max(1u, std::thread::hardware_concurrency())});
+    if (nt <= 1) { for (size_t k = 0; k < n_new; k++) one(k); }
+    else {
+        std::vector<std::thread> th;
+        for (size_t t = 0; t < nt; t++) th.emplace_back([&, t]() { for (size_t k = t; k < n_new; k += nt) one(k); });
+        for (auto& x : th) x.join();
+    }
+    const bool bad = n_new && rt::h2d(kl->d.template as<HashCtx>() + n_old * S, host.data(), host.size() * sizeof(HashCtx), stream);
+    if (rt::sync(stream) || bad) return BBS_E_HIP;      // (the copy of the old rows must not outlive the buffer it writes)
+    out = std::move(kl);
+    return BBS_OK;
+}
+
+template <class C>
+int Ctx<C>::set_keyed_mixed_lengths(int enabled) {
+    std::lock_guard<std::mutex> g(mu);
+    if (keyed_mixed_lengths == (enabled != 0)) return BBS_OK;
+    if (!enabled) { keyed_mixed_lengths = false; key_lens.reset(); return BBS_OK; }
+    std::shared_ptr<const KeyLenSet> kl;
+    if (const auto ks = keys) {
+        if (const int rc = build_key_lens(ks, nullptr, 0, kl)) return rc;       // (the switch stays off)
+    }
+    key_lens = kl;
+    keyed_mixed_lengths = true;
     return BBS_OK;
 }
 

@@ -24,7 +24,7 @@ struct PvJob : JobBase<C> {
     MsgHashArgs mh{};                 // wire form with raw messages only
     BvState<C> bv{};                  // batch verification only
     KeyedJob<C> kj{};                 // keyed form only
-    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths)
+    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths, bbs_ctx_set_keyed_mixed_lengths)
 };
 
 // the form is deduced from the fields of PvIn that are set (ops_decl.hpp)
@@ -38,9 +38,14 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;        // internal limbs
     constexpr int NC = C::FpP::NC;      // canonical 32-bit words
     constexpr int FPB = 4 * NC;
+    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
+    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
+    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
     if constexpr (KEYED) {
-        if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
-        if (ctx->mixed_lengths) return BBS_E_STATE;       // a prefix per (key, length) is not built: keyed.hpp
+        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
+        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
+        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
+        if (ctx->mixed_lengths && !keyed_mixed) return BBS_E_STATE;
         if (n && !in.key_index) return BBS_E_ARG;
     } else {
         if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
@@ -58,6 +63,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
     // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
     const bool mixed = !KEYED && ctx->mixed_lengths;
+    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED ingest bodies serve both
     // ---- the batch as one staging image in page-locked memory, one asynchronous copy; everything else (the
     // reference's checks, range checks, unpacking, the SoA transposition) happens on the device: stage PvIngest
     // first ragged section: the commitments (core form) or the proof octet strings (wire form)
@@ -115,6 +121,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     if (rc) return rc;
     job->zero_on_reset.push_back({pair_ok, nn});          // a pairing lane that never ran reads as "product != 1"
     if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
     if (!wire) {
         PvIngestArgs<C>& ia = job->ingest;
         ia.n = n; ia.L = L; ia.dst_too_long = ctx->dst_too_long ? 1 : 0;
@@ -125,10 +132,8 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         ia.pts = pts; ia.sc = sc; ia.slots = slots; ia.dmask = dmask; ia.didx = didx_s; ia.rcount = rcount;
         ia.hdr_off = offs; ia.hdr_len = offs + nn; ia.ph_off = offs + 2 * nn; ia.ph_len = offs + 3 * nn;
         ia.status0 = job->d_status0.template as<int8_t>();
-        if constexpr (!KEYED) {
-            if (mixed && rt::launch<PvIngestMixed<C>>(job->stream(), MixedIngestArgs<PvIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-        }
-        if (!mixed && rt::launch<PvIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+        if (mixed_ingest && rt::launch<PvIngestMixed<C>>(job->stream(), MixedIngestArgs<PvIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+        if (!mixed_ingest && rt::launch<PvIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
     } else {
         PvOctArgs<C>& oa = job->oct;
         oa.n = n; oa.L = L; oa.dst_too_long = ctx->dst_too_long ? 1 : 0;
@@ -147,10 +152,8 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         if (rc) return rc;
         oa.status0 = job->d_status0.template as<int8_t>();
         if (rt::launch<PvOctDecode<C>>(job->stream(), oa, 3 * n)) return BBS_E_HIP;
-        if constexpr (!KEYED) {
-            if (mixed && rt::launch<PvOctIngestMixed<C>>(job->stream(), MixedIngestArgs<PvOctArgs<C>>{oa, job->mx.len}, n)) return BBS_E_HIP;
-        }
-        if (!mixed && rt::launch<PvOctIngest<C>>(job->stream(), oa, n)) return BBS_E_HIP;
+        if (mixed_ingest && rt::launch<PvOctIngestMixed<C>>(job->stream(), MixedIngestArgs<PvOctArgs<C>>{oa, job->mx.len}, n)) return BBS_E_HIP;
+        if (!mixed_ingest && rt::launch<PvOctIngest<C>>(job->stream(), oa, n)) return BBS_E_HIP;
     }
     if constexpr (KEYED) {
         if ((rc = keyed_gate(job.get(), n, job->kj.kidx, job->d_status0.template as<int8_t>()))) return rc;
@@ -176,14 +179,17 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     // compute unit together) on the first side stream from the start; chains that start at the same moment spread a long
     // wavefront over every compute unit first and the bucket workgroups then wait for whole compute units (measured: that
     // kernel 1.3 -> 4.1 ms, the batch 4.8 -> 7.6 ms, profiles/r05_g_single_batch_forms.log).  0.14 ms later they come second.
-    auto msm_chain = [j, mixed](int layout, bool chains_behind_scalars = false) {
+    auto msm_chain = [j, mixed, keyed_mixed](int layout, bool chains_behind_scalars = false) {
         auto chains2 = [j]() { j->stages.push_back({"pv_chains", [j]() { return rt::launch<PvChains<C>>(j->stream_aux(2), j->a, j->n * PvChains<C>::units(j->a)); }, 2, 0}); };
         if (layout == 3) j->stages.push_back({"pv_t1_chain", [j]() { return rt::launch<PvT1Chain<C>>(j->stream_aux(2), j->a, j->n); }, 2, 0});
         if (layout == 2 && !chains_behind_scalars) chains2();
         if (layout == 3) j->stages.push_back({"pv_var_mul", [j]() { return rt::launch<PvVarMul<C>>(j->stream(), j->a, j->n * (size_t)(j->a.nvar - PvVarMul<C>::first_part(j->a))); }});
-        if constexpr (KEYED)
-            j->stages.push_back({"pv_scalars_keyed", [j]() { return rt::launch<PvScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PvArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
-        else if (mixed)
+        if constexpr (KEYED) {
+            if (keyed_mixed)
+                j->stages.push_back({"pv_scalars_keyed_mixed", [j]() { return rt::launch<PvScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, PvArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
+            else
+                j->stages.push_back({"pv_scalars_keyed", [j]() { return rt::launch<PvScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PvArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+        } else if (mixed)
             j->stages.push_back({"pv_scalars_mixed", [j]() { return rt::launch<PvScalarsMixed<C>>(j->stream(), MixedScalarArgs<PvArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
         else
             j->stages.push_back({"pv_scalars", [j]() { return rt::launch<PvScalars<C>>(j->stream(), j->a, j->n); }});

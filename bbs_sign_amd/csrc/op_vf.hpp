@@ -14,7 +14,7 @@ struct VfJob : JobBase<C> {
     MsgHashArgs mh{};                 // raw-message form only
     BvState<C> bv{};                  // batch verification only
     KeyedJob<C> kj{};                 // keyed form only
-    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths)
+    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths, bbs_ctx_set_keyed_mixed_lengths)
 };
 
 // KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
@@ -24,9 +24,14 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
+    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
+    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
+    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
     if constexpr (KEYED) {
-        if (!ctx->gens_set || !ctx->keys) return BBS_E_STATE;
-        if (ctx->mixed_lengths) return BBS_E_STATE;       // a prefix per (key, length) is not built: keyed.hpp
+        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
+        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
+        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
+        if (ctx->mixed_lengths && !keyed_mixed) return BBS_E_STATE;
         if (n && !in.key_index) return BBS_E_ARG;
     } else {
         if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
@@ -98,11 +103,11 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     ia.status0 = job->d_status0.template as<int8_t>();
     // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
     const bool mixed = !KEYED && ctx->mixed_lengths;
+    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED ingest body serves both
     if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if constexpr (!KEYED) {
-        if (mixed && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-    }
-    if (!mixed && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if (mixed_ingest && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+    if (!mixed_ingest && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
     if constexpr (KEYED) {
         if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
     }
@@ -117,9 +122,12 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     // by the dozen and must own ONE hardware queue each (32 in flight: 4.2 M/s on one stream, 3.1 M/s on two).
     const int side = (!KEYED && ctx->batch_verify && !job->latency_form) ? 0 : 1;
     j->stages.push_back({"vf_var_mul", [j, side]() { return rt::launch<VfVarMul<C>>(side ? j->stream_aux(1) : j->stream(), j->a, j->n); }, side, 0});
-    if constexpr (KEYED)
-        j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
-    else if (mixed)
+    if constexpr (KEYED) {
+        if (keyed_mixed)
+            j->stages.push_back({"vf_scalars_keyed_mixed", [j]() { return rt::launch<VfScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, VfArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
+        else
+            j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+    } else if (mixed)
         j->stages.push_back({"vf_scalars_mixed", [j]() { return rt::launch<VfScalarsMixed<C>>(j->stream(), MixedScalarArgs<VfArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
     else
         j->stages.push_back({"vf_scalars", [j]() { return rt::launch<VfScalars<C>>(j->stream(), j->a, j->n); }});

@@ -621,9 +621,25 @@ struct Ctx : bbs_ctx {
     struct KeySet {
         size_t n = 0;
         std::vector<int8_t> status;  // per key: 1 accepted, BBS_ST_NOT_ON_CURVE refused
+        std::vector<G2Aff<C>> pk;    // host copy of every key (a refused key: the identity, never read): what its prefixes per length are hashed from
         DevBuf d;                    // [n] KeyEntry<C>
     };
     std::shared_ptr<const KeySet> keys;
+    // keyed jobs of mixed message counts (bbs_ctx_set_keyed_mixed_lengths): off by default, independent of mixed_lengths below.
+    // On: the keyed verify / proof_verify jobs created from now on accept item i under its own key k_i with its own count
+    // l_i <= L.  The one datum that depends on both is the domain prefix: one HashCtx per (key, length), row k of KeyLenSet =
+    // what rebuild_hash builds per length for the context's own key.  Built EAGERLY on host threads -- by the setter for the
+    // keys that exist, by add_keys for the keys it appends (the old rows are copied device to device) -- so while the switch is
+    // on key_lens always belongs to `keys`.  Immutable once built; a job holds a reference (JobBase::key_len_set).  The rows of a
+    // refused key hold key_hash0() and are never read: KeyGate decides such an item before the scalar stage looks at it.
+    bool keyed_mixed_lengths = false;
+    struct KeyLenSet {
+        std::shared_ptr<const KeySet> of;        // the key set these rows were built for
+        size_t stride = 0;                       // L + 1
+        DevBuf d;                                // [of->n][stride] HashCtx
+    };
+    std::shared_ptr<const KeyLenSet> key_lens;
+    size_t key_lens_bytes() const { const auto kl = key_lens; return keyed_mixed_lengths && kl ? kl->of->n * kl->stride * sizeof(HashCtx) : 0; }
     // mixed message counts (bbs_ctx_set_mixed_lengths): off by default.  On: the single-key verify / proof_verify jobs created
     // from now on accept item i with its own count l_i <= L; the only data of a context that depend on the count are the domain
     // prefixes, one HashCtx per length 0 .. L (prefix l = the first l + 1 generators: create_generators is prefix-consistent).
@@ -702,7 +718,7 @@ struct Ctx : bbs_ctx {
 
     int use() { return rt::set_device(device) ? BBS_E_HIP : BBS_OK; }
     size_t table_bytes() const {
-        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (mixed_lengths ? len_hash.size() * sizeof(HashCtx) : 0);
+        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (mixed_lengths ? len_hash.size() * sizeof(HashCtx) : 0) + key_lens_bytes();
     }
 
     // domain prefix:  Z_pad || compress(pk) || I2OSP(L,8) || compress(Q1) || compress(H_i).. || api_id
@@ -823,14 +839,19 @@ struct Ctx : bbs_ctx {
         h.dst_h2s_len = hc.hash.dst_h2s_len;
         return h;
     }
-    int8_t host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out) const;
+    int8_t host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out,
+                          G2Aff<C>* q_out = nullptr) const;
     int key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
-                  int8_t* status, uint8_t* rec_out, int8_t* inf_out);
+                  int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out = nullptr);
+    // the prefixes per (key, length) of bbs_ctx_set_keyed_mixed_lengths (op_key.hpp)
+    int build_key_lens(const std::shared_ptr<const KeySet>& ks, const std::shared_ptr<const KeyLenSet>& old, size_t n_old,
+                       std::shared_ptr<const KeyLenSet>& out);
+    int set_keyed_mixed_lengths(int enabled);
     int add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, int8_t* key_status,
                  uint8_t* rec_out, int8_t* inf_out, uint32_t* first_index);
     int set_public_keys(size_t n_keys, const uint8_t* b, const int8_t* is_identity, int8_t* key_status) {
         if (n_keys && !b) return BBS_E_ARG;
-        if (!n_keys) { keys.reset(); return BBS_OK; }
+        if (!n_keys) { keys.reset(); key_lens.reset(); return BBS_OK; }
         return add_keys(true, n_keys, b, is_identity, nullptr, key_status, nullptr, nullptr, nullptr);
     }
     size_t public_key_count() const { const auto ks = keys; return ks ? ks->n : 0; }
@@ -1029,6 +1050,7 @@ struct JobBase : bbs_job {
     std::vector<std::unique_ptr<DevBuf>> bufs;
     std::shared_ptr<const void> key_set;     // keyed jobs: the context's key set at upload (released after the streams synchronised)
     std::shared_ptr<const void> len_set;     // mixed-length jobs: the context's per-length domain prefixes at upload (likewise)
+    std::shared_ptr<const void> key_len_set; // keyed jobs of mixed counts: the prefixes per (key, length) at upload (likewise)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};
     rt::Event ev_fork[bbs_job::N_AUX]{}, ev_join[bbs_job::N_AUX]{};
@@ -1362,7 +1384,7 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJo
     constexpr uint32_t W = (uint32_t)KEY_SLOTS_PER_WAVE;
     const auto ks = ctx->keys;
     j->key_set = ks;
-    const size_t nk = ks->n;
+    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
     std::vector<uint32_t> cnt(nk, 0);
     words.assign(3 * n + n / W + 1, 0);
     uint32_t* kid = words.data();
@@ -1391,7 +1413,7 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJo
     for (size_t k = 0, w = 0; k < nk; k++)
         for (uint32_t q = 0; q < cnt[k] / W; q++) wkey[w++] = (uint32_t)k;
     words.resize(n + nu + nm + nu / W);
-    kj.keys = ks->d.template as<KeyEntry<C>>();
+    kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
     kj.pair.keys = kj.keys; kj.pair.n_uni = nu; kj.pair.n_slots = nu + nm;
 }
 // the device half: d = the words' place in the device copy of the staging image
@@ -1429,14 +1451,33 @@ void add_keyed_pairing_stages(J* j, KeyedJob<C>* kj, const PairArgs<C>* pa, int 
 struct MixedJob {
     const HashCtx* pref = nullptr;           // [L + 1] domain prefix of length l (the context's LenSet, held by the job)
     uint32_t* len = nullptr;                 // [n] written by the ingest stage
+    uint32_t stride = 0;                     // keyed jobs of mixed counts only: pref is [n_keys][stride], stride = L + 1
 };
+template <class J>
+int mixed_len_scratch(J* j, size_t nn, MixedJob& mx) {
+    int rc = BBS_OK;
+    mx.len = j->template scratch<uint32_t>(nn, rc);
+    return rc;
+}
 template <class C, class J>
 int mixed_bind(J* j, Ctx<C>* ctx, size_t nn, MixedJob& mx) {
     std::shared_ptr<const typename Ctx<C>::LenSet> ls;
     if (const int rc = ctx->sync_lengths(ls)) return rc;
     j->len_set = ls;
     mx.pref = ls->d.template as<HashCtx>();
-    int rc = BBS_OK;
-    mx.len = j->template scratch<uint32_t>(nn, rc);
-    return rc;
+    return mixed_len_scratch(j, nn, mx);
+}
+// keyed jobs of mixed counts (bbs_ctx_set_keyed_mixed_lengths): the prefixes per (key, length) instead of the context's per
+// length; they must be the rows of the key set keyed_order bound the job to (fail closed otherwise: a set that was replaced
+// between the two looks)
+template <class C, class J>
+int keyed_mixed_bind(J* j, Ctx<C>* ctx, size_t nn, MixedJob& mx) {
+    const auto kl = ctx->key_lens;
+    mx.stride = (uint32_t)ctx->L + 1;
+    if (j->key_set) {         // (an empty set has no rows and no item that reads one: KeyGate decides every item)
+        if (!kl || kl->of.get() != j->key_set.get() || kl->stride != (size_t)mx.stride) return BBS_E_STATE;
+        j->key_len_set = kl;
+        mx.pref = kl->d.template as<HashCtx>();
+    }
+    return mixed_len_scratch(j, nn, mx);
 }

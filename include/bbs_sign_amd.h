@@ -135,8 +135,8 @@ size_t bbs_device_free_bytes(int device_id);          /* device memory free righ
 
 int bbs_ctx_create(int curve, int device_id, bbs_ctx** out);
 void bbs_ctx_destroy(bbs_ctx* ctx);
-/* device memory of the context's tables (fixed-base window tables, line tables, constants, and the per-length domain
- * prefixes of bbs_ctx_set_mixed_lengths), in bytes */
+/* device memory of the context's tables (fixed-base window tables, line tables, constants, the per-length domain
+ * prefixes of bbs_ctx_set_mixed_lengths and the per-(key, length) prefixes of bbs_ctx_set_keyed_mixed_lengths), in bytes */
 size_t bbs_ctx_table_bytes(const bbs_ctx* ctx);
 
 /* window width (bits) of the fixed-base tables, 4..22, or 0 (THE DEFAULT) = chosen at bbs_ctx_set_generators from the
@@ -196,10 +196,31 @@ int bbs_ctx_set_fixed_base_tree(bbs_ctx* ctx, int enabled);
  * fixed-base tree and every window width.  Costs L + 1 domain prefixes (about 370 bytes each) of device memory, counted in
  * bbs_ctx_table_bytes, rebuilt by bbs_ctx_set_generators and the key setters.  Applies to jobs created afterwards; a job keeps
  * what it was created with.
- * NOT covered: the keyed entry points of a context with the switch on return BBS_E_STATE and enqueue nothing (a prefix per
- * (key, length) pair is a follow-up); sign and proof_gen are unchanged and keep deciding l != L as -1 whatever the switch
+ * NOT covered: the keyed entry points look at bbs_ctx_set_keyed_mixed_lengths (below), not at this switch; with this switch on
+ * and that one off they return BBS_E_STATE and enqueue nothing; sign and proof_gen are unchanged and keep deciding l != L as -1 whatever the switch
  * says; bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
+/* Mixed message counts for the KEYED entry points (off by default; with it off nothing changes anywhere, the BBS_E_STATE above
+ * included).  enabled = 1: every keyed verify and proof_verify job created from now on -- the eight bbs_*_keyed_* exports: core
+ * and wire forms, _submit and _batch, both job forms -- takes item i under its own key key_index[i] AND with its own count l_i,
+ * 0 <= l_i <= L.  The status of item i is, bit for bit, what a single-key context made with generators[0 .. l_i], that key and
+ * the same api_id and modes gives that item alone: the checks and their order are those of bbs_ctx_set_mixed_lengths ("l != L"
+ * becomes "l > L", still -1; -3, -6, -22, -23, -40, -41, -42 against the item's own l_i), and behind them an unknown or refused
+ * key index is BBS_ST_UNKNOWN_KEY whatever those checks decided, as in every keyed job.  Keyed jobs keep ignoring batch
+ * verification.
+ * Memory: one domain prefix per (key, length), (L + 1) * 368 bytes per key of the set, refused keys included (12 144 bytes at
+ * L = 32, beside the key's 29 KB line table), counted in bbs_ctx_table_bytes while the switch is on.  The prefixes are built on
+ * host threads when the switch is turned on (for the keys of the set) and by every registration call while it is on (for the
+ * keys it appends; the old rows are copied on the device), so any order of bbs_ctx_set_generators, registration and this call
+ * ends in the same verdicts; bbs_ctx_set_generators clears the key set and with it the prefixes, and while the switch is on a
+ * context without a key set is one with an empty set: every item is BBS_ST_UNKNOWN_KEY (with the switch off: BBS_E_STATE, as
+ * before).  Turning the switch off releases them.  BBS_E_NOMEM / BBS_E_HIP leave the switch as it was.
+ * Independent of bbs_ctx_set_mixed_lengths: single-key jobs never look at this switch, keyed jobs look at that one only to
+ * return BBS_E_STATE when it is on and this one is off.  Applies to jobs created afterwards; a job keeps the stages, the key set
+ * and the prefixes it was created with, whatever is switched, appended or replaced later.  BBS_E_ARG for a NULL ctx.
+ * NOT covered: keyed sign / proof_gen do not exist; bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust
+ * shim do not expose the switch. */
+int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled);
 
 /* Batch verification for core_proof_verify and core_verify (off by default).  When enabled, the n two-pairing
  * products of a batch (src/proof_verify.rs:112-115, src/verify.rs:88-92) are replaced by 16 products over random
@@ -378,9 +399,11 @@ size_t bbs_ctx_public_key_count(const bbs_ctx* ctx);
  * of the un-keyed form plus key_index (n entries) after n.  For an item whose key_index names an accepted key the status is
  * what the un-keyed form gives on a context with the same generators, api_id, window bits and modes and that key set by
  * bbs_ctx_set_public_key; for an index >= the set's size or naming a refused key it is BBS_ST_UNKNOWN_KEY.  BBS_E_STATE
- * without generators or a key set, BBS_E_ARG for a NULL key_index with n > 0.  Batch verification
- * (bbs_ctx_set_batch_verification) does not apply: every item gets its own pairing product.  The _submit forms return
- * ordinary jobs (bbs_job_wait, bbs_jobs_wait_any, bbs_job_free). */
+ * without generators; without a key set (unless bbs_ctx_set_keyed_mixed_lengths is on: then a missing set is the empty set
+ * and every item is BBS_ST_UNKNOWN_KEY); and on a context with bbs_ctx_set_mixed_lengths on unless
+ * bbs_ctx_set_keyed_mixed_lengths is on too (then every item has its own count, see there).  BBS_E_ARG for a NULL key_index
+ * with n > 0.  Batch verification (bbs_ctx_set_batch_verification) does not apply: every item gets its own pairing product.
+ * The _submit forms return ordinary jobs (bbs_job_wait, bbs_jobs_wait_any, bbs_job_free). */
 int bbs_core_proof_verify_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proofs_fixed,
                                        const uint8_t* commitments, const uint64_t* commit_off,
                                        const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
