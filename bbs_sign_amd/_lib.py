@@ -65,6 +65,7 @@ SIGNATURES = {
     "bbs_ctx_set_latency_mode": (ci, [vp, ci]),
     "bbs_ctx_set_fixed_base_tree": (ci, [vp, ci]),
     "bbs_ctx_set_mixed_lengths": (ci, [vp, ci]),
+    "bbs_ctx_set_mixed_lengths_gen": (ci, [vp, ci]),
     "bbs_ctx_set_keyed_mixed_lengths": (ci, [vp, ci]),
     "bbs_selftest_glv_split": (ci, [ci, c_u8p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "bbs_selftest_lin_pm": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),

@@ -276,6 +276,68 @@ def proof_verify_many(pk: PublicKey, items: Sequence[tuple]) -> list:
                                                                [it[1] for it in its], [it[2] for it in its]))
 
 
+# ------------------------------------------------------------------ many items, any lengths: the producing side
+def _mixed_gen_engine(key, L: int) -> Engine:
+    """A cached engine of this SecretKey (sign) or PublicKey (proof_gen) with bbs_ctx_set_mixed_lengths_gen on, made for L
+    messages or more: its own cache entries, as _mixed_engine's -- the smallest cached one that fits serves, a longer list
+    replaces the shorter ones."""
+    secret = isinstance(key, SecretKey)
+    name = ("sk", key.sk) if secret else (None if key.pk is None else tuple(map(tuple, key.pk)))
+    who = (key.curve, name, key.device, key.lib_path)
+    fits = [k for k in _eng_cache if k[0] == "mixed_gen" and k[2:] == who and k[1] >= L]
+    if fits:
+        return _eng_cache[min(fits, key=lambda k: k[1])]
+    eng = Engine(key.curve, device=key.device, lib_path=key.lib_path, window_bits=4 if key.lib_path is not None else None)
+    eng.set_generators(create_generators(key.curve, L + 1, key.lib_path), api_id(key.curve))
+    if secret:
+        eng.set_secret_key(key.sk)
+    else:
+        eng.set_public_key(key.pk)
+    eng.set_mixed_lengths_gen(True)
+    for k in [k for k in _eng_cache if k[0] == "mixed_gen" and k[2:] == who]:      # the shorter ones it replaces
+        _eng_cache.pop(k).close()
+    _eng_cache[("mixed_gen", L) + who] = eng
+    return eng
+
+
+def sign_many(sk: SecretKey, items: Sequence[tuple]) -> list:
+    """SecretKey.sign for many items ``(messages, header)`` whose message counts may differ, in ONE device call: one cached
+    engine whose L is the largest count present, with bbs_ctx_set_mixed_lengths_gen on, through the wire form.  Entry i is the
+    Signature ``sk.sign(*items[i])`` returns, or the BbsError it raises (returned, not raised: the other items stand)."""
+    if not items:
+        return []
+    eng = _mixed_gen_engine(sk, max(len(it[0]) for it in items))
+    octs, st = eng.sign_wire_batch([list(it[0]) for it in items], [it[1] for it in items])
+    return [BbsError(int(s)) if s < 0 else octets_to_signature(sk.curve, o, sk.lib_path) for o, s in zip(octs, st)]
+
+
+def proof_gen_many(pk: PublicKey, items: Sequence[tuple]) -> list:
+    """proof_gen for many items ``(signature, header, ph, messages, disclosed_indexes[, random_scalars])`` of any message
+    counts, in ONE device call, as sign_many.  Entry i is the Proof ``proof_gen(pk, *items[i])`` returns with the same random
+    scalars (drawn here, as there, where an item has none), or the BbsError it raises (returned, not raised).  A wrong number of
+    random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as it fails the one-item call."""
+    if not items:
+        return []
+    eng = _mixed_gen_engine(pk, max(len(it[3]) for it in items))
+    rnds = [list(it[5]) if len(it) > 5 and it[5] is not None else
+            calculate_random_scalars(pk.curve, max(5 + len(it[3]) - len(it[4]), 0)) for it in items]
+    out: list = [None] * len(items)
+    octs, idx = [], []
+    for i, it in enumerate(items):
+        try:
+            octs.append(signature_to_octets(pk.curve, it[0], pk.lib_path))
+            idx.append(i)
+        except BbsError as e:           # a signature that cannot be written as octets keeps the codec's error
+            out[i] = e
+    if idx:
+        its = [items[i] for i in idx]
+        po, st = eng.proof_gen_wire_batch(octs, [list(it[3]) for it in its], [list(it[4]) for it in its], [rnds[i] for i in idx],
+                                          [it[1] for it in its], [it[2] for it in its])
+        for i, o, s in zip(idx, po, st):
+            out[i] = BbsError(int(s)) if s < 0 else octets_to_proof(pk.curve, o, pk.lib_path)
+    return out
+
+
 # ------------------------------------------------------------------ many items, any issuers, any lengths
 class _IssuerEngine:
     """One engine per (curve, device, lib_path) with bbs_ctx_set_keyed_mixed_lengths on: made for the largest count seen, its

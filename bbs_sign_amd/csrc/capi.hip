@@ -442,6 +442,10 @@ int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_mixed_lengths(enabled); });
 }
+int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->set_mixed_lengths_gen(enabled); });
+}
 int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_keyed_mixed_lengths(enabled); });

@@ -11,6 +11,7 @@ struct PgJob : JobBase<C> {
     PgIngestArgs<C> ingest{};
     VfOctArgs<C> oct{};               // signature octets in (wire form) only
     MsgHashArgs mh{};                 // raw-message form only
+    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths_gen)
     // The proofs come off the device in the caller's layout (stage PgEmit): records, the m^ of the undisclosed messages
     // in ascending index order (L slots per item, the first ucount[i] used) and those counts.  Host side of a delivery:
     // one copy of the records, one contiguous copy per item of its commitments, the running offsets.
@@ -199,15 +200,27 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     if ((rc = job->finish_setup_device())) return rc;
     a.status = job->d_status.template as<int8_t>();
     ia.status0 = job->d_status0.template as<int8_t>();
-    if (rt::launch<PgIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
+    const bool mixed = ctx->mixed_lengths_gen;
+    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if (mixed && rt::launch<PgIngestMixed<C>>(job->stream(), MixedIngestArgs<PgIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+    if (!mixed && rt::launch<PgIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
     PgJob<C>* j = job.get();
-    j->stages.push_back({"pg_scalars", [j]() { return rt::launch<PgScalars<C>>(j->stream(), j->a, j->n); }});
+    if (mixed)
+        j->stages.push_back({"pg_scalars_mixed", [j]() { return rt::launch<PgScalarsMixed<C>>(j->stream(), MixedScalarArgs<PgArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
+    else
+        j->stages.push_back({"pg_scalars", [j]() { return rt::launch<PgScalars<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"pg_b_parts", [j]() { return rt::launch<PgBPart<C>>(j->stream(), j->a, j->n * (size_t)(2 * NFIX)); }});
     j->stages.push_back({"pg_b_combine", [j]() { return rt::launch<PgBCombine<C>>(j->stream(), j->a, j->n); }});
     if (j->a.ctab) j->stages.push_back({"pg_tables", [j]() { return rt::launch<PgTables<C>>(j->stream(), j->a, j->n * 2); }});
     j->stages.push_back({"pg_var_parts", [j]() { return rt::launch<PgVarPart<C>>(j->stream(), j->a, j->n * (size_t)j->a.nvar); }});
-    j->stages.push_back({"pg_finalize", [j]() { return rt::launch<PgFinalize<C>>(j->stream(), j->a, j->n); }});
-    j->stages.push_back({"pg_emit", [j]() { return rt::launch<PgEmit<C>>(j->stream(), j->a, j->n); }});
+    if (mixed) {
+        j->stages.push_back({"pg_finalize_mixed", [j]() { return rt::launch<PgFinalizeMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
+        j->stages.push_back({"pg_emit_mixed", [j]() { return rt::launch<PgEmitMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
+    } else {
+        j->stages.push_back({"pg_finalize", [j]() { return rt::launch<PgFinalize<C>>(j->stream(), j->a, j->n); }});
+        j->stages.push_back({"pg_emit", [j]() { return rt::launch<PgEmit<C>>(j->stream(), j->a, j->n); }});
+    }
     *out = job.release();
     return BBS_OK;
 }

@@ -10,6 +10,7 @@ struct SgJob : JobBase<C> {
     SgArgs<C> a{};
     VfIngestArgs<C> ingest{};
     MsgHashArgs mh{};                 // raw-message form only
+    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths_gen)
     // the records come off the device in the caller's layout (stage SgEmit): delivery is one copy
     size_t rec_bytes() const { return a.oct_form ? (size_t)(4 * C::FpP::NC + 32) : (size_t)(8 * C::FpP::NC + 32); }
     int set_octet_form() override { a.oct_form = 1; return BBS_OK; }
@@ -88,9 +89,16 @@ int sg_upload(Ctx<C>* ctx, size_t n, const SgIn& in, bbs_job** out) {
     }
     ia.sig_a = nullptr; ia.sig_e = nullptr; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
-    if (rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
+    const bool mixed = ctx->mixed_lengths_gen;
+    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if (mixed && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+    if (!mixed && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
     SgJob<C>* j = job.get();
-    j->stages.push_back({"sg_scalars", [j]() { return rt::launch<SgScalars<C>>(j->stream(), j->a, j->n); }});
+    if (mixed)
+        j->stages.push_back({"sg_scalars_mixed", [j]() { return rt::launch<SgScalarsMixed<C>>(j->stream(), MixedScalarArgs<SgArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
+    else
+        j->stages.push_back({"sg_scalars", [j]() { return rt::launch<SgScalars<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"sg_msm_parts", [j]() { return rt::launch<SgMsmPart<C>>(j->stream(), j->a, j->n * NFIX); }});
     j->stages.push_back({"sg_combine", [j]() { return rt::launch<SgCombine<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"sg_emit", [j]() { return rt::launch<SgEmit<C>>(j->stream(), j->a, j->n); }});

@@ -647,8 +647,14 @@ struct Ctx : bbs_ctx {
     // device array is immutable once built and a job holds a reference, so a change of key or generators never reaches a job
     // that exists (the rule of the key set above).
     bool mixed_lengths = false;
+    // the same for the producing side (bbs_ctx_set_mixed_lengths_gen): off by default and independent of mixed_lengths.  On: the
+    // sign / proof_gen jobs created from now on accept item i with its own count l_i <= L.  Both switches are served by the ONE
+    // array of prefixes below -- built while either is on, counted once by table_bytes.  (A context that signs has its public
+    // key: set_secret_key derives sk * BP2 and goes through set_pk_internal, so rebuild_hash sees pk_set on the signing side too.)
+    bool mixed_lengths_gen = false;
+    bool any_mixed_lengths() const { return mixed_lengths || mixed_lengths_gen; }
     struct LenSet { DevBuf d; };     // [L + 1] HashCtx
-    std::vector<HashCtx> len_hash;   // host mirror; empty unless the switch is on and generators and key are set
+    std::vector<HashCtx> len_hash;   // host mirror; empty unless one of the two switches is on and generators and key are set
     std::shared_ptr<const LenSet> len_set;      // null: to be uploaded from len_hash
     // batch verification (pippenger.hpp): off by default = every item gets its own pairing product
     bool batch_verify = false;
@@ -718,7 +724,7 @@ struct Ctx : bbs_ctx {
 
     int use() { return rt::set_device(device) ? BBS_E_HIP : BBS_OK; }
     size_t table_bytes() const {
-        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (mixed_lengths ? len_hash.size() * sizeof(HashCtx) : 0) + key_lens_bytes();
+        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (any_mixed_lengths() ? len_hash.size() * sizeof(HashCtx) : 0) + key_lens_bytes();
     }
 
     // domain prefix:  Z_pad || compress(pk) || I2OSP(L,8) || compress(Q1) || compress(H_i).. || api_id
@@ -734,7 +740,7 @@ struct Ctx : bbs_ctx {
         len_set.reset();
         if (!(gens_set && pk_set)) { consts_dirty = true; return; }
         domain_midstate(pk, h);
-        if (mixed_lengths) {
+        if (any_mixed_lengths()) {
             // every generator is compressed ONCE; prefix l hashes the first l + 1 of them
             const std::vector<uint8_t> cg = compressed_gens();
             len_hash.assign((size_t)L + 1, key_hash0());
@@ -782,10 +788,17 @@ struct Ctx : bbs_ctx {
         rebuild_hash();
         return BBS_OK;
     }
+    int set_mixed_lengths_gen(int enabled) {
+        std::lock_guard<std::mutex> g(mu);
+        if (mixed_lengths_gen == (enabled != 0)) return BBS_OK;
+        mixed_lengths_gen = enabled != 0;
+        rebuild_hash();
+        return BBS_OK;
+    }
     // the per-length prefixes on the device, for a job that is being created (uploaded once per rebuild_hash)
     int sync_lengths(std::shared_ptr<const LenSet>& out) {
         std::lock_guard<std::mutex> g(mu);
-        if (!mixed_lengths || len_hash.empty()) return BBS_E_STATE;
+        if (!any_mixed_lengths() || len_hash.empty()) return BBS_E_STATE;
         if (!len_set) {
             std::shared_ptr<LenSet> ls(new LenSet());
             const size_t b = len_hash.size() * sizeof(HashCtx);

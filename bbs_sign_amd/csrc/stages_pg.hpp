@@ -81,9 +81,11 @@ struct PgIngestArgs {
     uint32_t *sig_a, *sig_e, *msgs, *dmask, *didx, *rcount, *rnd5, *mtilde, *hdr_off, *hdr_len, *ph_off, *ph_len;
     int8_t* status0;
 };
-template <class C>
-struct PgIngest {
-    static __host__ __device__ void run(const PgIngestArgs<C>& a, size_t i) {
+// MIXED (bbs_ctx_set_mixed_lengths_gen, PgIngestMixed below): the item's own message count l may be anything in 0 .. L and is
+// recorded in len[i] (0 for an item that is decided before or by the length check); l != L becomes l > L, nothing else changes
+template <class C, bool MIXED>
+struct PgIngestBody {
+    static BBS_HD void run(const PgIngestArgs<C>& a, size_t i, uint32_t* len) {
         using P = typename C::FpP;
         using R = typename C::FrP;
         constexpr int NC = P::NC;
@@ -97,6 +99,7 @@ struct PgIngest {
         const int MW = ((a.L > 1 ? a.L : 1) + 31) / 32;
         for (int w = 0; w < MW; w++) a.dmask[(size_t)w * n + i] = 0;
         a.rcount[i] = 0;
+        if constexpr (MIXED) len[i] = 0;
         if (a.oct) {
             // the verdicts of bbs_signature_from_octets first, in its order (see VfIngest)
             constexpr size_t NB = 4 * NC;
@@ -120,7 +123,8 @@ struct PgIngest {
         bool bad = false;
         for (uint64_t k = 0; k < r; k++) bad |= idx[k] >= l;
         if (bad) { a.status0[i] = -3; return; }                            // InvalidDisclosedIndex
-        if (l != (uint64_t)a.L) { a.status0[i] = -1; return; }             // proof_init: InvalidMessageAndGeneratorsLength
+        if (MIXED ? l > (uint64_t)a.L : l != (uint64_t)a.L) { a.status0[i] = -1; return; }   // proof_init: InvalidMessageAndGeneratorsLength
+        if constexpr (MIXED) len[i] = (uint32_t)l;
         uint64_t distinct = 0;
         for (uint64_t k = 0; k < r; k++) {
             const size_t j = (size_t)idx[k];
@@ -175,48 +179,79 @@ struct PgIngest {
         a.status0[i] = ok ? ST_PENDING : (int8_t)-40;
     }
 };
+template <class C>
+struct PgIngest {
+    static __host__ __device__ void run(const PgIngestArgs<C>& a, size_t i) { PgIngestBody<C, false>::run(a, i, nullptr); }
+};
+template <class C>
+struct PgIngestMixed {
+    static __host__ __device__ void run(const MixedIngestArgs<PgIngestArgs<C>>& m, size_t i) { PgIngestBody<C, true>::run(m.a, i, m.len); }
+};
+// the later stages of a mixed-length job that need the item's count and nothing else (PgFinalizeMixed, PgEmitMixed)
+template <class A>
+struct MixedLenArgs { A a; const uint32_t* len; };
 
+// h: the domain prefix (the context's, or that of the item's own length in a mixed-length job); l: the item's message count
+// (a.L unless the job is a mixed-length one)
+template <class C>
+BBS_HD void pg_scalars_item(const PgArgs<C>& a, size_t i, const HashCtx& h, int l) {
+    using R = typename C::FrP;
+    const size_t n = a.n;
+    Fr<C> r2c = fr_load_canon<C>(a.rnd5 + (size_t)1 * 8 * n, n, i);
+    Fr<C> dom = domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
+    soa_st<8>(a.dom, n, i, dom.v);
+    Fr<C> domc = fe_to_canonical<R>(dom);
+    Fr<C> one = fe_zero<R>();
+    one.v[0] = 1;
+    Fr<C> zero = fe_zero<R>();
+    soa_st<8>(a.fscal, n, i, one.v);
+    soa_st<8>(a.fscal + (size_t)8 * n, n, i, domc.v);
+    soa_st<8>(a.fscal2, n, i, zero.v);
+    soa_st<8>(a.fscal2 + (size_t)8 * n, n, i, zero.v);
+    for (int j = 0; j < l; j++) {
+        uint32_t m[8];
+        soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
+        soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, m);
+        soa_ld<8>(a.mtilde + (size_t)j * 8 * n, n, i, m);
+        soa_st<8>(a.fscal2 + (size_t)(2 + j) * 8 * n, n, i, m);
+    }
+    // variable-base scalars (proof_gen.rs:254-258, restructured over B and A)
+    Fr<C> r1 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5, n, i));
+    Fr<C> r2 = fr_to_mont<C>(r2c);
+    Fr<C> et = fr_load_canon<C>(a.rnd5 + (size_t)2 * 8 * n, n, i);
+    Fr<C> r1t = fr_load_canon<C>(a.rnd5 + (size_t)3 * 8 * n, n, i);
+    Fr<C> r3t = fr_load_canon<C>(a.rnd5 + (size_t)4 * 8 * n, n, i);
+    Fr<C> e = fr_load_canon<C>(a.sig_e, n, i);
+    Fr<C> r1r2 = fe_mul<R>(r1, r2);                               // Montgomery
+    Fr<C> v[PG_NVAR];
+    v[0] = r2c;                                                   // D      = r2 * B
+    v[1] = fe_to_canonical<R>(r1r2);                              // r1r2 * B
+    v[2] = fe_mul<R>(r2, r1t);                                    // T1 part: (r1~ r2) * B
+    v[3] = fe_mul<R>(r2, r3t);                                    // T2 part: (r3~ r2) * B
+    v[4] = v[1];                                                  // Abar   = (r1 r2) * A
+    v[5] = fe_mul<R>(r1r2, e);                                    // (e r1 r2) * A
+    v[6] = fe_mul<R>(r1r2, et);                                   // (e~ r1 r2) * A
+    for (int k = 0; k < PG_NVAR; k++) soa_st<8>(a.vscal + (size_t)k * 8 * n, n, i, v[k].v);
+}
 template <class C>
 struct PgScalars {
     static __host__ __device__ void run(const PgArgs<C>& a, size_t i) {
-        using R = typename C::FrP;
         if (a.status[i] != ST_PENDING) return;
-        const size_t n = a.n;
-        Fr<C> r2c = fr_load_canon<C>(a.rnd5 + (size_t)1 * 8 * n, n, i);
-        Fr<C> dom = domain_from_header<C>(a.cc->hash, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
-        soa_st<8>(a.dom, n, i, dom.v);
-        Fr<C> domc = fe_to_canonical<R>(dom);
-        Fr<C> one = fe_zero<R>();
-        one.v[0] = 1;
-        Fr<C> zero = fe_zero<R>();
-        soa_st<8>(a.fscal, n, i, one.v);
-        soa_st<8>(a.fscal + (size_t)8 * n, n, i, domc.v);
-        soa_st<8>(a.fscal2, n, i, zero.v);
-        soa_st<8>(a.fscal2 + (size_t)8 * n, n, i, zero.v);
-        for (int j = 0; j < a.L; j++) {
-            uint32_t m[8];
-            soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
-            soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, m);
-            soa_ld<8>(a.mtilde + (size_t)j * 8 * n, n, i, m);
-            soa_st<8>(a.fscal2 + (size_t)(2 + j) * 8 * n, n, i, m);
-        }
-        // variable-base scalars (proof_gen.rs:254-258, restructured over B and A)
-        Fr<C> r1 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5, n, i));
-        Fr<C> r2 = fr_to_mont<C>(r2c);
-        Fr<C> et = fr_load_canon<C>(a.rnd5 + (size_t)2 * 8 * n, n, i);
-        Fr<C> r1t = fr_load_canon<C>(a.rnd5 + (size_t)3 * 8 * n, n, i);
-        Fr<C> r3t = fr_load_canon<C>(a.rnd5 + (size_t)4 * 8 * n, n, i);
-        Fr<C> e = fr_load_canon<C>(a.sig_e, n, i);
-        Fr<C> r1r2 = fe_mul<R>(r1, r2);                               // Montgomery
-        Fr<C> v[PG_NVAR];
-        v[0] = r2c;                                                   // D      = r2 * B
-        v[1] = fe_to_canonical<R>(r1r2);                              // r1r2 * B
-        v[2] = fe_mul<R>(r2, r1t);                                    // T1 part: (r1~ r2) * B
-        v[3] = fe_mul<R>(r2, r3t);                                    // T2 part: (r3~ r2) * B
-        v[4] = v[1];                                                  // Abar   = (r1 r2) * A
-        v[5] = fe_mul<R>(r1r2, e);                                    // (e r1 r2) * A
-        v[6] = fe_mul<R>(r1r2, et);                                   // (e~ r1 r2) * A
-        for (int k = 0; k < PG_NVAR; k++) soa_st<8>(a.vscal + (size_t)k * 8 * n, n, i, v[k].v);
+        pg_scalars_item<C>(a, i, a.cc->hash, a.L);
+    }
+};
+// Mixed lengths (bbs_ctx_set_mixed_lengths_gen): as PvScalarsMixed (stages_pv.hpp) -- the domain from the prefix of the item's
+// own length, B's scalars and T2's for its l messages, and zeros WRITTEN for the bases H_{l+1} .. H_L in BOTH arrays (the
+// buffers come from the pools and hold what the last job left), so PgBPart runs unchanged.  The HashCtx is read through the
+// per-lane pointer and passed on by reference, never copied into a local.
+template <class C>
+struct PgScalarsMixed {
+    static __host__ __device__ void run(const MixedScalarArgs<PgArgs<C>>& m, size_t i) {
+        if (m.a.status[i] != ST_PENDING) return;
+        const int l = (int)m.len[i];
+        pg_scalars_item<C>(m.a, i, m.pref[l], l);
+        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
+        mixed_zero_scalars(m.a.fscal2, m.a.n, i, l, m.a.L);
     }
 };
 
@@ -414,128 +449,151 @@ struct PgVarPart {
     }
 };
 
+// l: the item's message count (a.L unless the job is a mixed-length one): m^ for the undisclosed j < l
+template <class C>
+BBS_HD void pg_finalize_item(const PgArgs<C>& a, size_t i, int l) {
+    using R = typename C::FrP;
+    constexpr int N = C::FpP::N;
+    const size_t n = a.n;
+    auto part = [&](int p) { return g1j_load<C>(a.partials + (size_t)p * 3 * N * n, n, i); };
+    G1Jac<C> pj[5];
+    if (a.nvar == PG_NVAR) {
+        pj[0] = part(4);                                              // Abar
+        pj[1] = g1j_add_i<C>(part(1), g1j_neg<C>(part(5)));             // Bbar = r1r2 B - e r1r2 A
+        pj[2] = part(0);                                              // D
+        pj[3] = g1j_add_i<C>(part(6), part(2));                         // T1
+        pj[4] = part(3);                                              // T2
+    } else {
+        pj[0] = part(1); pj[1] = part(2); pj[2] = part(0); pj[3] = part(3); pj[4] = part(4);      // the joint chains' own sums
+    }
+    for (int f = 0; f < NFIX; f++) pj[4] = g1j_add_i<C>(pj[4], part(a.nvar + f));
+    G1Aff<C> pa[5];
+    g1j_batch_to_aff<C, 5>(pj, pa);
+    // challenge (proof_gen.rs:272-328), disclosed indexes sorted + deduplicated (:151-161)
+    Sha256 s;
+    xmd48_begin(s);
+    const uint32_t Rn = a.rcount[i];
+    sha256_u64be(s, Rn);
+    for (uint32_t k = 0; k < Rn; k++) {
+        const uint32_t idx = a.didx[(size_t)k * n + i];
+        sha256_u64be(s, idx);
+        uint32_t m[8];
+        soa_ld<8>(a.msgs + (size_t)idx * 8 * n, n, i, m);
+        sha256_limbs_be8(s, m);
+    }
+    for (int p = 0; p < 5; p++) sha256_g1_compressed<C>(s, pa[p]);
+    Fr<C> dom;
+    soa_ld<8>(a.dom, n, i, dom.v);
+    sha256_fr_be<C>(s, dom);
+    sha256_u64be(s, a.ph_len[i]);
+    sha256_bytes(s, a.ph_bytes + a.ph_off[i], a.ph_len[i]);
+    uint32_t okm[12];
+    xmd48_finish(s, a.cc->hash.dst_h2s, a.cc->hash.dst_h2s_len, okm);
+    Fr<C> c = fr_from_okm<C>(okm);                                // Montgomery
+    // proof_finalize (proof_gen.rs:331-365)
+    Fr<C> r2 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)1 * 8 * n, n, i));
+    if (fe_is_zero<R>(r2)) { a.status[i] = -21; return; }         // :346 unwrap
+    Fr<C> r3 = fe_inv<R>(r2);
+    Fr<C> r1 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5, n, i));
+    Fr<C> et = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)2 * 8 * n, n, i));
+    Fr<C> r1t = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)3 * 8 * n, n, i));
+    Fr<C> r3t = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)4 * 8 * n, n, i));
+    Fr<C> e = fr_to_mont<C>(fr_load_canon<C>(a.sig_e, n, i));
+    Fr<C> o[4];
+    o[0] = fe_to_canonical<R>(fe_add<R>(et, fe_mul<R>(e, c)));
+    o[1] = fe_to_canonical<R>(fe_sub<R>(r1t, fe_mul<R>(r1, c)));
+    o[2] = fe_to_canonical<R>(fe_sub<R>(r3t, fe_mul<R>(r3, c)));
+    o[3] = fe_to_canonical<R>(c);
+    for (int k = 0; k < 4; k++) soa_st<8>(a.out_sc + (size_t)k * 8 * n, n, i, o[k].v);
+    for (int j = 0; j < l; j++) {
+        const uint32_t dm = a.dmask[(size_t)(j >> 5) * n + i];
+        if ((dm >> (j & 31)) & 1u) continue;
+        Fr<C> m = fr_load_canon<C>(a.msgs + (size_t)j * 8 * n, n, i);       // canonical
+        Fr<C> mt = fr_load_canon<C>(a.mtilde + (size_t)j * 8 * n, n, i);   // canonical
+        // m~ + m*c : mont_mul(c_mont, m_canon) = m*c canonical ; add canonical values mod r
+        Fr<C> mh = fe_add<R>(mt, fe_mul<R>(c, m));
+        soa_st<8>(a.out_mhat + (size_t)j * 8 * n, n, i, mh.v);
+    }
+    for (int p = 0; p < 3; p++) g1a_store_canon<C>(a.out_pts + (size_t)p * 2 * C::FpP::NC * n, n, i, pa[p]);
+    a.status[i] = 1;
+}
 template <class C>
 struct PgFinalize {
     static __host__ __device__ void run(const PgArgs<C>& a, size_t i) {
-        using R = typename C::FrP;
-        constexpr int N = C::FpP::N;
-        const size_t n = a.n;
         if (a.status[i] != ST_PENDING) return;
-        auto part = [&](int p) { return g1j_load<C>(a.partials + (size_t)p * 3 * N * n, n, i); };
-        G1Jac<C> pj[5];
-        if (a.nvar == PG_NVAR) {
-            pj[0] = part(4);                                              // Abar
-            pj[1] = g1j_add_i<C>(part(1), g1j_neg<C>(part(5)));             // Bbar = r1r2 B - e r1r2 A
-            pj[2] = part(0);                                              // D
-            pj[3] = g1j_add_i<C>(part(6), part(2));                         // T1
-            pj[4] = part(3);                                              // T2
-        } else {
-            pj[0] = part(1); pj[1] = part(2); pj[2] = part(0); pj[3] = part(3); pj[4] = part(4);      // the joint chains' own sums
-        }
-        for (int f = 0; f < NFIX; f++) pj[4] = g1j_add_i<C>(pj[4], part(a.nvar + f));
-        G1Aff<C> pa[5];
-        g1j_batch_to_aff<C, 5>(pj, pa);
-        // challenge (proof_gen.rs:272-328), disclosed indexes sorted + deduplicated (:151-161)
-        Sha256 s;
-        xmd48_begin(s);
-        const uint32_t Rn = a.rcount[i];
-        sha256_u64be(s, Rn);
-        for (uint32_t k = 0; k < Rn; k++) {
-            const uint32_t idx = a.didx[(size_t)k * n + i];
-            sha256_u64be(s, idx);
-            uint32_t m[8];
-            soa_ld<8>(a.msgs + (size_t)idx * 8 * n, n, i, m);
-            sha256_limbs_be8(s, m);
-        }
-        for (int p = 0; p < 5; p++) sha256_g1_compressed<C>(s, pa[p]);
-        Fr<C> dom;
-        soa_ld<8>(a.dom, n, i, dom.v);
-        sha256_fr_be<C>(s, dom);
-        sha256_u64be(s, a.ph_len[i]);
-        sha256_bytes(s, a.ph_bytes + a.ph_off[i], a.ph_len[i]);
-        uint32_t okm[12];
-        xmd48_finish(s, a.cc->hash.dst_h2s, a.cc->hash.dst_h2s_len, okm);
-        Fr<C> c = fr_from_okm<C>(okm);                                // Montgomery
-        // proof_finalize (proof_gen.rs:331-365)
-        Fr<C> r2 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)1 * 8 * n, n, i));
-        if (fe_is_zero<R>(r2)) { a.status[i] = -21; return; }         // :346 unwrap
-        Fr<C> r3 = fe_inv<R>(r2);
-        Fr<C> r1 = fr_to_mont<C>(fr_load_canon<C>(a.rnd5, n, i));
-        Fr<C> et = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)2 * 8 * n, n, i));
-        Fr<C> r1t = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)3 * 8 * n, n, i));
-        Fr<C> r3t = fr_to_mont<C>(fr_load_canon<C>(a.rnd5 + (size_t)4 * 8 * n, n, i));
-        Fr<C> e = fr_to_mont<C>(fr_load_canon<C>(a.sig_e, n, i));
-        Fr<C> o[4];
-        o[0] = fe_to_canonical<R>(fe_add<R>(et, fe_mul<R>(e, c)));
-        o[1] = fe_to_canonical<R>(fe_sub<R>(r1t, fe_mul<R>(r1, c)));
-        o[2] = fe_to_canonical<R>(fe_sub<R>(r3t, fe_mul<R>(r3, c)));
-        o[3] = fe_to_canonical<R>(c);
-        for (int k = 0; k < 4; k++) soa_st<8>(a.out_sc + (size_t)k * 8 * n, n, i, o[k].v);
-        for (int j = 0; j < a.L; j++) {
-            const uint32_t dm = a.dmask[(size_t)(j >> 5) * n + i];
-            if ((dm >> (j & 31)) & 1u) continue;
-            Fr<C> m = fr_load_canon<C>(a.msgs + (size_t)j * 8 * n, n, i);       // canonical
-            Fr<C> mt = fr_load_canon<C>(a.mtilde + (size_t)j * 8 * n, n, i);   // canonical
-            // m~ + m*c : mont_mul(c_mont, m_canon) = m*c canonical ; add canonical values mod r
-            Fr<C> mh = fe_add<R>(mt, fe_mul<R>(c, m));
-            soa_st<8>(a.out_mhat + (size_t)j * 8 * n, n, i, mh.v);
-        }
-        for (int p = 0; p < 3; p++) g1a_store_canon<C>(a.out_pts + (size_t)p * 2 * C::FpP::NC * n, n, i, pa[p]);
-        a.status[i] = 1;
+        pg_finalize_item<C>(a, i, a.L);
+    }
+};
+template <class C>
+struct PgFinalizeMixed {
+    static __host__ __device__ void run(const MixedLenArgs<PgArgs<C>>& m, size_t i) {
+        if (m.a.status[i] != ST_PENDING) return;
+        pg_finalize_item<C>(m.a, i, (int)m.len[i]);
     }
 };
 
 // last stage of proof_gen (lane per item): the proof in the caller's layout, zeros / no commitments unless the status is 1
+// l: the item's message count (a.L unless the job is a mixed-length one): commitments for the undisclosed j < l only; the
+// strides stay those of L.  A plain inline function, not BBS_HD: forced inlining merges the body into the kernel before it is
+// optimised on its own, which moved PgEmit on BLS12-381 from 46 to 50 registers; left to the ordinary inliner (the body is
+// small: it is inlined into both kernels) PgEmit keeps the code it had.
 template <class C>
-struct PgEmit {
-    static __host__ __device__ void run(const PgArgs<C>& a, size_t i) {
-        constexpr int NC = C::FpP::NC, W = 6 * NC + 32;
-        const size_t n = a.n;
-        const bool ok = a.status[i] == 1;
-        if (a.oct_form) {
-            constexpr size_t NB = 4 * NC;
-            const size_t stride = 3 * NB + 32 * (size_t)(4 + (a.L > 1 ? a.L : 1));
-            uint8_t* o = reinterpret_cast<uint8_t*>(a.out_rec) + i * stride;
-            uint32_t u = 0;
-            if (ok) {
-                for (int p = 0; p < 3; p++) {
-                    uint32_t pw[2 * NC];
-                    for (int k = 0; k < 2 * NC; k++) pw[k] = a.out_pts[((size_t)p * 2 * NC + k) * n + i];
-                    g1_words_to_octets<C>(pw, pw + NC, o + (size_t)p * NB);
-                }
-                uint32_t w[8];
-                for (int q = 0; q < 3; q++) {
-                    for (int k = 0; k < 8; k++) w[k] = a.out_sc[((size_t)q * 8 + k) * n + i];
-                    words_be32(w, o + 3 * NB + 32 * (size_t)q);
-                }
-                for (int j = 0; j < a.L; j++) {
-                    const uint32_t dm = a.dmask[(size_t)(j >> 5) * n + i];
-                    if ((dm >> (j & 31)) & 1u) continue;
-                    for (int k = 0; k < 8; k++) w[k] = a.out_mhat[((size_t)j * 8 + k) * n + i];
-                    words_be32(w, o + 3 * NB + 96 + 32 * (size_t)u);
-                    u++;
-                }
-                for (int k = 0; k < 8; k++) w[k] = a.out_sc[((size_t)3 * 8 + k) * n + i];
-                words_be32(w, o + 3 * NB + 96 + 32 * (size_t)u);
-            }
-            a.ucount[i] = ok ? u : 0xFFFFFFFFu;          // no string at all for a failed item
-            return;
-        }
-        uint32_t* r = a.out_rec + i * (size_t)W;
-        for (int k = 0; k < 6 * NC; k++) r[k] = ok ? a.out_pts[(size_t)k * n + i] : 0u;
-        for (int k = 0; k < 32; k++) r[6 * NC + k] = ok ? a.out_sc[(size_t)k * n + i] : 0u;
+__host__ __device__ inline void pg_emit_item(const PgArgs<C>& a, size_t i, int l) {
+    constexpr int NC = C::FpP::NC, W = 6 * NC + 32;
+    const size_t n = a.n;
+    const bool ok = a.status[i] == 1;
+    if (a.oct_form) {
+        constexpr size_t NB = 4 * NC;
+        const size_t stride = 3 * NB + 32 * (size_t)(4 + (a.L > 1 ? a.L : 1));
+        uint8_t* o = reinterpret_cast<uint8_t*>(a.out_rec) + i * stride;
         uint32_t u = 0;
         if (ok) {
-            uint32_t* m = a.out_mh + i * (size_t)(a.L > 1 ? a.L : 1) * 8;
-            for (int j = 0; j < a.L; j++) {
+            for (int p = 0; p < 3; p++) {
+                uint32_t pw[2 * NC];
+                for (int k = 0; k < 2 * NC; k++) pw[k] = a.out_pts[((size_t)p * 2 * NC + k) * n + i];
+                g1_words_to_octets<C>(pw, pw + NC, o + (size_t)p * NB);
+            }
+            uint32_t w[8];
+            for (int q = 0; q < 3; q++) {
+                for (int k = 0; k < 8; k++) w[k] = a.out_sc[((size_t)q * 8 + k) * n + i];
+                words_be32(w, o + 3 * NB + 32 * (size_t)q);
+            }
+            for (int j = 0; j < l; j++) {
                 const uint32_t dm = a.dmask[(size_t)(j >> 5) * n + i];
                 if ((dm >> (j & 31)) & 1u) continue;
-                for (int k = 0; k < 8; k++) m[(size_t)u * 8 + k] = a.out_mhat[((size_t)j * 8 + k) * n + i];
+                for (int k = 0; k < 8; k++) w[k] = a.out_mhat[((size_t)j * 8 + k) * n + i];
+                words_be32(w, o + 3 * NB + 96 + 32 * (size_t)u);
                 u++;
             }
+            for (int k = 0; k < 8; k++) w[k] = a.out_sc[((size_t)3 * 8 + k) * n + i];
+            words_be32(w, o + 3 * NB + 96 + 32 * (size_t)u);
         }
-        a.ucount[i] = u;
+        a.ucount[i] = ok ? u : 0xFFFFFFFFu;          // no string at all for a failed item
+        return;
     }
+    uint32_t* r = a.out_rec + i * (size_t)W;
+    for (int k = 0; k < 6 * NC; k++) r[k] = ok ? a.out_pts[(size_t)k * n + i] : 0u;
+    for (int k = 0; k < 32; k++) r[6 * NC + k] = ok ? a.out_sc[(size_t)k * n + i] : 0u;
+    uint32_t u = 0;
+    if (ok) {
+        uint32_t* m = a.out_mh + i * (size_t)(a.L > 1 ? a.L : 1) * 8;
+        for (int j = 0; j < l; j++) {
+            const uint32_t dm = a.dmask[(size_t)(j >> 5) * n + i];
+            if ((dm >> (j & 31)) & 1u) continue;
+            for (int k = 0; k < 8; k++) m[(size_t)u * 8 + k] = a.out_mhat[((size_t)j * 8 + k) * n + i];
+            u++;
+        }
+    }
+    a.ucount[i] = u;
+}
+template <class C>
+struct PgEmit {
+    static __host__ __device__ void run(const PgArgs<C>& a, size_t i) { pg_emit_item<C>(a, i, a.L); }
+};
+// (a failed item has len = 0 or a count it never uses: nothing is counted or written for it)
+template <class C>
+struct PgEmitMixed {
+    static __host__ __device__ void run(const MixedLenArgs<PgArgs<C>>& m, size_t i) { pg_emit_item<C>(m.a, i, (int)m.len[i]); }
 };
 
 }  // namespace bbs

@@ -24,41 +24,60 @@ struct SgArgs {
     int oct_form;             // 1: out_rec holds n octet strings compress(A) || I2OSP(e, 32) instead (fp_bytes + 32 each)
 };
 
+// h: the domain prefix (the context's, or that of the item's own length in a mixed-length job); l: the item's message count
+// (a.L unless the job is a mixed-length one)
+template <class C>
+BBS_HD void sg_scalars_item(const SgArgs<C>& a, size_t i, const HashCtx& h, int l) {
+    using R = typename C::FrP;
+    const size_t n = a.n;
+    Fr<C> dom = domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
+    // e = hash_to_scalar(sk || m_1 .. m_l || domain)   (sign.rs:90-118)
+    Sha256 s;
+    xmd48_begin(s);
+    sha256_limbs_be8(s, a.sk);
+    for (int j = 0; j < l; j++) {
+        uint32_t m[8];
+        soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
+        sha256_limbs_be8(s, m);
+    }
+    sha256_fr_be<C>(s, dom);
+    uint32_t okm[12];
+    xmd48_finish(s, a.cc->hash.dst_h2s, a.cc->hash.dst_h2s_len, okm);
+    Fr<C> e = fr_from_okm<C>(okm);
+    Fr<C> ec = fe_to_canonical<R>(e);
+    soa_st<8>(a.out_e, n, i, ec.v);
+    Fr<C> skm = fe_from_limbs<R>(a.sk);
+    Fr<C> spe = fe_add<R>(skm, e);
+    if (fe_is_zero<R>(spe)) { a.status[i] = -20; return; }     // sign.rs:129 unwrap
+    Fr<C> inv = fe_inv<R>(spe);                                 // Montgomery
+    Fr<C> invc = fe_to_canonical<R>(inv);
+    soa_st<8>(a.fscal, n, i, invc.v);
+    Fr<C> di = fe_mul<R>(dom, invc);                            // (dom R) inv / R = dom*inv canonical
+    soa_st<8>(a.fscal + (size_t)8 * n, n, i, di.v);
+    for (int j = 0; j < l; j++) {
+        Fr<C> m = fr_load_canon<C>(a.msgs + (size_t)j * 8 * n, n, i);
+        Fr<C> mi = fe_mul<R>(inv, m);
+        soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, mi.v);
+    }
+}
 template <class C>
 struct SgScalars {
     static __host__ __device__ void run(const SgArgs<C>& a, size_t i) {
-        using R = typename C::FrP;
         if (a.status[i] != ST_PENDING) return;
-        const size_t n = a.n;
-        Fr<C> dom = domain_from_header<C>(a.cc->hash, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
-        // e = hash_to_scalar(sk || m_1 .. m_L || domain)   (sign.rs:90-118)
-        Sha256 s;
-        xmd48_begin(s);
-        sha256_limbs_be8(s, a.sk);
-        for (int j = 0; j < a.L; j++) {
-            uint32_t m[8];
-            soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
-            sha256_limbs_be8(s, m);
-        }
-        sha256_fr_be<C>(s, dom);
-        uint32_t okm[12];
-        xmd48_finish(s, a.cc->hash.dst_h2s, a.cc->hash.dst_h2s_len, okm);
-        Fr<C> e = fr_from_okm<C>(okm);
-        Fr<C> ec = fe_to_canonical<R>(e);
-        soa_st<8>(a.out_e, n, i, ec.v);
-        Fr<C> skm = fe_from_limbs<R>(a.sk);
-        Fr<C> spe = fe_add<R>(skm, e);
-        if (fe_is_zero<R>(spe)) { a.status[i] = -20; return; }     // sign.rs:129 unwrap
-        Fr<C> inv = fe_inv<R>(spe);                                 // Montgomery
-        Fr<C> invc = fe_to_canonical<R>(inv);
-        soa_st<8>(a.fscal, n, i, invc.v);
-        Fr<C> di = fe_mul<R>(dom, invc);                            // (dom R) inv / R = dom*inv canonical
-        soa_st<8>(a.fscal + (size_t)8 * n, n, i, di.v);
-        for (int j = 0; j < a.L; j++) {
-            Fr<C> m = fr_load_canon<C>(a.msgs + (size_t)j * 8 * n, n, i);
-            Fr<C> mi = fe_mul<R>(inv, m);
-            soa_st<8>(a.fscal + (size_t)(2 + j) * 8 * n, n, i, mi.v);
-        }
+        sg_scalars_item<C>(a, i, a.cc->hash, a.L);
+    }
+};
+// Mixed lengths (bbs_ctx_set_mixed_lengths_gen): as PvScalarsMixed (stages_pv.hpp) -- the domain from the prefix of the item's
+// own length, e over its l messages, its scalars in fscal[2 .. 2 + l) and zeros WRITTEN for the bases behind them (also for an
+// item that ends here with -20: nothing reads its scalars, and nothing stale stays behind).  The HashCtx is read through the
+// per-lane pointer and passed on by reference, never copied into a local.
+template <class C>
+struct SgScalarsMixed {
+    static __host__ __device__ void run(const MixedScalarArgs<SgArgs<C>>& m, size_t i) {
+        if (m.a.status[i] != ST_PENDING) return;
+        const int l = (int)m.len[i];
+        sg_scalars_item<C>(m.a, i, m.pref[l], l);
+        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
     }
 };
 

@@ -391,6 +391,12 @@ class Engine:
         count 0 .. L, each decided as a context made for its own count would (jobs created afterwards)."""
         self._chk(self.lib.bbs_ctx_set_mixed_lengths(self.h, 1 if on else 0), "bbs_ctx_set_mixed_lengths")
 
+    def set_mixed_lengths_gen(self, on: bool):
+        """bbs_ctx_set_mixed_lengths_gen: the sign / proof_gen batches of this engine accept items of any message count 0 .. L,
+        each giving the bytes a context made for its own count would (jobs created afterwards); independent of
+        set_mixed_lengths."""
+        self._chk(self.lib.bbs_ctx_set_mixed_lengths_gen(self.h, 1 if on else 0), "bbs_ctx_set_mixed_lengths_gen")
+
     def set_keyed_mixed_lengths(self, on: bool):
         """bbs_ctx_set_keyed_mixed_lengths: the keyed verify / proof_verify batches of this engine accept item i under its own
         key with its own message count 0 .. L (jobs created afterwards); independent of set_mixed_lengths."""

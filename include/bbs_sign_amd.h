@@ -136,7 +136,7 @@ size_t bbs_device_free_bytes(int device_id);          /* device memory free righ
 int bbs_ctx_create(int curve, int device_id, bbs_ctx** out);
 void bbs_ctx_destroy(bbs_ctx* ctx);
 /* device memory of the context's tables (fixed-base window tables, line tables, constants, the per-length domain
- * prefixes of bbs_ctx_set_mixed_lengths and the per-(key, length) prefixes of bbs_ctx_set_keyed_mixed_lengths), in bytes */
+ * prefixes of bbs_ctx_set_mixed_lengths / bbs_ctx_set_mixed_lengths_gen and the per-(key, length) prefixes of bbs_ctx_set_keyed_mixed_lengths), in bytes */
 size_t bbs_ctx_table_bytes(const bbs_ctx* ctx);
 
 /* window width (bits) of the fixed-base tables, 4..22, or 0 (THE DEFAULT) = chosen at bbs_ctx_set_generators from the
@@ -197,9 +197,27 @@ int bbs_ctx_set_fixed_base_tree(bbs_ctx* ctx, int enabled);
  * bbs_ctx_table_bytes, rebuilt by bbs_ctx_set_generators and the key setters.  Applies to jobs created afterwards; a job keeps
  * what it was created with.
  * NOT covered: the keyed entry points look at bbs_ctx_set_keyed_mixed_lengths (below), not at this switch; with this switch on
- * and that one off they return BBS_E_STATE and enqueue nothing; sign and proof_gen are unchanged and keep deciding l != L as -1 whatever the switch
- * says; bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
+ * and that one off they return BBS_E_STATE and enqueue nothing; sign and proof_gen do not look at this switch (theirs is bbs_ctx_set_mixed_lengths_gen, below) and keep deciding
+ * l != L as -1 whatever this one says; bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
+/* Mixed message counts for the PRODUCING side (off by default; with it off nothing changes anywhere).  The reference picks its
+ * generators by the item's own count in sign and proof_gen too (src/sign.rs:44-49, src/proof_gen.rs:91-96).  enabled = 1: every
+ * sign and proof_gen entry point of the context -- bbs_core_sign_*, bbs_sign_octets_*, bbs_sign_wire_*, bbs_core_proof_gen_*,
+ * bbs_proof_gen_octets_*, bbs_proof_gen_wire_*; _upload, _batch and _submit; both job forms -- takes item i with its own message
+ * count l_i, 0 <= l_i <= L.  The status AND the output bytes of item i are, bit for bit, what a context made with
+ * generators[0 .. l_i] (same key, api_id, modes and random scalars) gives that item alone: the checks and their order are
+ * unchanged, only "l != L" becomes "l > L" (still -1); -2, -3, -4, -20, -21, -23 and -40 are decided against the item's own
+ * l_i -- a disclosed index with l_i <= index < L is -3.  proof_gen delivers exactly l_i - r_i commitments (an octet string of
+ * exactly the fixed-length proof's size); the contract on the number of random scalars, 5 + l_i - r_i (BBS_E_ARG for the call),
+ * was per item already.
+ * Independent of bbs_ctx_set_mixed_lengths and bbs_ctx_set_keyed_mixed_lengths: verify and proof_verify never look at this
+ * switch.  It shares the L + 1 domain prefixes with bbs_ctx_set_mixed_lengths: they are built while either switch is on, counted
+ * ONCE in bbs_ctx_table_bytes, and rebuilt by bbs_ctx_set_generators, bbs_ctx_set_secret_key and bbs_ctx_set_public_key, so
+ * every order of set-up ends in the same outputs.  Applies to jobs created afterwards; a job keeps the stages it was created
+ * with.  BBS_E_ARG for a NULL ctx.
+ * NOT covered: keyed forms (there is no set of secret keys); bbs_issuer and bbs_pool keep one context per count; the C++ wrapper
+ * and the Rust shim do not expose the switch. */
+int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
 /* Mixed message counts for the KEYED entry points (off by default; with it off nothing changes anywhere, the BBS_E_STATE above
  * included).  enabled = 1: every keyed verify and proof_verify job created from now on -- the eight bbs_*_keyed_* exports: core
  * and wire forms, _submit and _batch, both job forms -- takes item i under its own key key_index[i] AND with its own count l_i,
