@@ -120,6 +120,15 @@ SIGNATURES = {
     "bbs_core_verify_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
     "bbs_verify_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_verify_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    # keyed proof_gen: as the un-keyed forms, key_index after n
+    "bbs_core_proof_gen_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                             c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_proof_gen_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                            c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p]),
+    "bbs_proof_gen_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p,
+                                             c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_proof_gen_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p,
+                                            c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
     "bbs_sign_wire_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_sign_wire_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),
     "bbs_sign_octets_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),

@@ -427,6 +427,39 @@ def proof_verify_many_issuers(items: Sequence[tuple]) -> list:
                              kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]))
 
 
+def proof_gen_many_issuers(items: Sequence[tuple]) -> list:
+    """proof_gen for many items ``(pk, signature, header, ph, messages, disclosed_indexes[, random_scalars])`` of ANY issuers
+    and ANY message counts, in ONE device call per (curve, device, lib_path): the cached engine of verify_many_issuers (its
+    keys are registered once, whichever side meets them first), through bbs_proof_gen_wire_keyed_batch.  Entry i is the Proof
+    ``proof_gen(*items[i])`` returns with the same random scalars (drawn here, as there, where an item has none), or the
+    BbsError it raises (returned, not raised: the other items stand).  A signature that cannot be written as octets keeps the
+    codec's error; a wrong number of random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as in
+    proof_gen_many; a ``pk`` the library refuses gives ``BbsError(-44)``, the divergence verify_many_issuers describes."""
+    out: list = [None] * len(items)
+    groups: Dict[tuple, List[int]] = {}
+    for i, it in enumerate(items):
+        groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
+    for (curve, device, lib_path), group in groups.items():
+        ie = _issuer_engine(curve, device, lib_path, max(len(items[i][4]) for i in group), [items[i][0].pk for i in group])
+        octs, idx = [], []
+        for i in group:
+            try:
+                octs.append(signature_to_octets(curve, items[i][1], lib_path))
+                idx.append(i)
+            except BbsError as e:
+                out[i] = e
+        if not idx:
+            continue
+        its = [items[i] for i in idx]
+        rnds = [list(it[6]) if len(it) > 6 and it[6] is not None else
+                calculate_random_scalars(curve, max(5 + len(it[4]) - len(it[5]), 0)) for it in its]
+        po, st = ie.eng.proof_gen_wire_keyed_batch([ie.index[ie.name(it[0].pk)] for it in its], octs, [list(it[4]) for it in its],
+                                                   [list(it[5]) for it in its], rnds, [it[2] for it in its], [it[3] for it in its])
+        for i, o, s in zip(idx, po, st):
+            out[i] = BbsError(int(s)) if s < 0 else octets_to_proof(curve, o, lib_path)
+    return out
+
+
 # ---------------------------------------------------------------------------------- wire codec
 def _curve_id(curve: str) -> int:
     return 0 if curve == "bls12_381" else 1

@@ -96,7 +96,10 @@ static int upload(bbs_ctx* ctx, size_t n, const VfIn& in, bbs_job** job) {
     return with_curve(ctx, [&](auto* c) { return vf_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
 }
 static int upload(bbs_ctx* ctx, size_t n, const SgIn& in, bbs_job** job) { return with_curve(ctx, [&](auto* c) { return sg_upload(c, n, in, job); }); }
-static int upload(bbs_ctx* ctx, size_t n, const PgIn& in, bbs_job** job) { return with_curve(ctx, [&](auto* c) { return pg_upload(c, n, in, job); }); }
+template <bool KEYED = false>
+static int upload(bbs_ctx* ctx, size_t n, const PgIn& in, bbs_job** job) {
+    return with_curve(ctx, [&](auto* c) { return pg_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
+}
 
 // ---- host-side helpers shared by both curves --------------------------------------------------
 template <class C>
@@ -371,6 +374,24 @@ static int verify_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index,
     if (int rc = empty_raw_batch(msg_byte_off, msg_item_off, n)) return rc;
     return verify_submit<KEYED>(ctx, n, VfIn{.msg_off = msg_item_off, .headers = headers, .hdr_off = hdr_off, .signature_octets = signature_octets,
                                              .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off, .key_index = key_index}, status, job_out);
+}
+
+// the reference's PUBLIC proof_gen (src/proof_gen.rs:78-113) in one call: signature octets and raw messages in, proof octets out
+template <bool KEYED>
+static int proof_gen_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
+                                 const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio,
+                                 const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                 uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out || !oct_off_out || (n && (!octets_out || !sig_octets || !msg_item_off))) return BBS_E_ARG;
+    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
+    if (rc) return rc;
+    bbs_job* job = nullptr;
+    rc = upload<KEYED>(ctx, n, PgIn{.msg_off = msg_item_off, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd, .rnd_off = rno, .headers = h,
+                                    .hdr_off = ho, .ph = ph, .ph_off = pho, .signature_octets = sig_octets, .msg_bytes = msg_bytes,
+                                    .msg_byte_off = msg_byte_off, .key_index = key_index}, &job);
+    if (rc) return rc;
+    if ((rc = job->set_octet_form())) { delete job; return rc; }
+    return submit_with_results(job, status, octets_out, nullptr, oct_off_out, job_out);
 }
 
 #pragma GCC visibility push(default)
@@ -810,6 +831,25 @@ int bbs_core_proof_gen_submit(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const
     if (rc) return rc;
     return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
 }
+// keyed proof_gen (keyed.hpp PgScalarsKeyed; op_pg.hpp): item i under key key_index[i] of the context's key set
+int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
+                                    const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
+                                    const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                    uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    bbs_job* job = nullptr;
+    int rc = upload<true>(ctx, n, PgIn{.signatures = sigs, .messages = m, .msg_off = mo, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd,
+                                       .rnd_off = rno, .headers = h, .hdr_off = ho, .ph = ph, .ph_off = pho, .key_index = key_index}, &job);
+    if (rc) return rc;
+    return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
+}
+int bbs_core_proof_gen_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
+                                   const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
+                                   const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                   uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_proof_gen_keyed_submit(ctx, n, key_index, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho, pf_out, cm_out, cmo_out, status, &job), job);
+}
 // sign / proof_gen to the WIRE: the results leave the device as octet strings (compression on the device)
 int bbs_sign_octets_submit(bbs_ctx* ctx, size_t n, const uint8_t* m, const uint64_t* mo, const uint8_t* h, const uint64_t* ho,
                            uint8_t* sig_octets_out, int8_t* status, bbs_job** job_out) {
@@ -848,16 +888,23 @@ int bbs_proof_gen_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets,
                               const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
                               const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
                               uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out || !oct_off_out || (n && (!octets_out || !sig_octets || !msg_item_off))) return BBS_E_ARG;
-    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
-    if (rc) return rc;
+    return proof_gen_wire_submit<false>(ctx, n, nullptr, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho,
+                                        octets_out, oct_off_out, status, job_out);
+}
+int bbs_proof_gen_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
+                                    const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio,
+                                    const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                    uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
+    return proof_gen_wire_submit<true>(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho,
+                                       octets_out, oct_off_out, status, job_out);
+}
+int bbs_proof_gen_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
+                                   const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio,
+                                   const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                   uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status) {
     bbs_job* job = nullptr;
-    rc = upload(ctx, n, PgIn{.msg_off = msg_item_off, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd, .rnd_off = rno, .headers = h,
-                             .hdr_off = ho, .ph = ph, .ph_off = pho, .signature_octets = sig_octets, .msg_bytes = msg_bytes,
-                             .msg_byte_off = msg_byte_off}, &job);
-    if (rc) return rc;
-    if ((rc = job->set_octet_form())) { delete job; return rc; }
-    return submit_with_results(job, status, octets_out, nullptr, oct_off_out, job_out);
+    return wait_and_free(bbs_proof_gen_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho,
+                                                         octets_out, oct_off_out, status, &job), job);
 }
 int bbs_proof_gen_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                              const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,

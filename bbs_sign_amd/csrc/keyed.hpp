@@ -54,6 +54,16 @@ struct VfScalarsKeyed {
     }
 };
 
+// keyed proof_gen (bbs_*proof_gen*_keyed_*): the key enters a proof in calculate_domain alone (no pairing, no W), so this stage
+// is all a keyed producing job has of its own; PgBPart .. PgEmit follow unchanged
+template <class C>
+struct PgScalarsKeyed {
+    static __host__ __device__ void run(const KeyedScalarArgs<C, PgArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        pg_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
+    }
+};
+
 // Keyed jobs of mixed message counts (bbs_ctx_set_keyed_mixed_lengths): item i under its own key kidx[i] with its own count
 // len[i] <= L (written by the MIXED ingest bodies, which such a job launches where a keyed job launches the fixed-length ones;
 // KeyGate follows unchanged).  The domain starts from the prefix of THAT key and THAT length, pref[kidx * stride + l] (runtime.hpp
@@ -80,6 +90,17 @@ struct VfScalarsKeyedMixed {
         const int l = (int)k.len[i];
         vf_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
         mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
+    }
+};
+// (zeros in BOTH scalar arrays, as PgScalarsMixed: B's sum and T2's run over the same bases)
+template <class C>
+struct PgScalarsKeyedMixed {
+    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, PgArgs<C>>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        const int l = (int)k.len[i];
+        pg_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
+        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
+        mixed_zero_scalars(k.a.fscal2, k.a.n, i, l, k.a.L);
     }
 };
 

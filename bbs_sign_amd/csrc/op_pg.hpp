@@ -11,7 +11,8 @@ struct PgJob : JobBase<C> {
     PgIngestArgs<C> ingest{};
     VfOctArgs<C> oct{};               // signature octets in (wire form) only
     MsgHashArgs mh{};                 // raw-message form only
-    MixedJob mx{};                    // mixed-length form only (bbs_ctx_set_mixed_lengths_gen)
+    KeyedJob<C> kj{};                 // keyed form only (its pairing order stays empty: a proof is derived without a pairing)
+    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths_gen, bbs_ctx_set_keyed_mixed_lengths)
     // The proofs come off the device in the caller's layout (stage PgEmit): records, the m^ of the undisclosed messages
     // in ascending index order (L slots per item, the first ucount[i] used) and those counts.  Host side of a delivery:
     // one copy of the records, one contiguous copy per item of its commitments, the running offsets.
@@ -86,12 +87,27 @@ struct PgJob : JobBase<C> {
     }
 };
 
-template <class C>
+// KEYED (bbs_*proof_gen*_keyed_*, instantiated in tu_pgk_*.hip): item i is derived under key key_index[i] of the context's key
+// set (keyed.hpp).  The key enters through the domain alone (proof_gen.rs:78-113 -> calculate_domain): the scalar stage reads
+// the key's midstate, or the prefix of (key, length), and every other stage is the single-key job's.  The context's single
+// public key is neither needed nor looked at.
+template <class C, bool KEYED>
 int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
-    if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
+    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
+    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
+    if constexpr (KEYED) {
+        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
+        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
+        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
+        if (ctx->mixed_lengths_gen && !keyed_mixed) return BBS_E_STATE;
+        if (n && !in.key_index) return BBS_E_ARG;
+    } else {
+        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
+    }
     const bool wire = in.signature_octets != nullptr, raw = in.msg_byte_off != nullptr;
     if (!out || (n && ((!in.signatures && !wire) || !in.msg_off || !in.didx_off || !in.rnd_off || !in.random_scalars))) return BBS_E_ARG;
     const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
@@ -124,8 +140,12 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
         if (bad) continue;                                            // -> InvalidDisclosedIndex
         if (nr != 5 + l - r) return BBS_E_ARG;
     }
-    if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm)) return rc0;
+    std::vector<uint32_t> kwords;     // keyed: the key indexes, in the staging image
+    size_t kwords_at = 0;
+    if constexpr (KEYED) keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
+    if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
+    if constexpr (KEYED) job->kj.kidx = reinterpret_cast<const uint32_t*>(dimg + kwords_at);
     auto d64 = [&](size_t at) { return reinterpret_cast<const uint64_t*>(dimg + at); };
     auto d32 = [&](size_t at) { return reinterpret_cast<const uint32_t*>(dimg + at); };
     int rc = BBS_OK;
@@ -201,12 +221,22 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     a.status = job->d_status.template as<int8_t>();
     ia.status0 = job->d_status0.template as<int8_t>();
     // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
-    const bool mixed = ctx->mixed_lengths_gen;
+    const bool mixed = !KEYED && ctx->mixed_lengths_gen;
+    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED bodies serve both
     if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (mixed && rt::launch<PgIngestMixed<C>>(job->stream(), MixedIngestArgs<PgIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-    if (!mixed && rt::launch<PgIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if (mixed_ingest && rt::launch<PgIngestMixed<C>>(job->stream(), MixedIngestArgs<PgIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
+    if (!mixed_ingest && rt::launch<PgIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if constexpr (KEYED) {
+        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
+    }
     PgJob<C>* j = job.get();
-    if (mixed)
+    if constexpr (KEYED) {
+        if (keyed_mixed)
+            j->stages.push_back({"pg_scalars_keyed_mixed", [j]() { return rt::launch<PgScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, PgArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
+        else
+            j->stages.push_back({"pg_scalars_keyed", [j]() { return rt::launch<PgScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PgArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
+    } else if (mixed)
         j->stages.push_back({"pg_scalars_mixed", [j]() { return rt::launch<PgScalarsMixed<C>>(j->stream(), MixedScalarArgs<PgArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
     else
         j->stages.push_back({"pg_scalars", [j]() { return rt::launch<PgScalars<C>>(j->stream(), j->a, j->n); }});
@@ -214,7 +244,7 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     j->stages.push_back({"pg_b_combine", [j]() { return rt::launch<PgBCombine<C>>(j->stream(), j->a, j->n); }});
     if (j->a.ctab) j->stages.push_back({"pg_tables", [j]() { return rt::launch<PgTables<C>>(j->stream(), j->a, j->n * 2); }});
     j->stages.push_back({"pg_var_parts", [j]() { return rt::launch<PgVarPart<C>>(j->stream(), j->a, j->n * (size_t)j->a.nvar); }});
-    if (mixed) {
+    if (mixed_ingest) {
         j->stages.push_back({"pg_finalize_mixed", [j]() { return rt::launch<PgFinalizeMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
         j->stages.push_back({"pg_emit_mixed", [j]() { return rt::launch<PgEmitMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
     } else {

@@ -65,12 +65,13 @@ struct PgIn {
     const uint8_t* signature_octets = nullptr;
     const uint8_t* msg_bytes = nullptr;
     const uint64_t* msg_byte_off = nullptr;
+    const uint32_t* key_index = nullptr;        // KEYED only: item i is derived under key key_index[i] of the context's key set
 };
 // declarations of the per-operation templates (defined in op_*.hpp, instantiated in tu_*.hip)
 template <class C, bool KEYED = false> int pv_upload(Ctx<C>*, size_t, const PvIn&, bbs_job**);
 template <class C, bool KEYED = false> int vf_upload(Ctx<C>*, size_t, const VfIn&, bbs_job**);
 template <class C> int sg_upload(Ctx<C>*, size_t, const SgIn&, bbs_job**);
-template <class C> int pg_upload(Ctx<C>*, size_t, const PgIn&, bbs_job**);
+template <class C, bool KEYED = false> int pg_upload(Ctx<C>*, size_t, const PgIn&, bbs_job**);
 template <class C> int h2s_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
 template <class C> int msm_batch(Ctx<C>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 template <class C> int selftest_f12(Ctx<C>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
@@ -92,7 +93,9 @@ extern template int vf_upload<BnCurve, true>(Ctx<BnCurve>*, size_t, const VfIn&,
 extern template int sg_upload<BlsCurve>(Ctx<BlsCurve>*, size_t, const SgIn&, bbs_job**);
 extern template int sg_upload<BnCurve>(Ctx<BnCurve>*, size_t, const SgIn&, bbs_job**);
 extern template int pg_upload<BlsCurve>(Ctx<BlsCurve>*, size_t, const PgIn&, bbs_job**);
+extern template int pg_upload<BlsCurve, true>(Ctx<BlsCurve>*, size_t, const PgIn&, bbs_job**);
 extern template int pg_upload<BnCurve>(Ctx<BnCurve>*, size_t, const PgIn&, bbs_job**);
+extern template int pg_upload<BnCurve, true>(Ctx<BnCurve>*, size_t, const PgIn&, bbs_job**);
 extern template int Ctx<BlsCurve>::set_generators(const uint8_t*, size_t, const uint8_t*, size_t);
 extern template int h2s_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
 extern template int msm_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);

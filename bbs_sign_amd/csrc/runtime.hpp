@@ -1429,6 +1429,20 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJo
     kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
     kj.pair.keys = kj.keys; kj.pair.n_uni = nu; kj.pair.n_slots = nu + nm;
 }
+// the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
+template <class C, class J>
+void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words) {
+    const auto ks = ctx->keys;
+    j->key_set = ks;
+    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
+    words.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = key_index[i];
+        words[i] = (k < nk && ks->status[k] == 1) ? k : KEY_NONE;
+    }
+    kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
+    kj.pair.keys = kj.keys; kj.pair.n_uni = 0; kj.pair.n_slots = 0;
+}
 // the device half: d = the words' place in the device copy of the staging image
 template <class C>
 void keyed_bind(KeyedJob<C>& kj, size_t n, const uint32_t* d) {

@@ -759,6 +759,83 @@ class Engine:
         job._decode = lambda: (self._dec_proofs(pf, cm, cmo, st, n), st[:n])
         return job
 
+    # keyed proof_gen: item i under key key_index[i] of the key set (set_public_keys / add_public_keys*); an item with an
+    # unknown or refused key has status -44 and no output.  The context's single public key is not needed.
+    def core_proof_gen_keyed_submit(self, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
+        """bbs_core_proof_gen_keyed_submit; ``job.wait()`` then ``job.result`` and ``job.output()`` -> (proofs | None, statuses)."""
+        n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)
+        ki, kip = self._key_index(key_index, n)
+        total = sum(len(m) for m in messages)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        pf = np.zeros(max(n, 1) * (6 * self.fpb + 128), dtype=np.uint8)
+        cm = np.zeros(max(total, 1) * 32, dtype=np.uint8)
+        cmo = np.zeros(n + 1, dtype=np.uint64)
+        j = ctypes.c_void_p()
+        self._chk(self.lib.bbs_core_proof_gen_keyed_submit(self.h, n, kip, *args, _u8(pf), _u8(cm), _u64(cmo),
+                                                           st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), "bbs_core_proof_gen_keyed_submit")
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._decode = lambda: (self._dec_proofs(pf, cm, cmo, st, n), st[:n])
+        return job
+
+    def core_proof_gen_keyed_batch(self, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None):
+        """bbs_core_proof_gen_keyed_batch -> (proofs | None, statuses)."""
+        n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)
+        ki, kip = self._key_index(key_index, n)
+        total = sum(len(m) for m in messages)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        pf = np.zeros(max(n, 1) * (6 * self.fpb + 128), dtype=np.uint8)
+        cm = np.zeros(max(total, 1) * 32, dtype=np.uint8)
+        cmo = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(self.lib.bbs_core_proof_gen_keyed_batch(self.h, n, kip, *args, _u8(pf), _u8(cm), _u64(cmo),
+                                                          st.ctypes.data_as(_lib.c_i8p)), "bbs_core_proof_gen_keyed_batch")
+        return self._dec_proofs(pf, cm, cmo, st, n), st[:n]
+
+    def _pg_wire_keyed(self, fn, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers, phs, tail=()):
+        n = len(sig_octets)
+        ki, kip = self._key_index(key_index, n)
+        ob, bad = self._sig_octets(sig_octets)
+        mb, mbo, mio = self._raw_msgs(messages_raw)
+        di, dio = self._indexes(disclosed_idx)
+        rs, ro = self._scalars(random_scalars)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        pb, po = _ragged_bytes(phs if phs is not None else [b""] * n)
+        cap = sum(3 * self.fpb + 32 * (4 + len(m)) for m in messages_raw)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        oc = np.zeros(max(cap, 1), dtype=np.uint8)
+        oo = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(getattr(self.lib, fn)(self.h, n, kip, _u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u64(di), _u64(dio), _u8(rs), _u64(ro),
+                                        _u8(hb), _u64(ho), _u8(pb), _u64(po), _u8(oc), _u64(oo), st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+
+        fix = self._wrong_length_fixup(bad)
+
+        def decode():
+            out = [oc[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(n)]
+            if fix:
+                fix(st)
+            for i in bad:
+                out[i] = b""
+            return out, st[:n]
+        return n, st, fix, decode
+
+    def proof_gen_wire_keyed_batch(self, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers=None, phs=None):
+        """bbs_proof_gen_wire_keyed_batch: the reference's public proof_gen under many issuer keys -- signature octets, raw
+        messages, indexes and the random scalars in, (proof octet strings, statuses) out."""
+        n, st, fix, decode = self._pg_wire_keyed("bbs_proof_gen_wire_keyed_batch", key_index, sig_octets, messages_raw, disclosed_idx,
+                                            random_scalars, headers, phs)
+        return decode()
+
+    def proof_gen_wire_keyed_submit(self, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
+        """bbs_proof_gen_wire_keyed_submit; ``job.wait()`` then ``job.output()`` -> (proof octet strings, statuses)."""
+        j = ctypes.c_void_p()
+        n, st, fix, decode = self._pg_wire_keyed("bbs_proof_gen_wire_keyed_submit", key_index, sig_octets, messages_raw, disclosed_idx,
+                                            random_scalars, headers, phs, (ctypes.byref(j),))
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._fixup = (lambda: fix(st)) if fix else None
+        job._decode = decode
+        return job
+
     def core_proof_gen_upload(self, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
         n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)
         j = ctypes.c_void_p()

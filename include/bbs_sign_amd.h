@@ -215,8 +215,9 @@ int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
  * ONCE in bbs_ctx_table_bytes, and rebuilt by bbs_ctx_set_generators, bbs_ctx_set_secret_key and bbs_ctx_set_public_key, so
  * every order of set-up ends in the same outputs.  Applies to jobs created afterwards; a job keeps the stages it was created
  * with.  BBS_E_ARG for a NULL ctx.
- * NOT covered: keyed forms (there is no set of secret keys); bbs_issuer and bbs_pool keep one context per count; the C++ wrapper
- * and the Rust shim do not expose the switch. */
+ * NOT covered: the keyed proof_gen entry points look at bbs_ctx_set_keyed_mixed_lengths (below), not at this switch; with this
+ * switch on and that one off they return BBS_E_STATE and enqueue nothing; keyed sign does not exist (there is no set of secret
+ * keys); bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
 /* Mixed message counts for the KEYED entry points (off by default; with it off nothing changes anywhere, the BBS_E_STATE above
  * included).  enabled = 1: every keyed verify and proof_verify job created from now on -- the eight bbs_*_keyed_* exports: core
@@ -236,7 +237,9 @@ int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
  * Independent of bbs_ctx_set_mixed_lengths: single-key jobs never look at this switch, keyed jobs look at that one only to
  * return BBS_E_STATE when it is on and this one is off.  Applies to jobs created afterwards; a job keeps the stages, the key set
  * and the prefixes it was created with, whatever is switched, appended or replaced later.  BBS_E_ARG for a NULL ctx.
- * NOT covered: keyed sign / proof_gen do not exist; bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust
+ * Keyed proof_gen (bbs_*proof_gen*_keyed_*, below) takes mixed counts by this switch too: the same prefixes, and the output
+ * bytes of item i are those of bbs_ctx_set_mixed_lengths_gen on that single-key context.
+ * NOT covered: keyed sign does not exist; bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust
  * shim do not expose the switch. */
 int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled);
 
@@ -456,6 +459,54 @@ int bbs_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_ind
 int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
                                 const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                                 const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+/* Keyed forms of bbs_core_proof_gen_* and bbs_proof_gen_wire_*: ONE context derives proofs from signatures of MANY issuers.
+ * The reference takes the public key per call (src/proof_gen.rs:78-113) and uses it in calculate_domain alone -- no pairing,
+ * no W -- so a keyed item reads its key's domain midstate from the key set the keyed verify entry points use, and everything
+ * else is the single-key job.  The arguments are those of the un-keyed form plus key_index (n entries) after n.  For an item
+ * whose key_index names an accepted key (the identity key is one) the status AND the output bytes are, bit for bit, what the
+ * un-keyed form gives that item alone on a context with the same generators, api_id, window bits, modes and random scalars and
+ * that key set by bbs_ctx_set_public_key; for an index >= the set's size or naming a refused key the status is
+ * BBS_ST_UNKNOWN_KEY whatever the other checks decided, and the item has no output (zero record, no octet string).  The
+ * context's single public key is not needed and not looked at.  With bbs_ctx_set_keyed_mixed_lengths on, item i also has its
+ * own count l_i <= L and its bytes are those of a single-key context made with generators[0 .. l_i].
+ * BBS_E_STATE without generators; without a key set (unless bbs_ctx_set_keyed_mixed_lengths is on: then a missing set is the
+ * empty set and every item is BBS_ST_UNKNOWN_KEY); and on a context with bbs_ctx_set_mixed_lengths_gen on unless
+ * bbs_ctx_set_keyed_mixed_lengths is on too.  BBS_E_ARG for a NULL key_index with n > 0, a NULL status, and -- whatever the
+ * item's key -- for an item whose number of random scalars is not 5 + l_i - r_i.  Both job forms; the _submit forms return
+ * ordinary jobs.  A key costs its full entry (~30 KB on BLS12-381, the W line table included) although proof_gen reads only the
+ * midstate: there is no cheaper registration for proof-only keys.
+ * NOT covered: the octets (non-wire) keyed form and an _upload form; keyed sign does not exist (it would need a set of secret
+ * keys on the device); bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim do not route through these. */
+int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
+                                    const uint8_t* messages, const uint64_t* msg_off,
+                                    const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                    const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                    const uint8_t* headers, const uint64_t* hdr_off,
+                                    const uint8_t* ph, const uint64_t* ph_off,
+                                    uint8_t* proofs_fixed_out, uint8_t* commitments_out,
+                                    uint64_t* commit_off_out, int8_t* status, bbs_job** job_out);
+int bbs_core_proof_gen_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
+                                   const uint8_t* messages, const uint64_t* msg_off,
+                                   const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                   const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                   const uint8_t* headers, const uint64_t* hdr_off,
+                                   const uint8_t* ph, const uint64_t* ph_off,
+                                   uint8_t* proofs_fixed_out, uint8_t* commitments_out,
+                                   uint64_t* commit_off_out, int8_t* status);
+int bbs_proof_gen_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
+                                    const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                    const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                    const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                    const uint8_t* headers, const uint64_t* hdr_off,
+                                    const uint8_t* ph, const uint64_t* ph_off,
+                                    uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out);
+int bbs_proof_gen_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
+                                   const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                   const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                   const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                   const uint8_t* headers, const uint64_t* hdr_off,
+                                   const uint8_t* ph, const uint64_t* ph_off,
+                                   uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status);
 
 /* The reference's PUBLIC sign (src/sign.rs:32-60): raw messages in, signature octet strings out (as bbs_sign_octets_*). */
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
