@@ -129,7 +129,15 @@ SIGNATURES = {
                                              c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_proof_gen_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p,
                                             c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
-    "bbs_sign_wire_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
+    # keyed sign: the signing key set, and the un-keyed forms with key_index after n
+    "bbs_ctx_set_secret_keys": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, c_i8p]),
+    "bbs_ctx_add_secret_keys": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, c_i8p, c_u32p]),
+    "bbs_ctx_secret_key_count": (sz, [vp]),
+    "bbs_core_sign_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_sign_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),
+    "bbs_sign_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_sign_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),
+    "bbs_sign_wire_submit": (ci,[vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_sign_wire_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),
     "bbs_sign_octets_submit": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_sign_octets_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_i8p]),

@@ -346,6 +346,7 @@ class _IssuerEngine:
     def __init__(self, curve, device, lib_path, L, keys=()):
         self.L = L
         self.index: Dict[object, int] = {}
+        self.sk_index: Dict[int, int] = {}          # sign_many_issuers: secret key -> its index in the signing set
         self.eng = Engine(curve, device=device, lib_path=lib_path, window_bits=4 if lib_path is not None else None)
         self.eng.set_generators(create_generators(curve, L + 1, lib_path), api_id(curve))
         self.eng.set_keyed_mixed_lengths(True)
@@ -372,6 +373,21 @@ class _IssuerEngine:
         by_index = sorted(self.index.items(), key=lambda kv: kv[1])
         return [None if name is None else tuple(name) for name, _ in by_index]
 
+    def register_secret(self, sks):
+        """Appends the secret keys that are not in the signing set yet (in one call, bbs_ctx_add_secret_keys); ``sk_index`` has
+        them afterwards.  The public half of a key gets the same index, so what was signed here verifies here without another
+        registration.  A scalar the library refuses (>= r) keeps its index: its items get BBS_ST_UNKNOWN_KEY."""
+        new = []
+        for sk in sks:
+            if sk not in self.sk_index and sk not in new:
+                new.append(sk)
+        if new:
+            st, pks, first = self.eng.add_secret_keys(new)
+            for k, sk in enumerate(new):
+                self.sk_index[sk] = first + k
+                if st[k] == 1:
+                    self.index.setdefault(self.name(pks[k]), first + k)
+
 
 _issuer_cache: Dict[tuple, _IssuerEngine] = {}
 
@@ -384,11 +400,34 @@ def _issuer_engine(curve, device, lib_path, L, pks) -> _IssuerEngine:
     ie = _issuer_cache.get(who)
     if ie is None or ie.L < L:
         old = ie.keys_in_order() if ie is not None else []
+        old_sks = sorted(ie.sk_index, key=ie.sk_index.get) if ie is not None else []
         if ie is not None:
             _issuer_cache.pop(who).eng.close()
         ie = _issuer_cache[who] = _IssuerEngine(curve, device, lib_path, L, old)
+        ie.register_secret(old_sks)
     ie.register(pks)
     return ie
+
+
+def sign_many_issuers(items: Sequence[tuple]) -> list:
+    """SecretKey.sign for many items ``(sk, header, messages)`` of ANY issuers and ANY message counts, in ONE device call per
+    (curve, device, lib_path): the cached engine of verify_many_issuers / proof_gen_many_issuers, whose signing key set grows by
+    appending (a key is registered once per engine), through bbs_sign_wire_keyed_batch.  Entry i is the Signature
+    ``items[i][0].sign(items[i][2], items[i][1])`` returns, or the BbsError it raises (returned, not raised: the other items
+    stand).  One divergence: a secret key that is not below the group order is registered as a refused key, and its items get
+    ``BbsError(-44)`` (BBS_ST_UNKNOWN_KEY), where the one-item form fails with a BbsRuntimeError from bbs_ctx_set_secret_key."""
+    out: list = [None] * len(items)
+    groups: Dict[tuple, List[int]] = {}
+    for i, it in enumerate(items):
+        groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
+    for (curve, device, lib_path), idx in groups.items():
+        its = [items[i] for i in idx]
+        ie = _issuer_engine(curve, device, lib_path, max(len(it[2]) for it in its), [])
+        ie.register_secret([it[0].sk for it in its])
+        octs, st = ie.eng.sign_wire_keyed_batch([ie.sk_index[it[0].sk] for it in its], [list(it[2]) for it in its], [it[1] for it in its])
+        for i, o, s in zip(idx, octs, st):
+            out[i] = BbsError(int(s)) if s < 0 else octets_to_signature(curve, o, lib_path)
+    return out
 
 
 def _many_issuers(items, count, to_octets, run):

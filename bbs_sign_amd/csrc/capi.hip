@@ -95,7 +95,10 @@ template <bool KEYED = false>
 static int upload(bbs_ctx* ctx, size_t n, const VfIn& in, bbs_job** job) {
     return with_curve(ctx, [&](auto* c) { return vf_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
 }
-static int upload(bbs_ctx* ctx, size_t n, const SgIn& in, bbs_job** job) { return with_curve(ctx, [&](auto* c) { return sg_upload(c, n, in, job); }); }
+template <bool KEYED = false>
+static int upload(bbs_ctx* ctx, size_t n, const SgIn& in, bbs_job** job) {
+    return with_curve(ctx, [&](auto* c) { return sg_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
+}
 template <bool KEYED = false>
 static int upload(bbs_ctx* ctx, size_t n, const PgIn& in, bbs_job** job) {
     return with_curve(ctx, [&](auto* c) { return pg_upload<curve_of<decltype(c)>, KEYED>(c, n, in, job); });
@@ -392,6 +395,22 @@ static int proof_gen_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_ind
     if (rc) return rc;
     if ((rc = job->set_octet_form())) { delete job; return rc; }
     return submit_with_results(job, status, octets_out, nullptr, oct_off_out, job_out);
+}
+
+// the reference's PUBLIC sign (src/sign.rs:63-132) in one call: raw messages in, signatures as octet strings out
+template <bool KEYED>
+static int sign_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                            const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status,
+                            bbs_job** job_out) {
+    if (!ctx || !status || !job_out || (n && (!sig_octets_out || !msg_item_off))) return BBS_E_ARG;
+    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
+    if (rc) return rc;
+    bbs_job* job = nullptr;
+    rc = upload<KEYED>(ctx, n, SgIn{.msg_off = msg_item_off, .headers = h, .hdr_off = ho, .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off,
+                                    .key_index = key_index}, &job);
+    if (rc) return rc;
+    if ((rc = job->set_octet_form())) { delete job; return rc; }
+    return submit_with_results(job, status, sig_octets_out, nullptr, nullptr, job_out);
 }
 
 #pragma GCC visibility push(default)
@@ -791,17 +810,48 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
+// the signing key set of keyed sign (runtime.hpp SignSet; registration: op_kg.hpp add_secret_keys)
+int bbs_ctx_set_secret_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out, int8_t* is_identity_out) {
+    if (!ctx || (n_keys && (!sk32 || !key_status))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return add_secret_keys(c, true, n_keys, sk32, key_status, pk_affine_out, is_identity_out, nullptr); });
+}
+int bbs_ctx_add_secret_keys(bbs_ctx* ctx, size_t n, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out, int8_t* is_identity_out,
+                            uint32_t* first_index) {
+    if (!ctx || !first_index || (n && (!sk32 || !key_status))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return add_secret_keys(c, false, n, sk32, key_status, pk_affine_out, is_identity_out, first_index); });
+}
+size_t bbs_ctx_secret_key_count(const bbs_ctx* ctx) {
+    if (!ctx) return 0;
+    return ctx->curve == BBS_CURVE_BLS12_381 ? static_cast<const Ctx<BlsCurve>*>(ctx)->secret_key_count() : static_cast<const Ctx<BnCurve>*>(ctx)->secret_key_count();
+}
 // the reference's PUBLIC sign: raw messages in (msg_to_scalars on the device), signatures as octet strings out
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                          const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out || (n && (!sig_octets_out || !msg_item_off))) return BBS_E_ARG;
-    int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
-    if (rc) return rc;
+    return sign_wire_submit<false>(ctx, n, nullptr, msg_bytes, msg_byte_off, msg_item_off, h, ho, sig_octets_out, status, job_out);
+}
+// keyed sign (keyed.hpp SgScalarsKeyed; op_sg.hpp): item i under key key_index[i] of the context's key set and signing set
+int bbs_sign_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                               const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status,
+                               bbs_job** job_out) {
+    return sign_wire_submit<true>(ctx, n, key_index, msg_bytes, msg_byte_off, msg_item_off, h, ho, sig_octets_out, status, job_out);
+}
+int bbs_sign_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                              const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status) {
     bbs_job* job = nullptr;
-    rc = upload(ctx, n, SgIn{.msg_off = msg_item_off, .headers = h, .hdr_off = ho, .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off}, &job);
+    return wait_and_free(bbs_sign_wire_keyed_submit(ctx, n, key_index, msg_bytes, msg_byte_off, msg_item_off, h, ho, sig_octets_out, status, &job), job);
+}
+int bbs_core_sign_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* m, const uint64_t* mo, const uint8_t* h,
+                               const uint64_t* ho, uint8_t* sigs_out, int8_t* status, bbs_job** job_out) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    bbs_job* job = nullptr;
+    int rc = upload<true>(ctx, n, SgIn{.messages = m, .msg_off = mo, .headers = h, .hdr_off = ho, .key_index = key_index}, &job);
     if (rc) return rc;
-    if ((rc = job->set_octet_form())) { delete job; return rc; }
-    return submit_with_results(job, status, sig_octets_out, nullptr, nullptr, job_out);
+    return submit_with_results(job, status, sigs_out, nullptr, nullptr, job_out);
+}
+int bbs_core_sign_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* m, const uint64_t* mo, const uint8_t* h,
+                              const uint64_t* ho, uint8_t* sigs_out, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_sign_keyed_submit(ctx, n, key_index, m, mo, h, ho, sigs_out, status, &job), job);
 }
 int bbs_sign_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                         const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status) {

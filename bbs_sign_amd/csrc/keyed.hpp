@@ -104,6 +104,52 @@ struct PgScalarsKeyedMixed {
     }
 };
 
+// Keyed sign (bbs_*sign*_keyed_*): item i under key kidx[i] of the context's key set AND its signing set (runtime.hpp SignSet:
+// row k = the 8 canonical words of sk_k, 32 bytes, 32-byte aligned).  core_sign meets the key in the domain (the key's midstate,
+// or the prefix of (key, length)), in the hash that gives e and in 1 / (sk + e); SgMsmPart .. SgEmit never see a key and follow
+// unchanged.  The row index diverges per lane, so the row is read with vector loads into the lane's registers; the index is the
+// caller's public key_index.  The gate decides every item that has no secret row before the scalar stage runs: KEY_NONE as
+// KeyGate does, KEY_NO_SECRET (an accepted key that was registered public-only) as BBS_ST_NO_SECRET_KEY -- neither ever indexes
+// the signing set, a midstate or a prefix.
+constexpr uint32_t KEY_NO_SECRET = 0xFFFFFFFEu;
+struct SignKeyGate {
+    static __host__ __device__ void run(const KeyGateArgs& a, size_t i) {
+        const uint32_t k = a.kidx[i];
+        if (k == KEY_NONE) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
+        else if (k == KEY_NO_SECRET) a.status0[i] = (int8_t)BBS_ST_NO_SECRET_KEY;
+    }
+};
+BBS_HD void sign_key_row(const uint32_t* sks, uint32_t k, uint32_t* sk) {
+    const uint32_t* row = static_cast<const uint32_t*>(__builtin_assume_aligned(sks + (size_t)8 * k, 32));
+    for (int j = 0; j < 8; j++) sk[j] = row[j];
+}
+template <class C>
+struct KeyedSignArgs { SgArgs<C> a; const KeyEntry<C>* keys; const uint32_t* kidx; const uint32_t* sks; };
+template <class C>
+struct SgScalarsKeyed {
+    static __host__ __device__ void run(const KeyedSignArgs<C>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        const uint32_t key = k.kidx[i];
+        uint32_t sk[8];
+        sign_key_row(k.sks, key, sk);
+        sg_scalars_item<C>(k.a, i, k.keys[key].hash, sk, k.a.L);
+    }
+};
+template <class C>
+struct KeyedMixedSignArgs { SgArgs<C> a; const HashCtx* pref; uint32_t stride; const uint32_t* kidx; const uint32_t* len; const uint32_t* sks; };
+template <class C>
+struct SgScalarsKeyedMixed {
+    static __host__ __device__ void run(const KeyedMixedSignArgs<C>& k, size_t i) {
+        if (k.a.status[i] != ST_PENDING) return;
+        const int l = (int)k.len[i];
+        const uint32_t key = k.kidx[i];
+        uint32_t sk[8];
+        sign_key_row(k.sks, key, sk);
+        sg_scalars_item<C>(k.a, i, k.pref[(size_t)key * k.stride + (size_t)l], sk, l);
+        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
+    }
+};
+
 // the keyed pairing step: e(Pa, W_key(i)) * e(+-Pb, BP2) == 1 for the items of the slots [0, n_slots)
 template <class C>
 struct PairKeyedArgs {

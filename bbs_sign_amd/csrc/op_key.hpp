@@ -130,6 +130,10 @@ int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* i
     if (!n) { if (first_index) *first_index = (uint32_t)n_old; return BBS_OK; }
     std::shared_ptr<KeySet> ks(new KeySet());
     ks->n = n_old + n;
+    {
+        static std::atomic<uint64_t> next_lineage{1};
+        ks->lineage = old ? old->lineage : next_lineage.fetch_add(1);
+    }
     ks->status.assign(ks->n, (int8_t)BBS_ST_NOT_ON_CURVE);
     {
         G2Aff<C> id{};

@@ -167,3 +167,92 @@ int sk_to_pk_batch(Ctx<C>* ctx, size_t n, const uint8_t* sk32, uint8_t* pk_affin
     }
     return crc ? BBS_E_HIP : BBS_OK;
 }
+
+// Registration of secret keys for keyed sign (bbs_ctx_set_secret_keys / bbs_ctx_add_secret_keys; runtime.hpp SignSet, keyed.hpp
+// SgScalarsKeyed).  The public halves of the whole call come from the KgPublic stage, as sk_to_pk_batch's do, and then go
+// through add_keys like keys that arrive as records: a secret-registered key IS a public-registered key plus its row of the
+// signing set, under the same index.  A scalar >= r is refused: BBS_ST_NONCANONICAL, a refused public entry, a zero row.
+// Order: derive; build the new signing set (exactly n_old + n rows: the old rows copied device to device, zero rows for the
+// public-only keys appended since, the new rows uploaded); then add_keys; the two pointers are swapped last, so a failure
+// anywhere leaves both sets as they were and the set that was being built is cleared by its destructor.  Every buffer that
+// held a secret -- the device scalars KgPublic read, the converted words, the rows' staging copy -- is cleared on every way out.
+template <class C>
+int add_secret_keys(Ctx<C>* ctx, bool replace, size_t n, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out, int8_t* inf_out,
+                    uint32_t* first_index) {
+    constexpr size_t FPB = Ctx<C>::FPB;
+    using SignSet = typename Ctx<C>::SignSet;
+    if (n && (!sk32 || !key_status)) return BBS_E_ARG;
+    if (!ctx->gens_set) return BBS_E_STATE;
+    if (ctx->use()) return BBS_E_HIP;
+    if (!n) {
+        if (replace) ctx->drop_key_sets();
+        else if (first_index) *first_index = (uint32_t)ctx->public_key_count();
+        return BBS_OK;
+    }
+    const auto old_keys = replace ? nullptr : ctx->keys;
+    const auto old_sign = replace ? nullptr : ctx->sign_keys;
+    const size_t n_old = old_keys ? old_keys->n : 0;
+    if (n_old + n > 0xFFFFFFF0u) return BBS_E_ARG;
+    if (old_sign && (!old_keys || old_sign->lineage != old_keys->lineage || old_sign->n > n_old)) return BBS_E_STATE;
+    KgSecrets secrets(ctx->stream);
+    Soa S;
+    DevBuf d_sk, d_st;
+    std::vector<uint32_t> rows(n * 8, 0u);
+    std::vector<uint8_t> rec(n * 4 * FPB, 0);
+    std::vector<int8_t> inf(n, 0), st(n, 0), pub_st(n, 0);
+    std::shared_ptr<SignSet> ss(new SignSet());
+    uint32_t first = 0;
+    auto body = [&]() -> int {
+        S.init(8, n);
+        secrets.host.push_back({S.aos.data(), S.aos.size() * 4});
+        secrets.host.push_back({rows.data(), rows.size() * 4});
+        for (size_t i = 0; i < n; i++) for (int k = 0; k < 8; k++) S.at(k, i) = le32(sk32 + i * 32 + 4 * k);
+        const std::vector<uint32_t>& soa = S.soa();
+        secrets.host.push_back({S.v.data(), S.v.size() * 4});
+        if (d_sk.alloc(n * 32) || d_st.alloc(n)) return BBS_E_NOMEM;
+        secrets.dev.push_back({d_sk.p, n * 32});
+        if (rt::h2d(d_sk.p, soa.data(), n * 32, ctx->stream) || rt::dmemset(d_st.p, (uint8_t)ST_PENDING, n, ctx->stream)) return BBS_E_HIP;
+        if (const int rc = kg_public_run<C>(ctx, n, d_sk.as<uint32_t>(), d_st.as<int8_t>(), rec.data(), inf.data(), nullptr)) return rc;
+        if (rt::d2h(st.data(), d_st.p, n, ctx->stream)) return BBS_E_HIP;
+        if (!statuses_final(st.data(), n)) return BBS_E_STATE;
+        // the signing set: [0, old_sign->n) copied, [old_sign->n, n_old) public-only (zero), [n_old, n_old + n) this call's
+        ss->n = n_old + n;
+        ss->device = ctx->device;
+        ss->has.assign(ss->n, 0);
+        if (ss->d.alloc(ss->n * 32)) return BBS_E_NOMEM;
+        if (rt::dmemset(ss->d.p, 0, ss->n * 32, ctx->stream)) return BBS_E_HIP;
+        if (old_sign) {
+            std::copy(old_sign->has.begin(), old_sign->has.end(), ss->has.begin());
+            ss->n_secret = old_sign->n_secret;
+            if (rt::d2d_async(ss->d.p, old_sign->d.p, old_sign->n * 32, ctx->stream)) return BBS_E_HIP;
+        }
+        for (size_t i = 0; i < n; i++) {
+            if (st[i] != 1) {        // refused: a record no key has (0xFF.. is no field element), so that add_keys refuses it too
+                std::memset(rec.data() + i * 4 * FPB, 0xFF, 4 * FPB);
+                inf[i] = 0;
+                continue;
+            }
+            for (int k = 0; k < 8; k++) rows[i * 8 + k] = S.at(k, i);
+            ss->has[n_old + i] = 1;
+            ss->n_secret++;
+        }
+        if (rt::h2d(ss->d.template as<uint32_t>() + n_old * 8, rows.data(), n * 32, ctx->stream) || rt::sync(ctx->stream)) return BBS_E_HIP;
+        if (const int rc = ctx->add_keys(replace, n, rec.data(), inf.data(), nullptr, pub_st.data(), nullptr, nullptr, &first)) return rc;
+        ss->lineage = ctx->keys->lineage;
+        ctx->sign_keys = std::move(ss);
+        return BBS_OK;
+    };
+    const int rc = body();
+    if (rc) (void)rt::sync(ctx->stream);               // (a copy into the set that is given up must not outlive it)
+    const int crc = secrets.clear();
+    if (rc) return rc;
+    for (size_t i = 0; i < n; i++) {
+        const bool ok = st[i] == 1 && pub_st[i] == 1;
+        key_status[i] = ok ? (int8_t)1 : st[i] != 1 ? st[i] : pub_st[i];
+        if (!ok) { std::memset(rec.data() + i * 4 * FPB, 0, 4 * FPB); inf[i] = 0; }
+    }
+    if (pk_affine_out) std::memcpy(pk_affine_out, rec.data(), n * 4 * FPB);
+    if (inf_out) std::memcpy(inf_out, inf.data(), n);
+    if (first_index) *first_index = first;
+    return crc ? BBS_E_HIP : BBS_OK;
+}

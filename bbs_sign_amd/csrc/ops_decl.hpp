@@ -47,6 +47,7 @@ struct SgIn {
     // msg_byte_off != nullptr: raw messages, hashed to scalars on the device (see VfIn)
     const uint8_t* msg_bytes = nullptr;
     const uint64_t* msg_byte_off = nullptr;
+    const uint32_t* key_index = nullptr;        // KEYED only: item i is signed under key key_index[i] of the context's signing set
 };
 struct PgIn {
     const uint8_t* signatures = nullptr;
@@ -70,7 +71,7 @@ struct PgIn {
 // declarations of the per-operation templates (defined in op_*.hpp, instantiated in tu_*.hip)
 template <class C, bool KEYED = false> int pv_upload(Ctx<C>*, size_t, const PvIn&, bbs_job**);
 template <class C, bool KEYED = false> int vf_upload(Ctx<C>*, size_t, const VfIn&, bbs_job**);
-template <class C> int sg_upload(Ctx<C>*, size_t, const SgIn&, bbs_job**);
+template <class C, bool KEYED = false> int sg_upload(Ctx<C>*, size_t, const SgIn&, bbs_job**);
 template <class C, bool KEYED = false> int pg_upload(Ctx<C>*, size_t, const PgIn&, bbs_job**);
 template <class C> int h2s_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
 template <class C> int msm_batch(Ctx<C>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
@@ -92,6 +93,8 @@ extern template int vf_upload<BnCurve>(Ctx<BnCurve>*, size_t, const VfIn&, bbs_j
 extern template int vf_upload<BnCurve, true>(Ctx<BnCurve>*, size_t, const VfIn&, bbs_job**);
 extern template int sg_upload<BlsCurve>(Ctx<BlsCurve>*, size_t, const SgIn&, bbs_job**);
 extern template int sg_upload<BnCurve>(Ctx<BnCurve>*, size_t, const SgIn&, bbs_job**);
+extern template int sg_upload<BlsCurve, true>(Ctx<BlsCurve>*, size_t, const SgIn&, bbs_job**);
+extern template int sg_upload<BnCurve, true>(Ctx<BnCurve>*, size_t, const SgIn&, bbs_job**);
 extern template int pg_upload<BlsCurve>(Ctx<BlsCurve>*, size_t, const PgIn&, bbs_job**);
 extern template int pg_upload<BlsCurve, true>(Ctx<BlsCurve>*, size_t, const PgIn&, bbs_job**);
 extern template int pg_upload<BnCurve>(Ctx<BnCurve>*, size_t, const PgIn&, bbs_job**);
@@ -124,6 +127,9 @@ extern template int Ctx<BnCurve>::set_keyed_mixed_lengths(int);
 extern template int selftest_key_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);
 template <class C> int key_gen_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint8_t*, int8_t*);
 template <class C> int sk_to_pk_batch(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*, int8_t*);
+template <class C> int add_secret_keys(Ctx<C>*, bool, size_t, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
+extern template int add_secret_keys<BlsCurve>(Ctx<BlsCurve>*, bool, size_t, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
+extern template int add_secret_keys<BnCurve>(Ctx<BnCurve>*, bool, size_t, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
 extern template int key_gen_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint8_t*, int8_t*);
 extern template int sk_to_pk_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*, int8_t*);
 extern template int key_gen_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint8_t*, int8_t*);

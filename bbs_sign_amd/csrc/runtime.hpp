@@ -623,8 +623,32 @@ struct Ctx : bbs_ctx {
         std::vector<int8_t> status;  // per key: 1 accepted, BBS_ST_NOT_ON_CURVE refused
         std::vector<G2Aff<C>> pk;    // host copy of every key (a refused key: the identity, never read): what its prefixes per length are hashed from
         DevBuf d;                    // [n] KeyEntry<C>
+        uint64_t lineage = 0;        // the same for a set and every set appended to it, new for a set that replaces one (SignSet)
     };
     std::shared_ptr<const KeySet> keys;
+    // Signing key set of keyed sign (bbs_ctx_set_secret_keys / bbs_ctx_add_secret_keys, op_kg.hpp): the secret halves of the key
+    // set, row k = the 8 canonical words of sk_k whose public half sk_k * BP2 is key k of `keys`.  The rules of KeySet --
+    // immutable once built, grows by appending (a new array of exactly n_old + n rows, the old rows copied device to device), a
+    // keyed sign job holds a reference -- plus one: the device array is CLEARED before it is released, whoever lets go last (the
+    // context, a job, a setter).  It keeps no host copy of a secret.  The set covers the keys [0, n) of the key set it was built
+    // beside (same lineage); a key appended public-only lies beyond n or has has[k] == 0 and a zero row, as a refused key has.
+    struct SignSet {
+        size_t n = 0, n_secret = 0;  // rows; rows with a secret half
+        uint64_t lineage = 0;        // of the key set the rows belong to
+        std::vector<uint8_t> has;    // per row: 1 = key k has a secret half
+        DevBuf d;                    // [n][8] words
+        int device = 0;
+        ~SignSet() {                 // cleared and synchronised, only then back to the pool (a stream of its own: every holder has synchronised its streams)
+            if (!d.p) return;
+            (void)rt::set_device(device);
+            rt::Stream s{};
+            (void)rt::dmemset(d.p, 0, d.bytes, s);
+            (void)rt::sync(s);
+        }
+    };
+    std::shared_ptr<const SignSet> sign_keys;
+    size_t secret_key_count() const { const auto ss = sign_keys; return ss ? ss->n_secret : 0; }
+    void drop_key_sets() { keys.reset(); key_lens.reset(); sign_keys.reset(); }
     // keyed jobs of mixed message counts (bbs_ctx_set_keyed_mixed_lengths): off by default, independent of mixed_lengths below.
     // On: the keyed verify / proof_verify jobs created from now on accept item i under its own key k_i with its own count
     // l_i <= L.  The one datum that depends on both is the domain prefix: one HashCtx per (key, length), row k of KeyLenSet =
@@ -864,8 +888,10 @@ struct Ctx : bbs_ctx {
                  uint8_t* rec_out, int8_t* inf_out, uint32_t* first_index);
     int set_public_keys(size_t n_keys, const uint8_t* b, const int8_t* is_identity, int8_t* key_status) {
         if (n_keys && !b) return BBS_E_ARG;
-        if (!n_keys) { keys.reset(); key_lens.reset(); return BBS_OK; }
-        return add_keys(true, n_keys, b, is_identity, nullptr, key_status, nullptr, nullptr, nullptr);
+        if (!n_keys) { drop_key_sets(); return BBS_OK; }
+        const int rc = add_keys(true, n_keys, b, is_identity, nullptr, key_status, nullptr, nullptr, nullptr);
+        if (!rc) sign_keys.reset();  // the new set has no secret halves (a failure leaves both sets)
+        return rc;
     }
     size_t public_key_count() const { const auto ks = keys; return ks ? ks->n : 0; }
     int set_secret_key(const uint8_t* sk32) {
@@ -1064,6 +1090,7 @@ struct JobBase : bbs_job {
     std::shared_ptr<const void> key_set;     // keyed jobs: the context's key set at upload (released after the streams synchronised)
     std::shared_ptr<const void> len_set;     // mixed-length jobs: the context's per-length domain prefixes at upload (likewise)
     std::shared_ptr<const void> key_len_set; // keyed jobs of mixed counts: the prefixes per (key, length) at upload (likewise)
+    std::shared_ptr<const void> sign_key_set;// keyed sign jobs: the context's signing set at upload (likewise; the last holder clears it)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};
     rt::Event ev_fork[bbs_job::N_AUX]{}, ev_join[bbs_job::N_AUX]{};
@@ -1442,6 +1469,25 @@ void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, Keyed
     }
     kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
     kj.pair.keys = kj.keys; kj.pair.n_uni = 0; kj.pair.n_slots = 0;
+}
+// keyed sign: the same look at the key set AND at the signing set (Ctx::SignSet) -- KEY_NONE as above, KEY_NO_SECRET for an
+// accepted key without a secret half; only an index that names a secret row is passed on.  BBS_E_STATE (fail closed) where the
+// two sets do not belong together: a set that was replaced between the two looks.  *sks = the rows on the device (null: none).
+template <class C, class J>
+int keyed_sign_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words, const uint32_t** sks) {
+    const auto ss = ctx->sign_keys;
+    keyed_indexes<C>(j, ctx, n, key_index, kj, words);
+    const auto ks = std::static_pointer_cast<const typename Ctx<C>::KeySet>(j->key_set);
+    if (ss && (!ks || ss->lineage != ks->lineage || ss->n > ks->n)) return BBS_E_STATE;
+    j->sign_key_set = ss;
+    // (no signing set: only where bbs_ctx_set_keyed_mixed_lengths is on -- the empty set, every index is unknown)
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = words[i];
+        if (!ss) words[i] = KEY_NONE;
+        else if (k != KEY_NONE && !(k < ss->n && ss->has[k])) words[i] = KEY_NO_SECRET;
+    }
+    *sks = ss ? ss->d.template as<uint32_t>() : nullptr;
+    return BBS_OK;
 }
 // the device half: d = the words' place in the device copy of the staging image
 template <class C>

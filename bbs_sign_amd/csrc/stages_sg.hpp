@@ -25,16 +25,17 @@ struct SgArgs {
 };
 
 // h: the domain prefix (the context's, or that of the item's own length in a mixed-length job); l: the item's message count
-// (a.L unless the job is a mixed-length one)
+// (a.L unless the job is a mixed-length one); sk: the 8 canonical words of the item's secret key -- a.sk of the single-key
+// stages (a kernel argument: scalar registers after inlining), the lane's own row of the signing set in the keyed ones
 template <class C>
-BBS_HD void sg_scalars_item(const SgArgs<C>& a, size_t i, const HashCtx& h, int l) {
+BBS_HD void sg_scalars_item(const SgArgs<C>& a, size_t i, const HashCtx& h, const uint32_t* sk, int l) {
     using R = typename C::FrP;
     const size_t n = a.n;
     Fr<C> dom = domain_from_header<C>(h, a.hdr_bytes + a.hdr_off[i], a.hdr_len[i]);
     // e = hash_to_scalar(sk || m_1 .. m_l || domain)   (sign.rs:90-118)
     Sha256 s;
     xmd48_begin(s);
-    sha256_limbs_be8(s, a.sk);
+    sha256_limbs_be8(s, sk);
     for (int j = 0; j < l; j++) {
         uint32_t m[8];
         soa_ld<8>(a.msgs + (size_t)j * 8 * n, n, i, m);
@@ -46,7 +47,7 @@ BBS_HD void sg_scalars_item(const SgArgs<C>& a, size_t i, const HashCtx& h, int 
     Fr<C> e = fr_from_okm<C>(okm);
     Fr<C> ec = fe_to_canonical<R>(e);
     soa_st<8>(a.out_e, n, i, ec.v);
-    Fr<C> skm = fe_from_limbs<R>(a.sk);
+    Fr<C> skm = fe_from_limbs<R>(sk);
     Fr<C> spe = fe_add<R>(skm, e);
     if (fe_is_zero<R>(spe)) { a.status[i] = -20; return; }     // sign.rs:129 unwrap
     Fr<C> inv = fe_inv<R>(spe);                                 // Montgomery
@@ -64,7 +65,7 @@ template <class C>
 struct SgScalars {
     static __host__ __device__ void run(const SgArgs<C>& a, size_t i) {
         if (a.status[i] != ST_PENDING) return;
-        sg_scalars_item<C>(a, i, a.cc->hash, a.L);
+        sg_scalars_item<C>(a, i, a.cc->hash, a.sk, a.L);
     }
 };
 // Mixed lengths (bbs_ctx_set_mixed_lengths_gen): as PvScalarsMixed (stages_pv.hpp) -- the domain from the prefix of the item's
@@ -76,7 +77,7 @@ struct SgScalarsMixed {
     static __host__ __device__ void run(const MixedScalarArgs<SgArgs<C>>& m, size_t i) {
         if (m.a.status[i] != ST_PENDING) return;
         const int l = (int)m.len[i];
-        sg_scalars_item<C>(m.a, i, m.pref[l], l);
+        sg_scalars_item<C>(m.a, i, m.pref[l], m.a.sk, l);
         mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
     }
 };

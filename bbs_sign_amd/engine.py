@@ -647,6 +647,98 @@ class Engine:
         job._decode = lambda: (self._dec_sigs(out, st, n), st[:n])
         return job
 
+    # ---- keyed sign: item i under key key_index[i] of the key set, with the secret half the signing set holds for it
+    # (set_secret_keys / add_secret_keys).  Status -44: unknown or refused key; -45: a key registered public-only.  Such an item
+    # has no output.  The context's single key is not needed.
+    def _secret_keys(self, fn, sks, tail=()):
+        n = len(sks)
+        for s in sks:
+            if not 0 <= int(s) < 1 << 256:
+                raise ValueError("secret key out of range")
+        buf = _bytes_arr(b"".join(self._fr(s) for s in sks)) if n else np.zeros(1, dtype=np.uint8)
+        rec = 4 * self.fpb
+        pk = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        ident = np.zeros(max(n, 1), dtype=np.int8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        try:
+            self._chk(getattr(self.lib, fn)(self.h, n, _u8(buf), st.ctypes.data_as(_lib.c_i8p), _u8(pk), ident.ctypes.data_as(_lib.c_i8p),
+                                            *tail), fn)
+        finally:
+            buf[:] = 0                                  # (the flattened copy of the secret keys made here)
+        p = pk.tobytes()
+        pks = [self._pk_dec(p[rec * i:rec * (i + 1)]) if st[i] == 1 and not ident[i] else None for i in range(n)]
+        return st[:n], pks
+
+    def set_secret_keys(self, sks: Sequence[int]):
+        """bbs_ctx_set_secret_keys: the context's SIGNING KEY SET (and, under the same indexes, its key set: key k's public half
+        is registered as set_public_keys registers it).  Returns ``(statuses, pks, first_index)``: statuses 1, or -40 for a
+        scalar >= r (the key keeps its index and its items get -44); pks[k] as set_public_keys takes it (None for sk = 0, the
+        identity key, and for a refused key); first_index is 0.  An empty list clears both sets."""
+        st, pks = self._secret_keys("bbs_ctx_set_secret_keys", sks)
+        return st, pks, 0
+
+    def add_secret_keys(self, sks: Sequence[int]):
+        """bbs_ctx_add_secret_keys: append to both sets; ``(statuses, pks, first_index)`` as set_secret_keys, key k of the call
+        has index first_index + k."""
+        first = ctypes.c_uint32(0)
+        st, pks = self._secret_keys("bbs_ctx_add_secret_keys", sks, (ctypes.byref(first),))
+        return st, pks, int(first.value)
+
+    def secret_key_count(self) -> int:
+        """bbs_ctx_secret_key_count: keys of the key set that have a secret half."""
+        return int(self.lib.bbs_ctx_secret_key_count(self.h))
+
+    def _sg_core_keyed(self, fn, key_index, messages, headers, tail=()):
+        n = len(messages)
+        ki, kip = self._key_index(key_index, n)
+        ms, mo = self._scalars(messages)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        out = np.zeros(max(n, 1) * (2 * self.fpb + 32), dtype=np.uint8)
+        self._chk(getattr(self.lib, fn)(self.h, n, kip, _u8(ms), _u64(mo), _u8(hb), _u64(ho), _u8(out), st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+        return n, st, lambda: (self._dec_sigs(out, st, n), st[:n])
+
+    def core_sign_keyed_batch(self, key_index, messages, headers=None):
+        """bbs_core_sign_keyed_batch -> (signatures | None, statuses)."""
+        n, st, decode = self._sg_core_keyed("bbs_core_sign_keyed_batch", key_index, messages, headers)
+        return decode()
+
+    def core_sign_keyed_submit(self, key_index, messages, headers=None) -> "Job":
+        """bbs_core_sign_keyed_submit; ``job.wait()`` then ``job.result`` and ``job.output()`` -> (signatures | None, statuses)."""
+        j = ctypes.c_void_p()
+        n, st, decode = self._sg_core_keyed("bbs_core_sign_keyed_submit", key_index, messages, headers, (ctypes.byref(j),))
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._decode = decode
+        return job
+
+    def _sg_wire_keyed(self, fn, key_index, messages_raw, headers, tail=()):
+        n = len(messages_raw)
+        ki, kip = self._key_index(key_index, n)
+        mb, mbo, mio = self._raw_msgs(messages_raw)
+        hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        rec = self.fpb + 32
+        out = np.zeros(max(n, 1) * rec, dtype=np.uint8)
+        self._chk(getattr(self.lib, fn)(self.h, n, kip, _u8(mb), _u64(mbo), _u64(mio), _u8(hb), _u64(ho), _u8(out),
+                                        st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+        return n, st, lambda: ([out[i * rec:(i + 1) * rec].tobytes() if st[i] == 1 else b"" for i in range(n)], st[:n])
+
+    def sign_wire_keyed_batch(self, key_index, messages_raw, headers=None):
+        """bbs_sign_wire_keyed_batch: the reference's public sign under many issuer keys -- raw messages in, (signature octet
+        strings, statuses) out."""
+        n, st, decode = self._sg_wire_keyed("bbs_sign_wire_keyed_batch", key_index, messages_raw, headers)
+        return decode()
+
+    def sign_wire_keyed_submit(self, key_index, messages_raw, headers=None) -> "Job":
+        """bbs_sign_wire_keyed_submit; ``job.wait()`` then ``job.output()`` -> (signature octet strings, statuses)."""
+        j = ctypes.c_void_p()
+        n, st, decode = self._sg_wire_keyed("bbs_sign_wire_keyed_submit", key_index, messages_raw, headers, (ctypes.byref(j),))
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._decode = decode
+        return job
+
     def sign_octets_submit(self, messages, headers=None) -> "Job":
         """bbs_sign_octets_submit: signatures leave as octet strings; ``job.wait()`` then ``job.output()`` ->
         (list of bytes, b"" for failed items; statuses)."""

@@ -65,6 +65,8 @@ extern "C" {
                                               * item was NOT computed -- the other items of the call were; retry later */
 #define BBS_ST_UNKNOWN_KEY (-44)             /* keyed entry points only: the item's key index is >= the key set's size or names a
                                               * key that bbs_ctx_set_public_keys refused; decided at ingest, never computed */
+#define BBS_ST_NO_SECRET_KEY (-45)           /* keyed sign only: the item's key index names an accepted key of the key set that was
+                                              * registered public-only (no secret half); decided at ingest, never computed */
 
 /* batch-level errors */
 #define BBS_OK 0
@@ -215,9 +217,9 @@ int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
  * ONCE in bbs_ctx_table_bytes, and rebuilt by bbs_ctx_set_generators, bbs_ctx_set_secret_key and bbs_ctx_set_public_key, so
  * every order of set-up ends in the same outputs.  Applies to jobs created afterwards; a job keeps the stages it was created
  * with.  BBS_E_ARG for a NULL ctx.
- * NOT covered: the keyed proof_gen entry points look at bbs_ctx_set_keyed_mixed_lengths (below), not at this switch; with this
- * switch on and that one off they return BBS_E_STATE and enqueue nothing; keyed sign does not exist (there is no set of secret
- * keys); bbs_issuer and bbs_pool keep one context per count; the C++ wrapper and the Rust shim do not expose the switch. */
+ * NOT covered: the keyed proof_gen and keyed sign entry points look at bbs_ctx_set_keyed_mixed_lengths (below), not at this
+ * switch; with this switch on and that one off they return BBS_E_STATE and enqueue nothing; bbs_issuer and bbs_pool keep one
+ * context per count; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
 /* Mixed message counts for the KEYED entry points (off by default; with it off nothing changes anywhere, the BBS_E_STATE above
  * included).  enabled = 1: every keyed verify and proof_verify job created from now on -- the eight bbs_*_keyed_* exports: core
@@ -238,9 +240,9 @@ int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
  * return BBS_E_STATE when it is on and this one is off.  Applies to jobs created afterwards; a job keeps the stages, the key set
  * and the prefixes it was created with, whatever is switched, appended or replaced later.  BBS_E_ARG for a NULL ctx.
  * Keyed proof_gen (bbs_*proof_gen*_keyed_*, below) takes mixed counts by this switch too: the same prefixes, and the output
- * bytes of item i are those of bbs_ctx_set_mixed_lengths_gen on that single-key context.
- * NOT covered: keyed sign does not exist; bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust
- * shim do not expose the switch. */
+ * bytes of item i are those of bbs_ctx_set_mixed_lengths_gen on that single-key context.  So does keyed sign
+ * (bbs_*sign*_keyed_*, below).
+ * NOT covered: bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled);
 
 /* Batch verification for core_proof_verify and core_verify (off by default).  When enabled, the n two-pairing
@@ -475,8 +477,8 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
  * item's key -- for an item whose number of random scalars is not 5 + l_i - r_i.  Both job forms; the _submit forms return
  * ordinary jobs.  A key costs its full entry (~30 KB on BLS12-381, the W line table included) although proof_gen reads only the
  * midstate: there is no cheaper registration for proof-only keys.
- * NOT covered: the octets (non-wire) keyed form and an _upload form; keyed sign does not exist (it would need a set of secret
- * keys on the device); bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim do not route through these. */
+ * NOT covered: the octets (non-wire) keyed form and an _upload form; bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim
+ * do not route through these. */
 int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
                                     const uint8_t* messages, const uint64_t* msg_off,
                                     const uint64_t* disclosed_idx, const uint64_t* didx_off,
@@ -507,6 +509,63 @@ int bbs_proof_gen_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_i
                                    const uint8_t* headers, const uint64_t* hdr_off,
                                    const uint8_t* ph, const uint64_t* ph_off,
                                    uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status);
+
+/* Keyed sign: ONE context signs under MANY issuer secret keys.  The reference takes the key per call (src/sign.rs:63, &self), so
+ * per-item keys are its semantics.
+ * The SIGNING KEY SET of a context is an immutable device array of canonical secret scalars, 32 bytes per key, indexed exactly
+ * like the key set of the keyed verify / proof_gen entry points and tied to it: key k's public half sk_k * BP2 is registered in
+ * the key set under the same index k, so one index names the key for sign, verify, proof_gen and proof_verify on the context.
+ * Registration: sk32 holds n little-endian scalars (as bbs_ctx_set_secret_key takes them).  key_status[k] is 1, or
+ * BBS_ST_NONCANONICAL for a scalar >= r: a refused key still occupies its index, its public entry is a refused entry, its secret
+ * row is zero, and every keyed operation gives items naming it BBS_ST_UNKNOWN_KEY.  sk = 0 is accepted: the identity key.  The
+ * public halves of the whole call are derived on the device (the path of bbs_sk_to_pk_batch) and registered as
+ * bbs_ctx_add_public_keys registers keys; pk_affine_out (n records of 4 field elements) and is_identity_out (n bytes), each may be
+ * NULL, receive them -- byte for byte bbs_sk_to_pk_batch's output, zero for a refused key.  Duplicate keys are legal.
+ *   bbs_ctx_set_secret_keys replaces BOTH sets (n_keys = 0 clears both).
+ *   bbs_ctx_add_secret_keys appends to both; *first_index = the index of the call's first key; n = 0 only reports the size.
+ *   bbs_ctx_secret_key_count: the keys of the key set that have a secret half.
+ * The set is immutable once built and grows by appending (a new array of exactly n_old + n rows; the old rows are copied on the
+ * device); a keyed sign job holds a reference to the set it was created with, so an append, a replace, a flip of
+ * bbs_ctx_set_keyed_mixed_lengths or bbs_ctx_set_generators never reaches a job that exists.  On any failure (BBS_E_NOMEM,
+ * BBS_E_HIP) both sets stay as they were.  SECRETS: the device array is cleared, and its stream synchronised, before its memory
+ * is released, whoever lets go of it last (bbs_ctx_destroy, a job when it is freed, a setter); the array an append replaces is
+ * cleared the same way, and so is every host or device copy the library makes during registration.  No entry point returns a
+ * secret.  No constant-time claim is made (as for bbs_ctx_set_secret_key).
+ * What drops the signing set: bbs_ctx_set_generators (it drops the key set), bbs_ctx_set_public_keys (n_keys = 0 included),
+ * bbs_ctx_set_secret_keys, bbs_ctx_destroy.  bbs_ctx_add_public_keys* does NOT: it appends public-only keys and keeps the signing
+ * set.  The context's single key (bbs_ctx_set_secret_key) is untouched and not looked at.
+ * BBS_E_ARG for a NULL ctx, a NULL first_index, and a NULL sk32 or key_status with n > 0; BBS_E_STATE without generators.
+ *
+ * Signing: the arguments of bbs_core_sign_* / bbs_sign_wire_* plus key_index (n entries) after n.  For an item whose key_index
+ * names an accepted key with a secret half, the status AND the signature bytes (record or octet string) are, bit for bit, what the
+ * un-keyed form gives that item alone on a context with the same generators, api_id and window bits and that key set by
+ * bbs_ctx_set_secret_key; with bbs_ctx_set_keyed_mixed_lengths on, item i also has its own count l_i <= L and the comparison
+ * context is made with generators[0 .. l_i].  An index >= the key set's size or naming a refused key gives BBS_ST_UNKNOWN_KEY;
+ * an index naming an accepted key that was registered public-only gives BBS_ST_NO_SECRET_KEY; both override whatever the other
+ * checks decided and leave a zero record (an all-zero octet string).  Such items are decided before the scalar stage and never
+ * index the secret array or a midstate.
+ * BBS_E_STATE without generators; without a signing set (unless bbs_ctx_set_keyed_mixed_lengths is on: then a missing set is the
+ * empty set and every item is BBS_ST_UNKNOWN_KEY, whatever the key set holds); and on a context with
+ * bbs_ctx_set_mixed_lengths_gen on unless bbs_ctx_set_keyed_mixed_lengths is on too.  BBS_E_ARG for a NULL key_index with n > 0.
+ * Both job forms; the _submit forms return ordinary jobs (bbs_job_wait, bbs_jobs_wait_any, bbs_job_fetch_signatures).
+ * NOT covered: an _upload form and the octets (non-wire) keyed form; bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim do
+ * not route through these. */
+int bbs_ctx_set_secret_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out,
+                            int8_t* is_identity_out);
+int bbs_ctx_add_secret_keys(bbs_ctx* ctx, size_t n, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out,
+                            int8_t* is_identity_out, uint32_t* first_index);
+size_t bbs_ctx_secret_key_count(const bbs_ctx* ctx);   /* keys of the key set that have a secret half */
+int bbs_core_sign_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* messages, const uint64_t* msg_off,
+                               const uint8_t* headers, const uint64_t* hdr_off, uint8_t* signatures_out, int8_t* status,
+                               bbs_job** job_out);
+int bbs_core_sign_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* messages, const uint64_t* msg_off,
+                              const uint8_t* headers, const uint64_t* hdr_off, uint8_t* signatures_out, int8_t* status);
+int bbs_sign_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes,
+                               const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* headers,
+                               const uint64_t* hdr_off, uint8_t* signature_octets_out, int8_t* status, bbs_job** job_out);
+int bbs_sign_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes,
+                              const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* headers,
+                              const uint64_t* hdr_off, uint8_t* signature_octets_out, int8_t* status);
 
 /* The reference's PUBLIC sign (src/sign.rs:32-60): raw messages in, signature octet strings out (as bbs_sign_octets_*). */
 int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
