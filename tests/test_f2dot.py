@@ -169,7 +169,9 @@ def test_glv_split(libs, cid, curve):
 def test_joint_multiplication(libs, cid, curve):
     """k0 P0 + k1 P1 + k2 P2 on the joint chain of proof_verify's T1, plain and with the GLV split, against the
     oracle's double-and-add: random and edge scalars (zero, even, below lambda, r - 1), the identity and repeated
-    points among the inputs (those take the per-point fallback)."""
+    points among the inputs.  Only the identity takes the per-point fallback: g1_odd_table fails for the identity and for
+    points of small order alone, so the repeated points (P, P, -P) go down the joint chain and meet the r == q / r == -q
+    branches of its mixed addition there (tests/test_chain_model.py says at which steps)."""
     c = curve
     fpb = c.fp_bytes
     rng = random.Random(99 + cid)
