@@ -67,6 +67,7 @@ SIGNATURES = {
     "bbs_ctx_set_mixed_lengths": (ci, [vp, ci]),
     "bbs_ctx_set_mixed_lengths_gen": (ci, [vp, ci]),
     "bbs_ctx_set_keyed_mixed_lengths": (ci, [vp, ci]),
+    "bbs_ctx_set_unit_lines": (ci, [vp, ci]),
     "bbs_selftest_glv_split": (ci, [ci, c_u8p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "bbs_selftest_lin_pm": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),
     "bbs_selftest_mul3": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),

@@ -490,6 +490,10 @@ int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_keyed_mixed_lengths(enabled); });
 }
+int bbs_ctx_set_unit_lines(bbs_ctx* ctx, int enabled) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->set_unit_lines(enabled); });
+}
 int bbs_selftest_glv_split(int curve, const uint8_t* k32, uint8_t* k1_16, uint8_t* k2_16, int* neg1, int* neg2) {
     if ((curve != BBS_CURVE_BLS12_381 && curve != BBS_CURVE_BN254) || !k32 || !k1_16 || !k2_16 || !neg1 || !neg2) return BBS_E_ARG;
     uint32_t k[8], k1[4], k2[4];

@@ -118,11 +118,36 @@ inline void build_schedule(MillerSchedule& s) {
     s.n_ops = k;
 }
 
-// returns false if a degenerate (vertical) line is met: Q is not a point of order r
+// (c, nl) -> (1/c, nl/c) times R^-1 for every entry (pairing.hpp "Unit form": the plain residues of 1/c and nl/c) with ONE
+// inversion (Montgomery's trick); false, and the table untouched, where some c is zero: a line through the twist's origin
 template <class C>
-inline bool build_line_table(const G2Aff<C>& Q, LineTable<C>& tab) {
+inline bool line_table_to_unit(LineTable<C>& tab) {
+    const int n = tab.n_lines;
+    std::vector<Fp2<C>> before((size_t)n);
+    Fp2<C> prod = f2_one<C>();
+    for (int s = 0; s < n; s++) {
+        if (f2_is_zero<C>(tab.e[s].c)) return false;
+        before[(size_t)s] = prod;
+        prod = f2_mul<C>(prod, tab.e[s].c);
+    }
+    Fp2<C> inv = f2_inv<C>(prod);
+    const Fp<C> rinv = f2_rinv<C>().c0;
+    for (int s = n - 1; s >= 0; s--) {
+        const Fp2<C> ci = f2_mul_fp<C>(f2_mul<C>(inv, before[(size_t)s]), rinv);
+        inv = f2_mul<C>(inv, tab.e[s].c);
+        tab.e[s].c = ci;
+        tab.e[s].nl = f2_mul<C>(tab.e[s].nl, ci);
+    }
+    return true;
+}
+
+// returns false if a degenerate (vertical) line is met: Q is not a point of order r.  want_unit: the unit form where every
+// c is invertible (tab.unit says which form came out; 0 for the identity, which has no lines)
+template <class C>
+inline bool build_line_table(const G2Aff<C>& Q, LineTable<C>& tab, bool want_unit) {
     tab.n_lines = 0;
     tab.q_is_identity = Q.inf ? 1 : 0;
+    tab.unit = 0;
     if (Q.inf) return true;
     G2Aff<C> T = Q;
     auto step = [&](const G2Aff<C>& other) -> bool {
@@ -147,6 +172,7 @@ inline bool build_line_table(const G2Aff<C>& Q, LineTable<C>& tab) {
         if (!step(Q1)) return false;
         if (!step(Q2)) return false;
     }
+    tab.unit = (want_unit && line_table_to_unit<C>(tab)) ? 1 : 0;
     return true;
 }
 

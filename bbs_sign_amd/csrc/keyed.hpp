@@ -187,7 +187,7 @@ struct PairMillerKeyed {
             const int nops = a.cc->sched.n_ops;
             for (int k = 0; k < nops; k++) {
                 if (a.cc->sched.op[k] == 0) f = f12_sqr<C>(f);
-                else f = f12_mul_line<C>(f, tab->e[li++], P);
+                else f = f12_mul_line<C>(f, tab->e[li++], P, tab->unit != 0);
             }
             if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
         }
@@ -200,7 +200,7 @@ static_assert(KEY_SLOTS_PER_WAVE == GRP_PER_WAVE, "the host cuts the pairing ord
 // PairDist over a slot map.  UNIFORM: every slot of the wavefront has the key wave_key[wave] -- read once, made
 // wave-uniform, so W's line entries are scalar loads exactly as in PairDist.  Mixed: each six-lane group reads the lines of
 // its own item's key (vector loads).
-template <class C, bool UNIFORM>
+template <class C, bool UNIT, bool UNIFORM>
 __device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size_t t) {
     const PairArgs<C>& a = ka.p;
     const int lane = (int)(t & 63);
@@ -229,8 +229,8 @@ __device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size
             if (cc->sched.op[k] == 0) {
                 m = d_sqr<C>(L, m);
             } else {
-                if (!skipA) m = d_mul_line<C>(L, m, tw->e[li], Pa);
-                if (!skipB) m = d_mul_line<C>(L, m, cc->tab_bp2.e[li], Pb);
+                if (!skipA) m = d_mul_line<C, UNIT>(L, m, tw->e[li], Pa);
+                if (!skipB) m = d_mul_line<C, UNIT>(L, m, cc->tab_bp2.e[li], Pb);
                 li++;
             }
         }
@@ -241,12 +241,13 @@ __device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size
     const bool one = d_is_one<C>(L, f);
     if (L.m == 0) a.out[i] = one ? 1 : 0;
 }
-template <class C>
+// UNIT: the form of every table of the key set and of BP2's (one form per context: runtime.hpp Ctx::rebuild_lines)
+template <class C, bool UNIT>
 struct PairDistKeyed {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairKeyedArgs<C>& ka, size_t t) {
-        if ((t >> 6) * GRP_PER_WAVE < ka.n_uni) pair_dist_keyed<C, true>(ka, t);     // (uniform over the wavefront)
-        else pair_dist_keyed<C, false>(ka, t);
+        if ((t >> 6) * GRP_PER_WAVE < ka.n_uni) pair_dist_keyed<C, UNIT, true>(ka, t);     // (uniform over the wavefront)
+        else pair_dist_keyed<C, UNIT, false>(ka, t);
     }
 };
 #endif

@@ -28,7 +28,7 @@ int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oc
         else if (!fe_from_le_bytes<P>(rec, q.x.c0) || !fe_from_le_bytes<P>(rec + FPB, q.x.c1) ||
                  !fe_from_le_bytes<P>(rec + 2 * FPB, q.y.c0) || !fe_from_le_bytes<P>(rec + 3 * FPB, q.y.c1)) return (int8_t)BBS_ST_NOT_ON_CURVE;
     }
-    if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q) || !build_line_table<C>(q, e.tab)) {
+    if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q) || !build_line_table<C>(q, e.tab, lines_unit())) {
         std::memset(&e.tab, 0, sizeof(e.tab));
         e.tab.q_is_identity = 1;
         return (int8_t)BBS_ST_NOT_ON_CURVE;
@@ -50,9 +50,10 @@ int8_t Ctx<C>::host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oc
 // Synchronises the context's stream.  status / rec_out / inf_out: host arrays, the last two may be null.
 template <class C>
 int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
-                      int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out) {
+                      int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out, size_t* n_other_form) {
+    if (n_other_form) *n_other_form = 0;
     if (!n) return BBS_OK;
-    if (q_out && on_device) return BBS_E_STATE;         // the host copies of the keys come from the host path only
+    if ((q_out || n_other_form) && on_device) return BBS_E_STATE;      // the host copies of the keys and the forms that came out: host path only
     if (!on_device) {
         std::vector<KeyEntry<C>> host(n);
         auto one = [&](size_t k) {
@@ -66,6 +67,9 @@ int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const in
             for (size_t t = 0; t < nt; t++) th.emplace_back([&, t]() { for (size_t k = t; k < n; k += nt) one(k); });
             for (auto& x : th) x.join();
         }
+        // tables that came out in the other form than the context's: keys without a unit form (add_keys rebuilds every table)
+        if (n_other_form)
+            for (size_t k = 0; k < n; k++) *n_other_form += (!host[k].tab.q_is_identity && (host[k].tab.unit != 0) != lines_unit()) ? 1 : 0;
         if (rt::h2d(d_out, host.data(), n * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
         return BBS_OK;
     }
@@ -109,6 +113,7 @@ int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const in
     a.gen_x = gen.x; a.gen_y = gen.y;
     a.frob_x = f2_from_consts<C>(C::K::FROB[0][2][0], C::K::FROB[0][2][1]);
     a.frob_y = f2_from_consts<C>(C::K::FROB[0][3][0], C::K::FROB[0][3][1]);
+    a.want_unit = lines_unit() ? 1 : 0;
     a.n_bits = (int)bits.size();
     for (size_t k = 0; k < bits.size(); k++) a.bits[k] = (uint8_t)bits[k];
     if (rt::launch<KeyBuild<C>>(stream, a, n)) return fail(BBS_E_HIP);
@@ -130,6 +135,8 @@ int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* i
     if (!n) { if (first_index) *first_index = (uint32_t)n_old; return BBS_OK; }
     std::shared_ptr<KeySet> ks(new KeySet());
     ks->n = n_old + n;
+    ks->unit = lines_unit();
+    size_t n_other_form = 0;
     {
         static std::atomic<uint64_t> next_lineage{1};
         ks->lineage = old ? old->lineage : next_lineage.fetch_add(1);
@@ -147,7 +154,8 @@ int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* i
         if (rt::d2d_async(ks->d.p, old->d.p, n_old * sizeof(KeyEntry<C>), stream)) return BBS_E_HIP;
     }
     if (const int rc = key_build(ks->d.template as<KeyEntry<C>>() + n_old, n, rec, is_inf, oct, KEY_BUILD_ON_DEVICE,
-                                 ks->status.data() + n_old, rec_out, inf_out, KEY_BUILD_ON_DEVICE ? nullptr : ks->pk.data() + n_old)) {
+                                 ks->status.data() + n_old, rec_out, inf_out, KEY_BUILD_ON_DEVICE ? nullptr : ks->pk.data() + n_old,
+                                 KEY_BUILD_ON_DEVICE ? nullptr : &n_other_form)) {
         (void)rt::sync(stream);      // (the copy of the old entries must not outlive the buffer it writes)
         return rc;
     }
@@ -165,7 +173,60 @@ int Ctx<C>::add_keys(bool replace, size_t n, const uint8_t* rec, const int8_t* i
     if (key_status) std::memcpy(key_status, ks->status.data() + n_old, n);
     if (first_index) *first_index = (uint32_t)n_old;
     keys = std::move(ks);
+    // a new key without a unit form, or the key that had none was just replaced: every table of the context changes form
+    if (n_other_form || lines_form_stale()) return rebuild_lines();
     return BBS_OK;
+}
+
+// Every line table of the context again -- BP2's, the public key's, the key set's (a new immutable set: jobs keep the one they
+// hold) -- in the form asked for (unit_lines); where one of them has no unit form, all of them in the (c, nl) form.  Only the
+// tables are rebuilt: statuses, host copies, midstates and the prefixes per (key, length) are carried over.  Synchronises the
+// context's stream.  Setter-time work on the host, as registration is.
+template <class C>
+int Ctx<C>::rebuild_lines() {
+    if (use()) return BBS_E_HIP;
+    const std::shared_ptr<const KeySet> old = keys;
+    for (int want = unit_lines ? 1 : 0;; want = 0) {
+        bool same = true;
+        if (!build_line_table<C>(g2_generator<C>(), hc.tab_bp2, want != 0)) return BBS_E_STATE;
+        same &= hc.tab_bp2.unit == want;
+        if (pk_set) {
+            if (!build_line_table<C>(pk, hc.tab_pk, want != 0)) return BBS_E_STATE;
+            same &= hc.tab_pk.q_is_identity || hc.tab_pk.unit == want;
+        }
+        std::shared_ptr<KeySet> ks;
+        if (same && old && old->n) {
+            std::vector<KeyEntry<C>> host(old->n);
+            if (rt::d2h(host.data(), old->d.p, old->n * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
+            for (size_t k = 0; k < old->n && same; k++) {
+                if (old->status[k] != 1 || old->pk[k].inf) continue;
+                LineTable<C>& t = host[k].tab;
+                if (!build_line_table<C>(old->pk[k], t, want != 0)) return BBS_E_STATE;
+                for (int s = 0; s < t.n_lines; s++) { t.e[s].c = f2_canon<C>(t.e[s].c); t.e[s].nl = f2_canon<C>(t.e[s].nl); }
+                same &= t.unit == want;
+            }
+            if (same) {
+                ks.reset(new KeySet());
+                ks->n = old->n; ks->status = old->status; ks->pk = old->pk; ks->lineage = old->lineage; ks->unit = want != 0;
+                if (ks->d.alloc(ks->n * sizeof(KeyEntry<C>))) return BBS_E_NOMEM;
+                if (rt::h2d(ks->d.p, host.data(), ks->n * sizeof(KeyEntry<C>), stream) || rt::sync(stream)) return BBS_E_HIP;
+            }
+        }
+        if (!same && want) continue;                    // a key without a unit form: everything in the (c, nl) form
+        consts_dirty = true;
+        if (ks) {
+            std::shared_ptr<const KeyLenSet> kl;
+            if (keyed_mixed_lengths) {
+                const std::shared_ptr<const KeySet> cks = ks;
+                const std::shared_ptr<const KeyLenSet> okl = key_lens;
+                const bool reuse = okl && okl->of.get() == old.get() && okl->stride == (size_t)L + 1;
+                if (const int rc = build_key_lens(cks, reuse ? okl : nullptr, reuse ? old->n : 0, kl)) return rc;
+            }
+            key_lens = kl;
+            keys = std::move(ks);
+        }
+        return BBS_OK;
+    }
 }
 
 // The prefixes per (key, length) of the keys [n_old, ks->n) on up to 16 host threads (the generators are compressed once), the

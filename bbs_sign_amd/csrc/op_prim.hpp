@@ -363,7 +363,9 @@ int pairing_batch(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, i
         rt::launch<PairFinal<C>>(ctx->stream, a, n) || rt::sync(ctx->stream)) return BBS_E_HIP;
 #else
     if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) ||
-        rt::launch<PairDist<C>>(ctx->stream, a, ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64) || rt::sync(ctx->stream)) return BBS_E_HIP;
+        (ctx->dev_lines_unit ? rt::launch<PairDist<C, true>>(ctx->stream, a, ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64)
+                             : rt::launch<PairDist<C, false>>(ctx->stream, a, ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64)) ||
+        rt::sync(ctx->stream)) return BBS_E_HIP;
 #endif
     if (rt::d2h(status, dSt.p, n, ctx->stream)) return BBS_E_HIP;
     return statuses_final(status, n) ? BBS_OK : BBS_E_STATE;
@@ -373,14 +375,14 @@ int pairing_batch(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, i
 // tower code compiled for the host (tower.hpp / pairing.hpp, validated against the oracle by the
 // host-twin tests); only the six-lane version runs on the device.
 template <class C, int OP>
-static Fp12<C> selftest_ref(const Fp12<C>& x, const Fp12<C>& y, const LineEntry<C>& le, const G1Aff<C>& P) {
+static Fp12<C> selftest_ref(const Fp12<C>& x, const Fp12<C>& y, const LineEntry<C>& le, bool unit, const G1Aff<C>& P) {
     if constexpr (OP == 0) return f12_mul<C>(x, y);
     else if constexpr (OP == 1) return f12_frob<C, 1>(x);
     else if constexpr (OP == 2) return f12_frob<C, 2>(x);
     else if constexpr (OP == 3) return f12_frob<C, 3>(x);
     else if constexpr (OP == 4) return f12_inv<C>(x);
     else if constexpr (OP == 5) return f12_conj<C>(x);
-    else if constexpr (OP == 6) return f12_mul_line<C>(x, le, P);
+    else if constexpr (OP == 6) return f12_mul_line<C>(x, le, P, unit);
     else if constexpr (OP == 7) return final_exponentiation<C>(x);
     else if constexpr (OP == 10) return f12_sqr<C>(x);
     else if constexpr (OP == 8) return f12_sqr<C>(x);
@@ -406,12 +408,14 @@ int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const
     if (op < 0 || op > 12 || op == 9) return BBS_E_ARG;
     if (!n) return BBS_OK;
     LineEntry<C> le{};
+    bool le_unit = false;
     if (op == 6) {
         if (line_table != 0 && line_table != 1) return BBS_E_ARG;
         if (line_table == 0 && !ctx->pk_set) return BBS_E_STATE;
         const LineTable<C>& tab = line_table ? ctx->hc.tab_bp2 : ctx->hc.tab_pk;
         if (line_index < 0 || line_index >= tab.n_lines) return BBS_E_ARG;
         le = tab.e[line_index];
+        le_unit = tab.unit != 0;
     }
     if (ctx->use()) return BBS_E_HIP;
     std::vector<uint32_t> X(n * 12 * N), B(n * 12 * N);
@@ -431,7 +435,7 @@ int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const
         f12_to_array<C>(x, xe);
         for (int k = 0; k < 12; k++) for (int j = 0; j < N; j++) { X[(i * 12 + k) * N + j] = xe[k].v[j]; B[(i * 12 + k) * N + j] = ye[k].v[j]; }
         if (!out_single || !act[i]) continue;
-#define BBS_ST_CASE(K) case K: ref[i] = selftest_ref<C, K>(x, y, le, Pt); break;
+#define BBS_ST_CASE(K) case K: ref[i] = selftest_ref<C, K>(x, y, le, le_unit, Pt); break;
         switch (op) {
             BBS_ST_CASE(0) BBS_ST_CASE(1) BBS_ST_CASE(2) BBS_ST_CASE(3) BBS_ST_CASE(4) BBS_ST_CASE(5)
             BBS_ST_CASE(6) BBS_ST_CASE(7) BBS_ST_CASE(8) BBS_ST_CASE(10) BBS_ST_CASE(11) BBS_ST_CASE(12)

@@ -13,6 +13,17 @@
 // scaled by a factor the final exponentiation kills it is
 //   M-type twist (BLS12-381):  c + (nl*xP) v + yP v w
 //   D-type twist (BN254)    :  yP + (nl*xP + c v) w
+//
+// Unit form.  c lies in Fp2, so the final exponentiation kills it as well: where every c of a table is invertible the
+// builder scales each line by 1/c and the constant term becomes a constant of Fp --
+//   M-type twist:  k + (k (nl/c)*xP) v + (k (1/c)*yP) v w
+//   D-type twist:  k (1/c)*yP + (k (nl/c)*xP + k v) w
+// -- with k = R^-1, R the Montgomery radix: the internal form of k is the integer 1, so the entries (nl/c) k and (1/c) k are
+// stored as the PLAIN residues of nl/c and 1/c, and the constant term times g is g's own limbs in the low columns of a dot
+// product (tower.hpp f2acc_init_rinv): no multiplication and no reduction of its own.  That is one Fp2 product fewer per line
+// in the six-lane kernel (pairing_dist.hpp d_mul_line).  c = 0 is a line through the
+// twist's origin; it cannot be excluded for a caller's key, so a table that meets one keeps the form above (unit = 0).
+// Every table a job reads has the same form (runtime.hpp Ctx::rebuild_lines), the kernels take it as a template parameter.
 #pragma once
 #include "g1.hpp"
 
@@ -23,6 +34,8 @@ namespace bbs {
 constexpr int MAX_MILLER_OPS = 256;    // schedule bytes: 0 = square f, 1 = multiply by next line
 constexpr int MAX_LINES = 128;
 
+// unit = 0: (c, nl) in the internal (Montgomery) form.  unit = 1: c holds 1/c and nl holds nl/c as plain residues in [0, p) --
+// read as internal forms they are (1/c) R^-1 and (nl/c) R^-1; the constant term R^-1 is not stored.
 template <class C>
 struct LineEntry {
     Fp2<C> c, nl;
@@ -33,6 +46,7 @@ struct LineTable {
     LineEntry<C> e[MAX_LINES];
     int n_lines;
     int q_is_identity;     // pair contributes 1
+    int unit;              // form of every entry (0 for a table without lines)
 };
 
 struct MillerSchedule {
@@ -41,8 +55,13 @@ struct MillerSchedule {
 };
 
 template <class C>
-BBS_HD Fp12<C> f12_mul_line(const Fp12<C>& f, const LineEntry<C>& le, const G1Aff<C>& P) {
+BBS_HD Fp12<C> f12_mul_line(const Fp12<C>& f, const LineEntry<C>& le, const G1Aff<C>& P, bool unit) {
     Fp2<C> lx = f2_mul_fp<C>(le.nl, P.x);
+    if (unit) {
+        const Fp2<C> ly = f2_mul_fp<C>(le.c, P.y);
+        if constexpr (C::K::TWIST_M) return f12_mul_by_line_M_unit<C>(f, lx, ly);
+        else return f12_mul_by_line_D_unit<C>(f, lx, ly);
+    }
     if constexpr (C::K::TWIST_M) {
         return f12_mul_by_line_M<C>(f, le.c, lx, P.y);
     } else {
@@ -128,8 +147,8 @@ BBS_HD_NOINLINE Fp12<C> miller_loop2(const MillerSchedule* sched, const LineTabl
         if (sched->op[k] == 0) {
             f = f12_sqr<C>(f);
         } else {
-            if (!skipA) f = f12_mul_line<C>(f, ta->e[li], Pa);
-            if (!skipB) f = f12_mul_line<C>(f, tb->e[li], Pb);
+            if (!skipA) f = f12_mul_line<C>(f, ta->e[li], Pa, ta->unit != 0);
+            if (!skipB) f = f12_mul_line<C>(f, tb->e[li], Pb, tb->unit != 0);
             li++;
         }
     }

@@ -10,7 +10,8 @@
 // in 64-bit columns and Montgomery-reduced once (tower.hpp F2Acc; N = limbs of Fp):
 //   mul        : c_k = sum_j g_j h_(k-j) xi^[j>k]                      6 * 3 N^2 + 2 N^2 multiply-accumulates
 //   square     : unordered pairs, four slots per lane                  4 * 3 N^2 + 2 N^2
-//   line (M/D) : sparse, 3 non-zero coefficients                       8 N^2 + 2 N^2 (+ 4 N^2 for nl * xP)
+//   line (M/D) : sparse, 3 non-zero coefficients                       8 N^2 + 2 N^2 (+ 2 N^2 for nl * xP, one component per lane)
+//   line, unit form (constant term R^-1, pairing.hpp)                    6 N^2 + 2 N^2 (+ 2 N^2 for (nl/c) xP and (1/c) yP, lanes 0..3)
 //   cyclotomic square (Granger-Scott over Fp4 pairs (m, m+3))          four column products, 4 N^2 + 2 N^2
 //   conj, frob : lane-local
 //   inverse    : gathered on every lane (once per item), one safegcd inversion in Fp
@@ -120,20 +121,18 @@ __device__ __forceinline__ Fp2<C> d_conj(const Lane6& L, const Fp2<C>& g) {   //
     return f2_sel<C>((L.m & 1) != 0, f2_neg<C>(g), g);
 }
 
-// multiply by the line through the twist point evaluated at P (see pairing.hpp for the forms)
-// three sparse terms as ONE dot product: 3 + 3 + 2 N^2 multiply-accumulates + one reduction pair
-template <class C>
+// multiply by the line through the twist point evaluated at P (see pairing.hpp for the forms).  UNIT = the table's form, the
+// same for every line a kernel reads: a template parameter of the pairing kernels, never a branch per line.
+// c form   : three sparse terms as ONE dot product: 3 + 3 + 2 N^2 multiply-accumulates + one reduction pair, + nl * xP
+// unit form: two terms and the constant term as the accumulator's initial value: 3 + 3 N^2 + one reduction pair, + the products with P
+template <class C, bool UNIT>
 __device__ __forceinline__ Fp2<C> d_mul_line(const Lane6& L, const Fp2<C>& g, const LineEntry<C>& le, const G1Aff<C>& P) {
-    // lx = nl * xP is the same on the six lanes of an item: each lane of a pair (m, m ^ 1) computes one of its two
-    // components and fetches the other (one Fp product + 14 ds_bpermute instead of two products)
-    const bool odd = (L.m & 1) != 0;
-    // (inlined multiplier: the called one takes half of its operands on the stack -- a scratch round trip per line)
-    const Fp<C> mine = fe_mul_i<typename C::FpP>(fe_select<typename C::FpP>(odd, le.nl.c1, le.nl.c0), P.x);
-    const Fp<C> other = fe_shfl<typename C::FpP>(mine, L.base + (L.m ^ 1));
-    const Fp2<C> lx = {fe_select<typename C::FpP>(odd, other, mine), fe_select<typename C::FpP>(odd, mine, other)};
     const int k = L.m;
     // l = c + lx w^2 + yP w^3 (M twist) :  c_k = g_k c + xi^[k<2] g_{k-2} lx + xi^[k<3] g_{k-3} yP
     // l = yP + lx w + c w^3   (D twist) :  c_k = g_k yP + xi^[k<1] g_{k-1} lx + xi^[k<3] g_{k-3} c
+    // unit form, r = R^-1, X = r (nl/c) xP, Y = r (1/c) yP:
+    // l = r + X w^2 + Y w^3   (M twist) :  c_k = r g_k + xi^[k<2] g_{k-2} X + xi^[k<3] g_{k-3} Y
+    // l = Y + X w + r w^3     (D twist) :  c_k = g_k Y + xi^[k<1] g_{k-1} X + r xi^[k<3] g_{k-3}
     constexpr int SA = C::K::TWIST_M ? 2 : 1;
     // g_(k - SA) is read from lane k - SA + 6 exactly when it wraps: lanes >= 6 - SA publish xi g for the first fetch, lanes
     // >= 3 for the second
@@ -141,17 +140,47 @@ __device__ __forceinline__ Fp2<C> d_mul_line(const Lane6& L, const Fp2<C>& g, co
     const Fp2<C> a = d_coef<C>(L, f2_sel<C>(k >= GRP - SA, gx, g), k < SA ? k + GRP - SA : k - SA);
     const Fp2<C> b = d_coef<C>(L, f2_sel<C>(k >= 3, gx, g), k < 3 ? k + 3 : k - 3);
     F2Acc<C> acc;
-    f2acc_zero<C>(acc);
-    if constexpr (C::K::TWIST_M) {
-        f2acc_mac<C, 1>(acc, g, le.c);
-        f2acc_mac<C, 1>(acc, a, lx);
-        f2acc_mac_fp<C>(acc, b, P.y);
+    if constexpr (UNIT) {
+        // X and Y are the same on the six lanes of an item: ONE lockstep Fp product computes their four components on lanes
+        // 0..3 (X.c0, X.c1, Y.c0, Y.c1; lanes 4 and 5 repeat lanes 0 and 1 and are not read), every lane fetches the four
+        // (inlined multiplier: the called one takes half of its operands on the stack -- a scratch round trip per line).
+        // Operand bounds: the components are products (normal, < 2p), a and b are published kernel values (normal): two
+        // terms of weight 1 in an accumulator made for six; the constant term is the accumulator's initial value.
+        const bool hi = (k & 2) != 0, odd = (k & 1) != 0;
+        const Fp<C> coef = fe_select<typename C::FpP>(hi, fe_select<typename C::FpP>(odd, le.c.c1, le.c.c0),
+                                                      fe_select<typename C::FpP>(odd, le.nl.c1, le.nl.c0));
+        const Fp<C> mine = fe_mul_i<typename C::FpP>(coef, fe_select<typename C::FpP>(hi, P.y, P.x));
+        const Fp2<C> X = {fe_shfl<typename C::FpP>(mine, L.base), fe_shfl<typename C::FpP>(mine, L.base + 1)};
+        const Fp2<C> Y = {fe_shfl<typename C::FpP>(mine, L.base + 2), fe_shfl<typename C::FpP>(mine, L.base + 3)};
+        if constexpr (C::K::TWIST_M) {
+            f2acc_init_rinv<C>(acc, g);
+            f2acc_mac<C, 1>(acc, a, X);
+            f2acc_mac<C, 1>(acc, b, Y);
+        } else {
+            f2acc_init_rinv<C>(acc, b);
+            f2acc_mac<C, 1>(acc, g, Y);
+            f2acc_mac<C, 1>(acc, a, X);
+        }
+        return f2acc_finish<C>(acc);
     } else {
-        f2acc_mac_fp<C>(acc, g, P.y);
-        f2acc_mac<C, 1>(acc, a, lx);
-        f2acc_mac<C, 1>(acc, b, le.c);
+        f2acc_zero<C>(acc);
+        // lx = nl * xP is the same on the six lanes of an item: each lane of a pair (m, m ^ 1) computes one of its two
+        // components and fetches the other (one Fp product + 14 ds_bpermute instead of two products)
+        const bool odd = (k & 1) != 0;
+        const Fp<C> mine = fe_mul_i<typename C::FpP>(fe_select<typename C::FpP>(odd, le.nl.c1, le.nl.c0), P.x);
+        const Fp<C> other = fe_shfl<typename C::FpP>(mine, L.base + (L.m ^ 1));
+        const Fp2<C> lx = {fe_select<typename C::FpP>(odd, other, mine), fe_select<typename C::FpP>(odd, mine, other)};
+        if constexpr (C::K::TWIST_M) {
+            f2acc_mac<C, 1>(acc, g, le.c);
+            f2acc_mac<C, 1>(acc, a, lx);
+            f2acc_mac_fp<C>(acc, b, P.y);
+        } else {
+            f2acc_mac_fp<C>(acc, g, P.y);
+            f2acc_mac<C, 1>(acc, a, lx);
+            f2acc_mac<C, 1>(acc, b, le.c);
+        }
+        return f2acc_finish<C>(acc);
     }
-    return f2acc_finish<C>(acc);
 }
 
 // Granger-Scott squaring of a cyclotomic element: Fp4 pairs (g_m, g_{m+3}), m = 0,1,2

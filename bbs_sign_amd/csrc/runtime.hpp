@@ -623,6 +623,7 @@ struct Ctx : bbs_ctx {
         std::vector<int8_t> status;  // per key: 1 accepted, BBS_ST_NOT_ON_CURVE refused
         std::vector<G2Aff<C>> pk;    // host copy of every key (a refused key: the identity, never read): what its prefixes per length are hashed from
         DevBuf d;                    // [n] KeyEntry<C>
+        bool unit = false;           // form of every line table of the set (lines_unit() when it was built)
         uint64_t lineage = 0;        // the same for a set and every set appended to it, new for a set that replaces one (SignSet)
     };
     std::shared_ptr<const KeySet> keys;
@@ -693,6 +694,25 @@ struct Ctx : bbs_ctx {
     std::atomic<int> live_jobs{0};
     bool latency_form_now() const { return latency_mode == 1 || (latency_mode == 2 && device_live_jobs(device).load() <= 2); }
     bool fix_tree = false;           // bbs_ctx_set_fixed_base_tree: the fixed-base sums as trees of affine additions
+    // Form of the Miller-loop line tables (pairing.hpp "Unit form", bbs_ctx_set_unit_lines).  ONE form per context: BP2's table,
+    // the public key's and every table of the key set have it, so a pairing kernel holds one form and a job picks its kernel
+    // by it -- for a keyed job that is the AND over its key set.  unit_lines is what the caller asked for (default: unit); a
+    // key whose walk meets c = 0 has no unit form, and while the context holds such a key every table is kept in the
+    // (c, nl) form (rebuild_lines, op_key.hpp).  dev_lines_unit is the form of the constants on the DEVICE (sync_consts),
+    // which is what a launch goes by.  Like a change of key, a change of form is for a context without jobs in flight.
+    bool unit_lines = true;
+    bool dev_lines_unit = false;
+    bool lines_unit() const { return hc.tab_bp2.unit != 0; }
+    bool lines_form_stale() const {  // a table in the other form, or the unit form wanted and not held
+        return (!hc.tab_pk.q_is_identity && hc.tab_pk.unit != hc.tab_bp2.unit) || (unit_lines && !lines_unit());
+    }
+    int rebuild_lines();             // every table again: the form asked for, or (c, nl) where some key has no unit form
+    int set_unit_lines(int enabled) {
+        std::lock_guard<std::mutex> g(mu);
+        unit_lines = enabled != 0;
+        if (lines_unit() == unit_lines) return BBS_OK;
+        return rebuild_lines();
+    }
     uint32_t rlc_seed[8] = {0};
     uint64_t rlc_counter = 0;
     std::mutex mu;                   // uploads may come from several host threads: counter and constant sync
@@ -733,7 +753,7 @@ struct Ctx : bbs_ctx {
         for (int k = 0; k < 3; k++) for (int m = 0; m < 6; m++) for (int c2 = 0; c2 < 2; c2++)
             for (int j = 0; j < N; j++) hc.frob[k][m][c2][j] = C::K::FROB[k][m][c2][j];
         build_schedule<C>(hc.sched);
-        if (!build_line_table<C>(g2_generator<C>(), hc.tab_bp2)) return BBS_E_ARG;
+        if (!build_line_table<C>(g2_generator<C>(), hc.tab_bp2, unit_lines)) return BBS_E_ARG;
         hc.tab_pk.q_is_identity = 1;
         hc.tab_pk.n_lines = 0;
         if (d_consts.alloc(sizeof(CtxConsts<C>))) return BBS_E_NOMEM;
@@ -801,6 +821,7 @@ struct Ctx : bbs_ctx {
         if (!consts_dirty) return BBS_OK;
         hc.tables = d_tables.as<uint32_t>();
         if (rt::h2d(d_consts.p, &hc, sizeof(hc), stream)) return BBS_E_HIP;
+        dev_lines_unit = lines_unit();
         consts_dirty = false;
         return BBS_OK;
     }
@@ -838,9 +859,12 @@ struct Ctx : bbs_ctx {
 
     int set_pk_internal(const G2Aff<C>& q) {
         if (!g2_on_curve<C>(q) || !g2_in_subgroup<C>(q)) return BBS_E_PUBLIC_KEY;
-        if (!build_line_table<C>(q, hc.tab_pk)) return BBS_E_PUBLIC_KEY;
+        if (!build_line_table<C>(q, hc.tab_pk, lines_unit())) return BBS_E_PUBLIC_KEY;
         pk = q;
         pk_set = true;
+        if (lines_form_stale()) {
+            if (const int rc = rebuild_lines()) return rc;
+        }
         rebuild_hash();
         return BBS_OK;
     }
@@ -879,7 +903,7 @@ struct Ctx : bbs_ctx {
     int8_t host_key_entry(const uint8_t* rec, bool is_inf, const uint8_t* oct, KeyEntry<C>& e, uint8_t* rec_out, int8_t* inf_out,
                           G2Aff<C>* q_out = nullptr) const;
     int key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const int8_t* is_inf, const uint8_t* oct, bool on_device,
-                  int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out = nullptr);
+                  int8_t* status, uint8_t* rec_out, int8_t* inf_out, G2Aff<C>* q_out = nullptr, size_t* n_other_form = nullptr);
     // the prefixes per (key, length) of bbs_ctx_set_keyed_mixed_lengths (op_key.hpp)
     int build_key_lens(const std::shared_ptr<const KeySet>& ks, const std::shared_ptr<const KeyLenSet>& old, size_t n_old,
                        std::shared_ptr<const KeyLenSet>& out);
@@ -1330,11 +1354,17 @@ void add_pairing_stages(J* j, PairArgs<C>* pargs, int aux, const char* nm_miller
     pargs->single = 0;      // always (stages.hpp PairArgs)
     if (split == PairSplit::Always || (split == PairSplit::ByJobForm && j->latency_form)) {
         // the two Miller loops of every item on separate wavefronts, then product + final exponentiation (stages.hpp)
-        j->stages.push_back({nm_miller, [j, pargs, aux]() { return rt::launch<PairMillerHalf<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 128); }, aux, 0});
+        j->stages.push_back({nm_miller, [j, pargs, aux]() { 
+            rt::Stream& st = aux ? j->stream_aux() : j->stream();
+            const size_t nt = ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 128;
+            return j->ctx->dev_lines_unit ? rt::launch<PairMillerHalf<C, true>>(st, *pargs, nt) : rt::launch<PairMillerHalf<C, false>>(st, *pargs, nt); }, aux, 0});
         j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinalDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
         return;
     }
-    j->stages.push_back({nm_dist, [j, pargs, aux]() { return rt::launch<PairDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
+    j->stages.push_back({nm_dist, [j, pargs, aux]() { 
+        rt::Stream& st = aux ? j->stream_aux() : j->stream();
+        const size_t nt = ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
+        return j->ctx->dev_lines_unit ? rt::launch<PairDist<C, true>>(st, *pargs, nt) : rt::launch<PairDist<C, false>>(st, *pargs, nt); }, aux, 0});
 #endif
 }
 
@@ -1414,6 +1444,7 @@ struct KeyedJob {
     const KeyEntry<C>* keys = nullptr;
     const uint32_t* kidx = nullptr;          // [n] key of item i, KEY_NONE: unknown / refused (decided by KeyGate)
     PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
+    bool unit = false;                       // line form of the key set the job holds (KeySet::unit)
 };
 // The host half, before the staging image is built: item i -> its key (KEY_NONE: unknown / refused) and the pairing order.
 // Items are sorted by key, stably (a counting sort); key k with c items fills floor(c / 10) key-uniform wavefronts, its c mod
@@ -1455,6 +1486,7 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJo
     words.resize(n + nu + nm + nu / W);
     kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
     kj.pair.keys = kj.keys; kj.pair.n_uni = nu; kj.pair.n_slots = nu + nm;
+    kj.unit = ks ? ks->unit : ctx->lines_unit();
 }
 // the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
 template <class C, class J>
@@ -1513,7 +1545,11 @@ void add_keyed_pairing_stages(J* j, KeyedJob<C>* kj, const PairArgs<C>* pa, int 
 #else
     j->stages.push_back({"pairing_6lane_keyed", [j, kj, pa, aux]() {
         kj->pair.p = *pa;
-        return rt::launch<PairDistKeyed<C>>(aux ? j->stream_aux() : j->stream(), kj->pair, ((kj->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64);
+        // the key set the job holds and BP2's table on the device must agree (they do unless the form was switched under the job)
+        if (kj->unit != j->ctx->dev_lines_unit) return -1;
+        rt::Stream& st = aux ? j->stream_aux() : j->stream();
+        const size_t nt = ((kj->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
+        return kj->unit ? rt::launch<PairDistKeyed<C, true>>(st, kj->pair, nt) : rt::launch<PairDistKeyed<C, false>>(st, kj->pair, nt);
     }, aux, 0});
 #endif
 }

@@ -10,6 +10,9 @@
 //     denominators of a key are inverted with ONE f2_inv (Montgomery's trick) and a second pass finishes the entries.  The
 //     host walk takes an Fp2 inversion per step.  The entries are equal as field elements; the stage stores the representative
 //     in [0, p) of every coordinate (the 28-bit limb form is not unique: a value may be stored as v or v + p).
+//   * the unit form (pairing.hpp; a.want_unit; entries times R^-1) needs 1/c = d / cn of every step: the product that is inverted runs over d cn
+//     (a zero cn counts as 1), and 1/d or 1/cn comes out of 1/(d cn) by one more product.  A key that meets cn = 0 keeps
+//     the (c, nl) form -- by selects, its lane stays with the wavefront -- and reports unit = 0, as build_line_table does.
 // Refusals of the line walk.  build_line_table refuses when T is the identity or the line is vertical; for a key that passed
 // the subgroup test (order exactly r) neither can happen: T = [k]Q with 1 < k < r at every addition, so T != +-Q, T is never
 // the identity or of order two, and on BN254 the Frobenius steps meet [6x+2]Q = +-[p]Q or [6x+2+p]Q = +-[p^2]Q for no key
@@ -42,14 +45,16 @@ struct KeyBuildArgs {
     uint32_t suffix_len;
     const HashCtx* hash0;        // dst_h2s of the context, dom_* zero
     Fp2<C> b2, gen_x, gen_y, frob_x, frob_y;     // twist constant, the generator (stand-in point), Frobenius constants (BN254)
+    int want_unit;               // the context's line form: entries (1/c, nl/c) where every c of the key is invertible
     int n_bits;
     uint8_t bits[KEY_MAX_BITS];  // Miller loop count, most significant bit first, the leading one dropped (miller_bits)
 };
 
-// workspace words per key: the denominator and the running product of every step of the line walk (n_steps = Miller loop
-// bits + the ones among them + the two Frobenius steps of BN254: 68 steps, 15232 bytes on BLS12-381)
+// workspace words per key: the denominator d, the factor d cn of the inverted product and the running product of every step
+// of the line walk (n_steps = Miller loop bits + the ones among them + the two Frobenius steps of BN254: 68 steps, 22848
+// bytes on BLS12-381)
 template <class C>
-constexpr size_t key_build_ws_words(size_t n_steps) { return n_steps * 2 * 2 * C::FpP::N; }
+constexpr size_t key_build_ws_words(size_t n_steps) { return n_steps * 3 * 2 * C::FpP::N; }
 
 // The point and root helpers are inlined into the kernel (their operands stay in registers) and are ordinary functions in a host
 // compilation, where one copy of each keeps the translation unit small.
@@ -169,11 +174,11 @@ BBS_HD bool kb_fe_gt_half(const Fe<P>& a) {
 }
 BBS_HD uint32_t kb_bswap(uint32_t l) { return (l << 24) | ((l & 0xff00u) << 8) | ((l >> 8) & 0xff00u) | (l >> 24); }
 
-// one step of the line walk: the entry's numerators go to the key's entry, its denominator and the running product of the
-// denominators to the workspace; T moves on.  dbl: the tangent at T; otherwise the line through T and (qx, qy).
+// one step of the line walk: the entry's numerators go to the key's entry, its denominator, the factor d cn and the running
+// product of the factors to the workspace; T moves on.  dbl: the tangent at T; otherwise the line through T and (qx, qy).
 template <class C>
 BBS_KB_HD void kb_line_step(const KeyBuildArgs<C>& a, size_t t, int s, bool dbl, G2Jac<C>& T, const Fp2<C>& qx, const Fp2<C>& qy,
-                         Fp2<C>& prod, bool& degenerate) {
+                         Fp2<C>& prod, bool& degenerate, bool& c_zero) {
     const Fp2<C> ZZ = f2_sqr<C>(T.z);
     Fp2<C> cn, nn, d;
     G2Jac<C> r;
@@ -203,11 +208,15 @@ BBS_KB_HD void kb_line_step(const KeyBuildArgs<C>& a, size_t t, int s, bool dbl,
     const bool dz = f2_is_zero<C>(d);
     degenerate |= dz;
     d = f2_select<C>(dz, f2_one<C>(), d);                              // (keeps the product invertible; the key is refused)
+    const bool cz = f2_is_zero<C>(cn);                                 // a line through the twist's origin: no unit form
+    c_zero |= cz;
+    const Fp2<C> dc = f2_mul<C>(d, f2_select<C>(cz, f2_one<C>(), cn));
     a.out[t].tab.e[s].c = cn;
     a.out[t].tab.e[s].nl = nn;
-    kb_ws_store<C>(a, t, 2 * s, d);
-    kb_ws_store<C>(a, t, 2 * s + 1, prod);                            // the product of the denominators BEFORE this step
-    prod = f2_mul<C>(prod, d);
+    kb_ws_store<C>(a, t, 3 * s, d);
+    kb_ws_store<C>(a, t, 3 * s + 1, dc);
+    kb_ws_store<C>(a, t, 3 * s + 2, prod);                            // the product of the factors BEFORE this step
+    prod = f2_mul<C>(prod, dc);
     T = r;
 }
 
@@ -278,34 +287,39 @@ struct KeyBuild {
         }
         // ---- 4. line table: the walk ...
         int ns = 0;
-        bool degenerate = false;
+        bool degenerate = false, c_zero = false;
         Fp2<C> prod = f2_one<C>();
         {
             G2Jac<C> T = {wx, wy, f2_one<C>()};
 #pragma unroll 1
             for (int k = 0; k < a.n_bits; k++) {
-                kb_line_step<C>(a, t, ns++, true, T, wx, wy, prod, degenerate);
-                if (a.bits[k]) kb_line_step<C>(a, t, ns++, false, T, wx, wy, prod, degenerate);
+                kb_line_step<C>(a, t, ns++, true, T, wx, wy, prod, degenerate, c_zero);
+                if (a.bits[k]) kb_line_step<C>(a, t, ns++, false, T, wx, wy, prod, degenerate, c_zero);
             }
             if constexpr (C::ID == 1) {                                // Q1 = frob(Q), Q2 = -frob(frob(Q))  (g2_frob_D)
                 const Fp2<C> x1 = f2_mul<C>(f2_conj<C>(wx), a.frob_x), y1 = f2_mul<C>(f2_conj<C>(wy), a.frob_y);
                 const Fp2<C> x2 = f2_mul<C>(f2_conj<C>(x1), a.frob_x), y2 = f2_neg<C>(f2_mul<C>(f2_conj<C>(y1), a.frob_y));
-                kb_line_step<C>(a, t, ns++, false, T, x1, y1, prod, degenerate);
-                kb_line_step<C>(a, t, ns++, false, T, x2, y2, prod, degenerate);
+                kb_line_step<C>(a, t, ns++, false, T, x1, y1, prod, degenerate, c_zero);
+                kb_line_step<C>(a, t, ns++, false, T, x2, y2, prod, degenerate, c_zero);
             }
         }
         refused |= degenerate;
         // ... one inversion, and the entries from the last to the first
         const bool table = !stand_in & !refused;
+        const bool unit = (a.want_unit != 0) & !c_zero;
         {
             Fp2<C> inv = f2_inv<C>(prod);
 #pragma unroll 1
             for (int s = ns - 1; s >= 0; s--) {
-                const Fp2<C> d = kb_ws_load<C>(a, t, 2 * s), before = kb_ws_load<C>(a, t, 2 * s + 1);
-                const Fp2<C> di = f2_mul<C>(inv, before);
-                inv = f2_mul<C>(inv, d);
+                const Fp2<C> d = kb_ws_load<C>(a, t, 3 * s), dc = kb_ws_load<C>(a, t, 3 * s + 1), before = kb_ws_load<C>(a, t, 3 * s + 2);
+                const Fp2<C> dci = f2_mul<C>(inv, before);             // 1 / (d cn)
+                inv = f2_mul<C>(inv, dc);
                 LineEntry<C>& e = a.out[t].tab.e[s];
-                const Fp2<C> c = f2_canon<C>(f2_mul<C>(e.c, di)), nl = f2_canon<C>(f2_mul<C>(e.nl, di));
+                // (c, nl) = (cn, nn) / d: times cn / (d cn);  (1/c, nl/c) = (d, nn) / cn: times d / (d cn)
+                const Fp2<C> cn1 = f2_select<C>(f2_is_zero<C>(e.c), f2_one<C>(), e.c);
+                // (the unit form stores plain residues: times R^-1, whose internal form is the integer 1)
+                const Fp2<C> di = f2_mul_fp<C>(f2_mul<C>(f2_select<C>(unit, d, cn1), dci), fe_select<typename C::FpP>(unit, f2_rinv<C>().c0, fe_one<typename C::FpP>()));
+                const Fp2<C> c = f2_canon<C>(f2_mul<C>(f2_select<C>(unit, d, e.c), di)), nl = f2_canon<C>(f2_mul<C>(e.nl, di));
                 e.c = f2_select<C>(table, c, f2_zero<C>());
                 e.nl = f2_select<C>(table, nl, f2_zero<C>());
             }
@@ -313,6 +327,7 @@ struct KeyBuild {
         KeyEntry<C>& o = a.out[t];
         o.tab.n_lines = table ? ns : 0;
         o.tab.q_is_identity = table ? 0 : 1;
+        o.tab.unit = (table & unit) ? 1 : 0;
         // ---- 5. domain midstate: Z_pad || compress(pk) || suffix  (g2_compress; the identity has its own encoding)
         uint32_t xw0[NC], xw1[NC];
         fe_to_words<P>(qx.c0, xw0);

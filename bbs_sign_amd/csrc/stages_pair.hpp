@@ -86,7 +86,7 @@ struct PairMiller {
             const int nops = a.cc->sched.n_ops;
             for (int k = 0; k < nops; k++) {
                 if (a.cc->sched.op[k] == 0) f = f12_sqr<C>(f);
-                else f = f12_mul_line<C>(f, tab->e[li++], P);
+                else f = f12_mul_line<C>(f, tab->e[li++], P, tab->unit != 0);
             }
             if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
         }
@@ -126,8 +126,9 @@ struct PairPrep {
 // wavefront-cooperative pairing check (pairing_dist.hpp): six lanes per item, Miller loop of both
 // pairs (shared squarings) and the final exponentiation fused in one kernel, nothing spilled to HBM.
 // Thread index: wave = t / 64 ; group = (t % 64) / 6 ; item = wave * 10 + group.
+// UNIT: the form of BOTH line tables (pairing.hpp "Unit form"), picked by the host per job.
 // =============================================================================================
-template <class C>
+template <class C, bool UNIT>
 struct PairDist {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
@@ -156,8 +157,8 @@ struct PairDist {
                 if (cc->sched.op[k] == 0) {
                     m = d_sqr<C>(L, m);
                 } else {
-                    if (!skipA) m = d_mul_line<C>(L, m, cc->tab_pk.e[li], Pa);
-                    if (!skipB) m = d_mul_line<C>(L, m, cc->tab_bp2.e[li], Pb);
+                    if (!skipA) m = d_mul_line<C, UNIT>(L, m, cc->tab_pk.e[li], Pa);
+                    if (!skipB) m = d_mul_line<C, UNIT>(L, m, cc->tab_bp2.e[li], Pb);
                     li++;
                 }
             }
@@ -178,7 +179,7 @@ struct PairDist {
 // squarings + 68 line products (0.66 of the joint loop), the two values are handed over in HBM ([pair][coefficient]
 // [2N][n], coalesced over the items' lanes m) and PairFinalDist multiplies them and runs the final exponentiation:
 // 820 wavefronts x 0.66 + 410 wavefronts x 1 instead of 410 x 2: 17 % more wave-time, a critical path ~0.8 ms shorter.
-template <class C>
+template <class C, bool UNIT>
 struct PairMillerHalf {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
@@ -204,7 +205,7 @@ struct PairMillerHalf {
             const int nops = cc->sched.n_ops;
             for (int k = 0; k < nops; k++) {
                 if (cc->sched.op[k] == 0) m = d_sqr<C>(L, m);
-                else m = d_mul_line<C>(L, m, tab.e[li++], P);
+                else m = d_mul_line<C, UNIT>(L, m, tab.e[li++], P);
             }
             if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
         }

@@ -202,7 +202,10 @@ struct SelfTestDist {
         else if constexpr (OP == 3) rd = d_frob<C, 3>(L, gx, ft);
         else if constexpr (OP == 4) rd = d_inv<C>(L, gx);
         else if constexpr (OP == 5) rd = d_conj<C>(L, gx);
-        else if constexpr (OP == 6) rd = d_mul_line<C>(L, gx, (a.line_table ? a.cc->tab_bp2 : a.cc->tab_pk).e[a.line_index], P);
+        else if constexpr (OP == 6) {                      // (the table's form: uniform over the launch)
+            const LineTable<C>& tab = a.line_table ? a.cc->tab_bp2 : a.cc->tab_pk;
+            rd = tab.unit ? d_mul_line<C, true>(L, gx, tab.e[a.line_index], P) : d_mul_line<C, false>(L, gx, tab.e[a.line_index], P);
+        }
         else if constexpr (OP == 7) rd = d_final_exp<C>(L, gx, ft);
         else if constexpr (OP == 10) rd = d_cyclo_sqr<C>(L, gx);
         else if constexpr (OP == 8) rd = d_sqr<C>(L, gx);

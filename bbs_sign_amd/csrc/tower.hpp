@@ -74,6 +74,26 @@ template <class C>
 BBS_HD void f2acc_zero(F2Acc<C>& acc) {
     r28::cols_zero<FP>(acc.t0); r28::cols_zero<FP>(acc.t1); r28::cols_zero<FP>(acc.ts);
 }
+// R^-1 (R = 2^(28 N), the Montgomery radix): the field element whose internal form is the integer 1
+template <class C>
+BBS_HD Fp2<C> f2_rinv() {
+    Fp2<C> r = f2_zero<C>();
+    r.c0.v[0] = 1;
+    return r;
+}
+// acc = u * R^-1 instead of zero: the product of u with the integer 1 is u itself, so its limbs (Karatsuba: u0 into t0, u0 + u1
+// into ts) become the initial low columns -- a term of the dot product for 2 N additions and no multiplication.  u normal; it adds
+// less than 2p to a sum whose bound is counted in p^2, so it takes no weight.
+template <class C>
+BBS_HD void f2acc_init_rinv(F2Acc<C>& acc, const Fp2<C>& u) {
+    constexpr int N = C::FpP::N;
+    f2acc_zero<C>(acc);
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        acc.t0[i] = u.c0.v[i];
+        acc.ts[i] = u.c0.v[i] + u.c1.v[i];
+    }
+}
 template <class C, int W = 1>
 BBS_HD void f2acc_mac(F2Acc<C>& acc, const Fp2<C>& a, const Fp2<C>& b) {
     constexpr int N = C::FpP::N;
@@ -527,6 +547,29 @@ BBS_HD_NOINLINE Fp12<C> f12_mul_by_line_D(const Fp12<C>& f, const Fp2<C>& l0, co
     Fp2<C> l0y = l0;
     l0y.c0 = fe_add<FP>(l0y.c0, yP);
     Fp6<C> s = f6_mul_by_01<C>(f6_add<C>(f.c0, f.c1), l0y, l1);
+    return {f6_add<C>(v0, f6_mul_v<C>(v1)), f6_sub<C>(f6_sub<C>(s, v0), v1)};
+}
+
+// the same lines scaled to the constant term R^-1 (pairing.hpp "Unit form"): lx, ly in Fp2
+// M-type twist: line = (R^-1 + lx v) + (ly v) w
+template <class C>
+BBS_HD_NOINLINE Fp12<C> f12_mul_by_line_M_unit(const Fp12<C>& f, const Fp2<C>& lx, const Fp2<C>& ly) {
+    // A = (R^-1, lx, 0), B = (0, ly, 0)
+    const Fp2<C> one = f2_rinv<C>();
+    Fp6<C> v0 = f6_mul_by_01<C>(f.c0, one, lx);
+    Fp6<C> v1 = f6_mul_by_1<C>(f.c1, ly);
+    Fp6<C> s = f6_mul_by_01<C>(f6_add<C>(f.c0, f.c1), one, f2_add<C>(lx, ly));
+    return {f6_add<C>(v0, f6_mul_v<C>(v1)), f6_sub<C>(f6_sub<C>(s, v0), v1)};
+}
+
+// D-type twist: line = ly + (lx + R^-1 v) w
+template <class C>
+BBS_HD_NOINLINE Fp12<C> f12_mul_by_line_D_unit(const Fp12<C>& f, const Fp2<C>& lx, const Fp2<C>& ly) {
+    // A = (ly, 0, 0), B = (lx, R^-1, 0)
+    const Fp2<C> one = f2_rinv<C>();
+    Fp6<C> v0 = f6_mul_by_0<C>(f.c0, ly);
+    Fp6<C> v1 = f6_mul_by_01<C>(f.c1, lx, one);
+    Fp6<C> s = f6_mul_by_01<C>(f6_add<C>(f.c0, f.c1), f2_add<C>(lx, ly), one);
     return {f6_add<C>(v0, f6_mul_v<C>(v1)), f6_sub<C>(f6_sub<C>(s, v0), v1)};
 }
 

@@ -1,7 +1,8 @@
 // explicit instantiation: key registration for BlsCurve
 #include "op_key.hpp"
 template int8_t Ctx<BlsCurve>::host_key_entry(const uint8_t*, bool, const uint8_t*, KeyEntry<BlsCurve>&, uint8_t*, int8_t*, G2Aff<BlsCurve>*) const;
-template int Ctx<BlsCurve>::key_build(KeyEntry<BlsCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, bool, int8_t*, uint8_t*, int8_t*, G2Aff<BlsCurve>*);
+template int Ctx<BlsCurve>::key_build(KeyEntry<BlsCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, bool, int8_t*, uint8_t*, int8_t*, G2Aff<BlsCurve>*, size_t*);
+template int Ctx<BlsCurve>::rebuild_lines();
 template int Ctx<BlsCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
 template int Ctx<BlsCurve>::build_key_lens(const std::shared_ptr<const Ctx<BlsCurve>::KeySet>&, const std::shared_ptr<const Ctx<BlsCurve>::KeyLenSet>&, size_t,
                                                std::shared_ptr<const Ctx<BlsCurve>::KeyLenSet>&);

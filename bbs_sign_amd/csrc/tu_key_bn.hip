@@ -1,7 +1,8 @@
 // explicit instantiation: key registration for BnCurve
 #include "op_key.hpp"
 template int8_t Ctx<BnCurve>::host_key_entry(const uint8_t*, bool, const uint8_t*, KeyEntry<BnCurve>&, uint8_t*, int8_t*, G2Aff<BnCurve>*) const;
-template int Ctx<BnCurve>::key_build(KeyEntry<BnCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, bool, int8_t*, uint8_t*, int8_t*, G2Aff<BnCurve>*);
+template int Ctx<BnCurve>::key_build(KeyEntry<BnCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, bool, int8_t*, uint8_t*, int8_t*, G2Aff<BnCurve>*, size_t*);
+template int Ctx<BnCurve>::rebuild_lines();
 template int Ctx<BnCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
 template int Ctx<BnCurve>::build_key_lens(const std::shared_ptr<const Ctx<BnCurve>::KeySet>&, const std::shared_ptr<const Ctx<BnCurve>::KeyLenSet>&, size_t,
                                                std::shared_ptr<const Ctx<BnCurve>::KeyLenSet>&);

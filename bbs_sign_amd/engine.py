@@ -402,6 +402,11 @@ class Engine:
         key with its own message count 0 .. L (jobs created afterwards); independent of set_mixed_lengths."""
         self._chk(self.lib.bbs_ctx_set_keyed_mixed_lengths(self.h, 1 if on else 0), "bbs_ctx_set_keyed_mixed_lengths")
 
+    def set_unit_lines(self, on: bool):
+        """bbs_ctx_set_unit_lines: the Miller-loop line tables of this engine in the unit form (the default) or the (c, nl)
+        form; rebuilds the tables, same verdicts."""
+        self._chk(self.lib.bbs_ctx_set_unit_lines(self.h, 1 if on else 0), "bbs_ctx_set_unit_lines")
+
     def set_fixed_base_tree(self, enabled: bool):
         """bbs_ctx_set_fixed_base_tree: fixed-base sums as one tree of affine additions per item (jobs created afterwards)."""
         self._chk(self.lib.bbs_ctx_set_fixed_base_tree(self.h, 1 if enabled else 0), "bbs_ctx_set_fixed_base_tree")

@@ -245,6 +245,17 @@ int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
  * NOT covered: bbs_issuer and bbs_pool do not route through it; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled);
 
+/* Form of the Miller-loop line tables (on by default).  Both G2 arguments of a pairing product are fixed per key, so the
+ * lines of a table can be scaled by the inverse of their constant term c (an element of Fp2: the final exponentiation
+ * removes it) and a line costs the pairing kernel two sparse products instead of three.  enabled = 1: every table of the
+ * context -- BP2's, the public key's, the key set's -- is kept in that unit form; a key whose walk meets c = 0 (a line
+ * through the twist's origin) has none, and while the context holds such a key all its tables are kept in the (c, nl) form,
+ * so such a key keeps working.  enabled = 0: the (c, nl) form throughout.  Verdicts are the same in both forms; the switch
+ * exists to measure one against the other in one build and to test the fallback.  The call rebuilds the tables on the host
+ * (BBS_E_NOMEM / BBS_E_HIP as registration) and, like a change of key, is meant for a context without jobs in flight: a
+ * keyed job that was created before the switch fails its pairing stage instead of mixing forms.  BBS_E_ARG for a NULL ctx. */
+int bbs_ctx_set_unit_lines(bbs_ctx* ctx, int enabled);
+
 /* Batch verification for core_proof_verify and core_verify (off by default).  When enabled, the n two-pairing
  * products of a batch (src/proof_verify.rs:112-115, src/verify.rs:88-92) are replaced by 16 products over random
  * linear combinations of the items' G1 arguments (sum rho_i * Abar_i, sum rho_i * Bbar_i; for verify
