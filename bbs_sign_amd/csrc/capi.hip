@@ -833,7 +833,7 @@ int bbs_sign_wire_submit(bbs_ctx* ctx, size_t n, const uint8_t* msg_bytes, const
                          const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status, bbs_job** job_out) {
     return sign_wire_submit<false>(ctx, n, nullptr, msg_bytes, msg_byte_off, msg_item_off, h, ho, sig_octets_out, status, job_out);
 }
-// keyed sign (keyed.hpp SgScalarsKeyed; op_sg.hpp): item i under key key_index[i] of the context's key set and signing set
+// keyed sign (stages_sg.hpp SgScalarsIn; op_sg.hpp): item i under key key_index[i] of the context's key set and signing set
 int bbs_sign_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                                const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, uint8_t* sig_octets_out, int8_t* status,
                                bbs_job** job_out) {
@@ -885,7 +885,7 @@ int bbs_core_proof_gen_submit(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const
     if (rc) return rc;
     return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
 }
-// keyed proof_gen (keyed.hpp PgScalarsKeyed; op_pg.hpp): item i under key key_index[i] of the context's key set
+// keyed proof_gen (stages_pg.hpp PgScalarsIn; op_pg.hpp): item i under key key_index[i] of the context's key set
 int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                                     const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
                                     const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,

@@ -1,6 +1,6 @@
 // Keyed verification (bbs_ctx_set_public_keys, bbs_*_keyed_*): every item of a batch names one key of the context's KEY SET
 // instead of the context's single public key.  Only two things of a verification depend on the key: the Miller-loop line
-// table of W = pk and the midstate of the domain hash.  A key-set entry holds both; everything else (the fixed-base window
+// table of W = pk and the midstate of the domain hash.  A key-set entry (stages_common.hpp KeyEntry) holds both; everything else (the fixed-base window
 // tables, BP2's line table, the Frobenius constants) stays in CtxConsts and is shared by all keys.
 //
 // Pairing order.  The six-lane pairing kernel (PairDist) reads W's line entries with SCALAR loads: the table is the same
@@ -19,12 +19,6 @@
 
 namespace bbs {
 
-template <class C>
-struct KeyEntry {
-    LineTable<C> tab;            // lines of W = this key
-    HashCtx hash;                // domain prefix midstate with this key (dst_h2s as the context's)
-};
-
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;     // item whose key index is unknown or names a refused key
 constexpr int KEY_SLOTS_PER_WAVE = 10;         // == GRP_PER_WAVE (pairing_dist.hpp)
 
@@ -36,117 +30,19 @@ struct KeyGate {
     }
 };
 
-// the domain of a keyed item from its key's entry (lane per item, as PvScalars / VfScalars)
-template <class C, class A>
-struct KeyedScalarArgs { A a; const KeyEntry<C>* keys; const uint32_t* kidx; };
-template <class C>
-struct PvScalarsKeyed {
-    static __host__ __device__ void run(const KeyedScalarArgs<C, PvArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        pv_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
-    }
-};
-template <class C>
-struct VfScalarsKeyed {
-    static __host__ __device__ void run(const KeyedScalarArgs<C, VfArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        vf_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
-    }
-};
-
-// keyed proof_gen (bbs_*proof_gen*_keyed_*): the key enters a proof in calculate_domain alone (no pairing, no W), so this stage
-// is all a keyed producing job has of its own; PgBPart .. PgEmit follow unchanged
-template <class C>
-struct PgScalarsKeyed {
-    static __host__ __device__ void run(const KeyedScalarArgs<C, PgArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        pg_scalars_item<C>(k.a, i, k.keys[k.kidx[i]].hash, k.a.L);
-    }
-};
-
-// Keyed jobs of mixed message counts (bbs_ctx_set_keyed_mixed_lengths): item i under its own key kidx[i] with its own count
-// len[i] <= L (written by the MIXED ingest bodies, which such a job launches where a keyed job launches the fixed-length ones;
-// KeyGate follows unchanged).  The domain starts from the prefix of THAT key and THAT length, pref[kidx * stride + l] (runtime.hpp
-// KeyLenSet, stride = L + 1), the scalars of the bases H_{l+1} .. H_L are written as zero as in PvScalarsMixed.  Everything
-// downstream takes either axis unchanged.  The arguments wrap the existing structs: no other kernel's argument layout changes.
-// Only a pending item is looked at: KEY_NONE (decided by KeyGate) and l > L (decided at ingest, len = 0) never index anything.
-// The index diverges per lane, so the 368 bytes of the HashCtx are read with vector loads through a per-lane pointer -- the
-// struct is passed on by reference, as PvScalarsKeyed does, never copied into a local (368 B of scratch per lane).
-template <class C, class A>
-struct KeyedMixedScalarArgs { A a; const HashCtx* pref; uint32_t stride; const uint32_t* kidx; const uint32_t* len; };
-template <class C>
-struct PvScalarsKeyedMixed {
-    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, PvArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        const int l = (int)k.len[i];
-        pv_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
-        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
-    }
-};
-template <class C>
-struct VfScalarsKeyedMixed {
-    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, VfArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        const int l = (int)k.len[i];
-        vf_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
-        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
-    }
-};
-// (zeros in BOTH scalar arrays, as PgScalarsMixed: B's sum and T2's run over the same bases)
-template <class C>
-struct PgScalarsKeyedMixed {
-    static __host__ __device__ void run(const KeyedMixedScalarArgs<C, PgArgs<C>>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        const int l = (int)k.len[i];
-        pg_scalars_item<C>(k.a, i, k.pref[(size_t)k.kidx[i] * k.stride + (size_t)l], l);
-        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
-        mixed_zero_scalars(k.a.fscal2, k.a.n, i, l, k.a.L);
-    }
-};
-
-// Keyed sign (bbs_*sign*_keyed_*): item i under key kidx[i] of the context's key set AND its signing set (runtime.hpp SignSet:
-// row k = the 8 canonical words of sk_k, 32 bytes, 32-byte aligned).  core_sign meets the key in the domain (the key's midstate,
-// or the prefix of (key, length)), in the hash that gives e and in 1 / (sk + e); SgMsmPart .. SgEmit never see a key and follow
-// unchanged.  The row index diverges per lane, so the row is read with vector loads into the lane's registers; the index is the
-// caller's public key_index.  The gate decides every item that has no secret row before the scalar stage runs: KEY_NONE as
-// KeyGate does, KEY_NO_SECRET (an accepted key that was registered public-only) as BBS_ST_NO_SECRET_KEY -- neither ever indexes
-// the signing set, a midstate or a prefix.
+// The domain of a keyed item: the scalar stages in their Keyed / KeyedMixed forms (stages_common.hpp DomainSrc, form_domain;
+// stages_*.hpp *ScalarsIn), instantiated from the keyed translation units only.
+//
+// Keyed sign (bbs_*sign*_keyed_*): item i under key kidx[i] of the context's key set AND its signing set (stages_sg.hpp
+// sign_key_row).  The gate decides every item that has no secret row before the scalar stage runs: KEY_NONE as KeyGate does,
+// KEY_NO_SECRET (an accepted key that was registered public-only) as BBS_ST_NO_SECRET_KEY -- neither ever indexes the signing
+// set, a midstate or a prefix.
 constexpr uint32_t KEY_NO_SECRET = 0xFFFFFFFEu;
 struct SignKeyGate {
     static __host__ __device__ void run(const KeyGateArgs& a, size_t i) {
         const uint32_t k = a.kidx[i];
         if (k == KEY_NONE) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
         else if (k == KEY_NO_SECRET) a.status0[i] = (int8_t)BBS_ST_NO_SECRET_KEY;
-    }
-};
-BBS_HD void sign_key_row(const uint32_t* sks, uint32_t k, uint32_t* sk) {
-    const uint32_t* row = static_cast<const uint32_t*>(__builtin_assume_aligned(sks + (size_t)8 * k, 32));
-    for (int j = 0; j < 8; j++) sk[j] = row[j];
-}
-template <class C>
-struct KeyedSignArgs { SgArgs<C> a; const KeyEntry<C>* keys; const uint32_t* kidx; const uint32_t* sks; };
-template <class C>
-struct SgScalarsKeyed {
-    static __host__ __device__ void run(const KeyedSignArgs<C>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        const uint32_t key = k.kidx[i];
-        uint32_t sk[8];
-        sign_key_row(k.sks, key, sk);
-        sg_scalars_item<C>(k.a, i, k.keys[key].hash, sk, k.a.L);
-    }
-};
-template <class C>
-struct KeyedMixedSignArgs { SgArgs<C> a; const HashCtx* pref; uint32_t stride; const uint32_t* kidx; const uint32_t* len; const uint32_t* sks; };
-template <class C>
-struct SgScalarsKeyedMixed {
-    static __host__ __device__ void run(const KeyedMixedSignArgs<C>& k, size_t i) {
-        if (k.a.status[i] != ST_PENDING) return;
-        const int l = (int)k.len[i];
-        const uint32_t key = k.kidx[i];
-        uint32_t sk[8];
-        sign_key_row(k.sks, key, sk);
-        sg_scalars_item<C>(k.a, i, k.pref[(size_t)key * k.stride + (size_t)l], sk, l);
-        mixed_zero_scalars(k.a.fscal, k.a.n, i, l, k.a.L);
     }
 };
 

@@ -168,8 +168,8 @@ int sk_to_pk_batch(Ctx<C>* ctx, size_t n, const uint8_t* sk32, uint8_t* pk_affin
     return crc ? BBS_E_HIP : BBS_OK;
 }
 
-// Registration of secret keys for keyed sign (bbs_ctx_set_secret_keys / bbs_ctx_add_secret_keys; runtime.hpp SignSet, keyed.hpp
-// SgScalarsKeyed).  The public halves of the whole call come from the KgPublic stage, as sk_to_pk_batch's do, and then go
+// Registration of secret keys for keyed sign (bbs_ctx_set_secret_keys / bbs_ctx_add_secret_keys; runtime.hpp SignSet, stages_sg.hpp
+// SgScalarsIn).  The public halves of the whole call come from the KgPublic stage, as sk_to_pk_batch's do, and then go
 // through add_keys like keys that arrive as records: a secret-registered key IS a public-registered key plus its row of the
 // signing set, under the same index.  A scalar >= r is refused: BBS_ST_NONCANONICAL, a refused public entry, a zero row.
 // Order: derive; build the new signing set (exactly n_old + n rows: the old rows copied device to device, zero rows for the

@@ -11,8 +11,7 @@ struct PgJob : JobBase<C> {
     PgIngestArgs<C> ingest{};
     VfOctArgs<C> oct{};               // signature octets in (wire form) only
     MsgHashArgs mh{};                 // raw-message form only
-    KeyedJob<C> kj{};                 // keyed form only (its pairing order stays empty: a proof is derived without a pairing)
-    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths_gen, bbs_ctx_set_keyed_mixed_lengths)
+    JobForm<C> jf{};                  // the job's form (job_form.hpp)
     // The proofs come off the device in the caller's layout (stage PgEmit): records, the m^ of the undisclosed messages
     // in ascending index order (L slots per item, the first ucount[i] used) and those counts.  Host side of a delivery:
     // one copy of the records, one contiguous copy per item of its commitments, the running offsets.
@@ -87,6 +86,8 @@ struct PgJob : JobBase<C> {
     }
 };
 
+constexpr const char* PG_SCALARS[4] = {"pg_scalars", "pg_scalars_mixed", "pg_scalars_keyed", "pg_scalars_keyed_mixed"};
+
 // KEYED (bbs_*proof_gen*_keyed_*, instantiated in tu_pgk_*.hip): item i is derived under key key_index[i] of the context's key
 // set (keyed.hpp).  The key enters through the domain alone (proof_gen.rs:78-113 -> calculate_domain): the scalar stage reads
 // the key's midstate, or the prefix of (key, length), and every other stage is the single-key job's.  The context's single
@@ -96,18 +97,8 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
-    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
-    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
-    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
-    if constexpr (KEYED) {
-        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
-        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
-        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
-        if (ctx->mixed_lengths_gen && !keyed_mixed) return BBS_E_STATE;
-        if (n && !in.key_index) return BBS_E_ARG;
-    } else {
-        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
-    }
+    Form form;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::ProofGen, n, in.key_index, form)) return rcf;
     const bool wire = in.signature_octets != nullptr, raw = in.msg_byte_off != nullptr;
     if (!out || (n && ((!in.signatures && !wire) || !in.msg_off || !in.didx_off || !in.rnd_off || !in.random_scalars))) return BBS_E_ARG;
     const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
@@ -116,14 +107,14 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     const size_t rec = wire ? (size_t)FPB + 32 : (size_t)2 * FPB + 32;
     auto job = std::unique_ptr<PgJob<C>>(new PgJob<C>(ctx));
     job->n = n;
+    job->jf.form = form;
     RaggedIn ms{in.msg_off, in.messages, 32}, di{in.didx_off, reinterpret_cast<const uint8_t*>(in.disclosed_idx), 8}, rs{in.rnd_off, in.random_scalars, 32},
              hb{in.hdr_off, in.headers, 1}, pb{in.ph_off, in.ph, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !di.measure(n) || !rs.measure(n) || !hb.measure(n) || !pb.measure(n)) return BBS_E_ARG;
-    const size_t nm = raw ? (size_t)ms.total : 0;
-    // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
-    if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
+    RaggedIn mb{};
+    size_t nm;
+    if (!raw_message_section(ms, in.msg_byte_off, in.msg_bytes, mb, nm)) return BBS_E_ARG;
     if (hb.total > 0xF0000000ull || pb.total > 0xF0000000ull) return BBS_E_ARG;
     // Host side, one comparison per item (no field data is touched): the contract of this ABI on the number of random
     // scalars (proof_gen.rs:145-149; checked where the reference would have got that far).  Everything else -- the
@@ -142,17 +133,17 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     }
     std::vector<uint32_t> kwords;     // keyed: the key indexes, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
+    if constexpr (KEYED) keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
     if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
-    if constexpr (KEYED) job->kj.kidx = reinterpret_cast<const uint32_t*>(dimg + kwords_at);
+    if constexpr (KEYED) keyed_bind<C>(job->jf, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     auto d64 = [&](size_t at) { return reinterpret_cast<const uint64_t*>(dimg + at); };
     auto d32 = [&](size_t at) { return reinterpret_cast<const uint32_t*>(dimg + at); };
     int rc = BBS_OK;
     const size_t Lw = (size_t)std::max(L, 1), nn = std::max<size_t>(n, 1);
     PgArgs<C>& a = job->a;
     a.n = n; a.L = L; a.Rmax = (int)Lw; a.cc = ctx->d_consts.template as<CtxConsts<C>>();
-    a.glv = (C::K::HAS_GLV && (C::K::GLV_ALWAYS || ctx->points_in_subgroup || wire)) ? 1 : 0;   // wire: the decoder checked A
+    a.glv = glv_flag<C>(ctx, wire);
     PgIngestArgs<C>& ia = job->ingest;
     ia.n = n; ia.L = L; ia.dst_too_long = ctx->dst_too_long ? 1 : 0;
     ia.rec = wire ? nullptr : d32(0);
@@ -220,33 +211,20 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     if ((rc = job->finish_setup_device())) return rc;
     a.status = job->d_status.template as<int8_t>();
     ia.status0 = job->d_status0.template as<int8_t>();
-    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
-    const bool mixed = !KEYED && ctx->mixed_lengths_gen;
-    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED bodies serve both
-    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (mixed_ingest && rt::launch<PgIngestMixed<C>>(job->stream(), MixedIngestArgs<PgIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-    if (!mixed_ingest && rt::launch<PgIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if ((rc = launch_ingest<PgIngest<C>, PgIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
+        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, ia.status0))) return rc;
     }
     PgJob<C>* j = job.get();
-    if constexpr (KEYED) {
-        if (keyed_mixed)
-            j->stages.push_back({"pg_scalars_keyed_mixed", [j]() { return rt::launch<PgScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, PgArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
-        else
-            j->stages.push_back({"pg_scalars_keyed", [j]() { return rt::launch<PgScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PgArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
-    } else if (mixed)
-        j->stages.push_back({"pg_scalars_mixed", [j]() { return rt::launch<PgScalarsMixed<C>>(j->stream(), MixedScalarArgs<PgArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
-    else
-        j->stages.push_back({"pg_scalars", [j]() { return rt::launch<PgScalars<C>>(j->stream(), j->a, j->n); }});
+    add_scalar_stage<C, KEYED, PgScalars<C>, PgScalarsIn>(j, PG_SCALARS);
     j->stages.push_back({"pg_b_parts", [j]() { return rt::launch<PgBPart<C>>(j->stream(), j->a, j->n * (size_t)(2 * NFIX)); }});
     j->stages.push_back({"pg_b_combine", [j]() { return rt::launch<PgBCombine<C>>(j->stream(), j->a, j->n); }});
     if (j->a.ctab) j->stages.push_back({"pg_tables", [j]() { return rt::launch<PgTables<C>>(j->stream(), j->a, j->n * 2); }});
     j->stages.push_back({"pg_var_parts", [j]() { return rt::launch<PgVarPart<C>>(j->stream(), j->a, j->n * (size_t)j->a.nvar); }});
-    if (mixed_ingest) {
-        j->stages.push_back({"pg_finalize_mixed", [j]() { return rt::launch<PgFinalizeMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
-        j->stages.push_back({"pg_emit_mixed", [j]() { return rt::launch<PgEmitMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->mx.len}, j->n); }});
+    if (j->jf.mixed()) {
+        j->stages.push_back({"pg_finalize_mixed", [j]() { return rt::launch<PgFinalizeMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->jf.src.len}, j->n); }});
+        j->stages.push_back({"pg_emit_mixed", [j]() { return rt::launch<PgEmitMixed<C>>(j->stream(), MixedLenArgs<PgArgs<C>>{j->a, j->jf.src.len}, j->n); }});
     } else {
         j->stages.push_back({"pg_finalize", [j]() { return rt::launch<PgFinalize<C>>(j->stream(), j->a, j->n); }});
         j->stages.push_back({"pg_emit", [j]() { return rt::launch<PgEmit<C>>(j->stream(), j->a, j->n); }});

@@ -23,9 +23,9 @@ struct PvJob : JobBase<C> {
     PvOctArgs<C> oct{};               // wire form only
     MsgHashArgs mh{};                 // wire form with raw messages only
     BvState<C> bv{};                  // batch verification only
-    KeyedJob<C> kj{};                 // keyed form only
-    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths, bbs_ctx_set_keyed_mixed_lengths)
+    PairedJobForm<C> jf{};            // the job's form (job_form.hpp)
 };
+constexpr const char* PV_SCALARS[4] = {"pv_scalars", "pv_scalars_mixed", "pv_scalars_keyed", "pv_scalars_keyed_mixed"};
 
 // the form is deduced from the fields of PvIn that are set (ops_decl.hpp)
 // KEYED (bbs_*_keyed_*, instantiated in tu_pvk_*.hip): item i is verified under key key_index[i] of the context's key set
@@ -38,18 +38,8 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;        // internal limbs
     constexpr int NC = C::FpP::NC;      // canonical 32-bit words
     constexpr int FPB = 4 * NC;
-    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
-    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
-    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
-    if constexpr (KEYED) {
-        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
-        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
-        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
-        if (ctx->mixed_lengths && !keyed_mixed) return BBS_E_STATE;
-        if (n && !in.key_index) return BBS_E_ARG;
-    } else {
-        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
-    }
+    Form form;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form)) return rcf;
     if (!out || (n && (!in.dmsg_off || !in.didx_off))) return BBS_E_ARG;
     if (n && !wire && (!in.proofs_fixed || !in.commit_off)) return BBS_E_ARG;
     if (n && wire && !in.proof_octets) return BBS_E_ARG;
@@ -58,12 +48,10 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     const size_t rec = 6 * FPB + 128;
     auto job = std::unique_ptr<PvJob<C>>(new PvJob<C>(ctx));
     job->n = n;
+    job->jf.form = form;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
-    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
-    const bool mixed = !KEYED && ctx->mixed_lengths;
-    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED ingest bodies serve both
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
     // ---- the batch as one staging image in page-locked memory, one asynchronous copy; everything else (the
     // reference's checks, range checks, unpacking, the SoA transposition) happens on the device: stage PvIngest
     // first ragged section: the commitments (core form) or the proof octet strings (wire form)
@@ -72,23 +60,20 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     dm.offsets_only = raw;
     if (!cm.measure(n) || !dm.measure(n) || !di.measure(n) || !hb.measure(n) || !pb.measure(n)) return BBS_E_ARG;
     if (hb.total > 0xF0000000ull || pb.total > 0xF0000000ull) return BBS_E_ARG;
-    const size_t nm = raw ? (size_t)dm.total : 0;                   // disclosed messages of the whole batch
-    // (message t of the batch is entry dmsg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.dmsg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
-    if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
-    // (the message section is ragged over MESSAGES, not items: stage_image places and fills it with nm as its count)
+    RaggedIn mb{};
+    size_t nm;                                                      // disclosed messages of the whole batch (raw form)
+    if (!raw_message_section(dm, in.msg_byte_off, in.msg_bytes, mb, nm)) return BBS_E_ARG;
     if (int rc0 = stage_image(job.get(), n, wire ? nullptr : in.proofs_fixed, wire ? 0 : rec, {&cm, &dm, &di, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
 
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
-    if constexpr (KEYED) keyed_bind<C>(job->kj, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
+    if constexpr (KEYED) keyed_bind<C>(job->jf, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     auto d64 = [&](size_t at) { return reinterpret_cast<const uint64_t*>(dimg + at); };
     auto d32 = [&](size_t at) { return reinterpret_cast<const uint32_t*>(dimg + at); };
     int rc = BBS_OK;
     const size_t Lw = (size_t)std::max(L, 1), nn = std::max<size_t>(n, 1);
     PvArgs<C>& a = job->a;
     a.n = n; a.L = L; a.Rmax = (int)Lw; a.cc = ctx->d_consts.template as<CtxConsts<C>>();
-    // wire form: every point has passed the subgroup check of the decoder, the GLV split needs no vouching
-    a.glv = (C::K::HAS_GLV && (C::K::GLV_ALWAYS || ctx->points_in_subgroup || wire)) ? 1 : 0;
+    a.glv = glv_flag<C>(ctx, wire);
     a.nvar = job->latency_form ? PV_NVAR_SPLIT : PV_NVAR;
     uint32_t* pts = job->template scratch<uint32_t>((size_t)3 * 2 * NC * nn, rc);
     uint32_t* sc = job->template scratch<uint32_t>((size_t)4 * 8 * nn, rc);
@@ -120,8 +105,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     int8_t* pair_ok = job->template scratch<int8_t>(nn, rc);
     if (rc) return rc;
     job->zero_on_reset.push_back({pair_ok, nn});          // a pairing lane that never ran reads as "product != 1"
-    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
+    if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
     if (!wire) {
         PvIngestArgs<C>& ia = job->ingest;
         ia.n = n; ia.L = L; ia.dst_too_long = ctx->dst_too_long ? 1 : 0;
@@ -132,8 +116,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         ia.pts = pts; ia.sc = sc; ia.slots = slots; ia.dmask = dmask; ia.didx = didx_s; ia.rcount = rcount;
         ia.hdr_off = offs; ia.hdr_len = offs + nn; ia.ph_off = offs + 2 * nn; ia.ph_len = offs + 3 * nn;
         ia.status0 = job->d_status0.template as<int8_t>();
-        if (mixed_ingest && rt::launch<PvIngestMixed<C>>(job->stream(), MixedIngestArgs<PvIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-        if (!mixed_ingest && rt::launch<PvIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+        if ((rc = launch_ingest<PvIngest<C>, PvIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     } else {
         PvOctArgs<C>& oa = job->oct;
         oa.n = n; oa.L = L; oa.dst_too_long = ctx->dst_too_long ? 1 : 0;
@@ -152,11 +135,10 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         if (rc) return rc;
         oa.status0 = job->d_status0.template as<int8_t>();
         if (rt::launch<PvOctDecode<C>>(job->stream(), oa, 3 * n)) return BBS_E_HIP;
-        if (mixed_ingest && rt::launch<PvOctIngestMixed<C>>(job->stream(), MixedIngestArgs<PvOctArgs<C>>{oa, job->mx.len}, n)) return BBS_E_HIP;
-        if (!mixed_ingest && rt::launch<PvOctIngest<C>>(job->stream(), oa, n)) return BBS_E_HIP;
+        if ((rc = launch_ingest<PvOctIngest<C>, PvOctIngestMixed<C>>(job.get(), job->jf, oa, n))) return rc;
     }
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, job->d_status0.template as<int8_t>()))) return rc;
+        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, job->d_status0.template as<int8_t>()))) return rc;
     }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.pts; pa.pb = a.pts + (size_t)2 * NC * n; pa.negate_b = 1;
@@ -179,20 +161,12 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     // compute unit together) on the first side stream from the start; chains that start at the same moment spread a long
     // wavefront over every compute unit first and the bucket workgroups then wait for whole compute units (measured: that
     // kernel 1.3 -> 4.1 ms, the batch 4.8 -> 7.6 ms, profiles/r05_g_single_batch_forms.log).  0.14 ms later they come second.
-    auto msm_chain = [j, mixed, keyed_mixed](int layout, bool chains_behind_scalars = false) {
+    auto msm_chain = [j](int layout, bool chains_behind_scalars = false) {
         auto chains2 = [j]() { j->stages.push_back({"pv_chains", [j]() { return rt::launch<PvChains<C>>(j->stream_aux(2), j->a, j->n * PvChains<C>::units(j->a)); }, 2, 0}); };
         if (layout == 3) j->stages.push_back({"pv_t1_chain", [j]() { return rt::launch<PvT1Chain<C>>(j->stream_aux(2), j->a, j->n); }, 2, 0});
         if (layout == 2 && !chains_behind_scalars) chains2();
         if (layout == 3) j->stages.push_back({"pv_var_mul", [j]() { return rt::launch<PvVarMul<C>>(j->stream(), j->a, j->n * (size_t)(j->a.nvar - PvVarMul<C>::first_part(j->a))); }});
-        if constexpr (KEYED) {
-            if (keyed_mixed)
-                j->stages.push_back({"pv_scalars_keyed_mixed", [j]() { return rt::launch<PvScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, PvArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
-            else
-                j->stages.push_back({"pv_scalars_keyed", [j]() { return rt::launch<PvScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, PvArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
-        } else if (mixed)
-            j->stages.push_back({"pv_scalars_mixed", [j]() { return rt::launch<PvScalarsMixed<C>>(j->stream(), MixedScalarArgs<PvArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
-        else
-            j->stages.push_back({"pv_scalars", [j]() { return rt::launch<PvScalars<C>>(j->stream(), j->a, j->n); }});
+        add_scalar_stage<C, KEYED, PvScalars<C>, PvScalarsIn>(j, PV_SCALARS);
         if (layout == 2 && chains_behind_scalars) chains2();
         if (j->a.fixwk.pts0) j->stages.push_back({"pv_fixed_tree", [j]() { return rt::launch<PvFixedTree<C>>(j->stream(), j->a, j->n); }});
         else j->stages.push_back({"pv_fixed_chunks", [j]() { return rt::launch<PvFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});
@@ -207,7 +181,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         // follows the MSM chain (verify: 7.4 -> 6.9 ms), but beside the 768 wavefronts of this operation's latency-form MSM
         // chain it oversubscribes the 1024 SIMDs and the queued wavefronts cost more than the split saves (measured
         // 5.1 ms split vs 4.4 ms fused, profiles/r03_j_latency_form_split.log)
-        if constexpr (KEYED) add_keyed_pairing_stages<C>(j, &j->kj, &j->pa, 1);
+        if constexpr (KEYED) add_keyed_pairing_stages<C>(j, &j->jf, &j->pa, 1);
         else add_pairing_stages<C>(j, &j->pa, 1, "pair_miller", "pair_final_exp", "pairing_6lane", PairSplit::Never);
         msm_chain(pv_msm_layout(false, job->latency_form));
         j->stages.push_back({"pv_challenge", [j]() { return rt::launch<PvChallenge<C>>(j->stream(), j->a, j->n); }, 0, join_chains});

@@ -10,9 +10,7 @@ struct SgJob : JobBase<C> {
     SgArgs<C> a{};
     VfIngestArgs<C> ingest{};
     MsgHashArgs mh{};                 // raw-message form only
-    KeyedJob<C> kj{};                 // keyed form only (its pairing order stays empty: sign has no pairing)
-    const uint32_t* sks = nullptr;    // keyed form only: the rows of the signing set the job holds (JobBase::sign_key_set)
-    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths_gen, bbs_ctx_set_keyed_mixed_lengths)
+    JobForm<C> jf{};                  // the job's form (job_form.hpp); keyed: src.sks = the rows of the signing set the job holds
     // the records come off the device in the caller's layout (stage SgEmit): delivery is one copy
     size_t rec_bytes() const { return a.oct_form ? (size_t)(4 * C::FpP::NC + 32) : (size_t)(8 * C::FpP::NC + 32); }
     int set_octet_form() override { a.oct_form = 1; return BBS_OK; }
@@ -40,48 +38,41 @@ struct SgJob : JobBase<C> {
     }
 };
 
+constexpr const char* SG_SCALARS[4] = {"sg_scalars", "sg_scalars_mixed", "sg_scalars_keyed", "sg_scalars_keyed_mixed"};
+
 // KEYED (bbs_*sign*_keyed_*, instantiated in tu_sgk_*.hip): item i is signed under key key_index[i] of the context's key set,
-// with the secret half its signing set holds (keyed.hpp SgScalarsKeyed).  The key enters through the domain, the hash that gives
+// with the secret half its signing set holds (stages_sg.hpp SgScalarsIn).  The key enters through the domain, the hash that gives
 // e and 1 / (sk + e) (sign.rs:63-132): the scalar stage reads the key's midstate, or the prefix of (key, length), and the key's
 // secret row; every other stage is the single-key job's.  The context's single key is neither needed nor looked at (a.sk of a
 // keyed job stays zero).
 template <class C, bool KEYED>
 int sg_upload(Ctx<C>* ctx, size_t n, const SgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
-    // keyed jobs of mixed counts: the switch is read ONCE per upload, as in pg_upload
-    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
-    if constexpr (KEYED) {
-        // (keyed jobs of mixed counts treat a missing signing set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
-        if (!ctx->gens_set || (!ctx->sign_keys && !keyed_mixed)) return BBS_E_STATE;
-        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
-        if (ctx->mixed_lengths_gen && !keyed_mixed) return BBS_E_STATE;
-        if (n && !in.key_index) return BBS_E_ARG;
-    } else {
-        if (!ctx->gens_set || !ctx->sk_set) return BBS_E_STATE;
-    }
+    Form form;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Sign, n, in.key_index, form)) return rcf;
     if (!out || (n && !in.msg_off)) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
     auto job = std::unique_ptr<SgJob<C>>(new SgJob<C>(ctx));
     job->n = n;
+    job->jf.form = form;
     // staging image + device-side checks (stage VfIngest without a signature record: sign.rs:77-79's length check,
     // range checks of the messages, SoA transposition)
     const bool raw = in.msg_byte_off != nullptr;
     RaggedIn ms{in.msg_off, in.messages, 32}, hb{in.hdr_off, in.headers, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !hb.measure(n) || hb.total > 0xF0000000ull) return BBS_E_ARG;
-    const size_t nm = raw ? (size_t)ms.total : 0;
-    // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
-    if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
+    RaggedIn mb{};
+    size_t nm;
+    if (!raw_message_section(ms, in.msg_byte_off, in.msg_bytes, mb, nm)) return BBS_E_ARG;
     std::vector<uint32_t> kwords;     // keyed: the key indexes, in the staging image
     size_t kwords_at = 0;
     if constexpr (KEYED) {
-        if (int rck = keyed_sign_indexes<C>(job.get(), ctx, n, in.key_index, job->kj, kwords, &job->sks)) return rck;
+        if (int rck = keyed_sign_indexes<C>(job.get(), ctx, n, in.key_index, job->jf, kwords)) return rck;
     }
     if (int rc0 = stage_image(job.get(), n, nullptr, 0, {&ms, &hb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
-    if constexpr (KEYED) job->kj.kidx = reinterpret_cast<const uint32_t*>(dimg + kwords_at);
+    if constexpr (KEYED) keyed_bind<C>(job->jf, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     int rc = BBS_OK;
     const size_t Lw = (size_t)std::max(L, 1), nn = std::max<size_t>(n, 1);
     SgArgs<C>& a = job->a;
@@ -112,26 +103,13 @@ int sg_upload(Ctx<C>* ctx, size_t n, const SgIn& in, bbs_job** out) {
     }
     ia.sig_a = nullptr; ia.sig_e = nullptr; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
-    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
-    const bool mixed = !KEYED && ctx->mixed_lengths_gen;
-    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED bodies serve both
-    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (mixed_ingest && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-    if (!mixed_ingest && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if ((rc = launch_ingest<VfIngest<C>, VfIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if constexpr (KEYED) {
-        if (rt::launch<SignKeyGate>(job->stream(), KeyGateArgs{n, job->kj.kidx, ia.status0}, n)) return BBS_E_HIP;
+        if (rt::launch<SignKeyGate>(job->stream(), KeyGateArgs{n, job->jf.src.kidx, ia.status0}, n)) return BBS_E_HIP;
     }
     SgJob<C>* j = job.get();
-    if constexpr (KEYED) {
-        if (keyed_mixed)
-            j->stages.push_back({"sg_scalars_keyed_mixed", [j]() { return rt::launch<SgScalarsKeyedMixed<C>>(j->stream(), KeyedMixedSignArgs<C>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len, j->sks}, j->n); }});
-        else
-            j->stages.push_back({"sg_scalars_keyed", [j]() { return rt::launch<SgScalarsKeyed<C>>(j->stream(), KeyedSignArgs<C>{j->a, j->kj.keys, j->kj.kidx, j->sks}, j->n); }});
-    } else if (mixed)
-        j->stages.push_back({"sg_scalars_mixed", [j]() { return rt::launch<SgScalarsMixed<C>>(j->stream(), MixedScalarArgs<SgArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
-    else
-        j->stages.push_back({"sg_scalars", [j]() { return rt::launch<SgScalars<C>>(j->stream(), j->a, j->n); }});
+    add_scalar_stage<C, KEYED, SgScalars<C>, SgScalarsIn>(j, SG_SCALARS);
     j->stages.push_back({"sg_msm_parts", [j]() { return rt::launch<SgMsmPart<C>>(j->stream(), j->a, j->n * NFIX); }});
     j->stages.push_back({"sg_combine", [j]() { return rt::launch<SgCombine<C>>(j->stream(), j->a, j->n); }});
     j->stages.push_back({"sg_emit", [j]() { return rt::launch<SgEmit<C>>(j->stream(), j->a, j->n); }});

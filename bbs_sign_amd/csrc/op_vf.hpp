@@ -13,9 +13,9 @@ struct VfJob : JobBase<C> {
     VfOctArgs<C> oct{};               // wire form only
     MsgHashArgs mh{};                 // raw-message form only
     BvState<C> bv{};                  // batch verification only
-    KeyedJob<C> kj{};                 // keyed form only
-    MixedJob mx{};                    // mixed-length forms only (bbs_ctx_set_mixed_lengths, bbs_ctx_set_keyed_mixed_lengths)
+    PairedJobForm<C> jf{};            // the job's form (job_form.hpp)
 };
+constexpr const char* VF_SCALARS[4] = {"vf_scalars", "vf_scalars_mixed", "vf_scalars_keyed", "vf_scalars_keyed_mixed"};
 
 // KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
 // (keyed.hpp); the fused pairing kernel in both job forms, no batch verification
@@ -24,18 +24,8 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
-    // keyed jobs of mixed counts: item i under its own key AND with its own count.  The switch is read ONCE per upload: the
-    // checks, the stages and the data of the job all go by this one look, whatever a setter does meanwhile
-    const bool keyed_mixed = KEYED && ctx->keyed_mixed_lengths;
-    if constexpr (KEYED) {
-        // (keyed jobs of mixed counts treat a missing key set as the empty set: every item is BBS_ST_UNKNOWN_KEY)
-        if (!ctx->gens_set || (!ctx->keys && !keyed_mixed)) return BBS_E_STATE;
-        // (the single-key switch alone builds no prefix per (key, length): that is bbs_ctx_set_keyed_mixed_lengths, keyed.hpp)
-        if (ctx->mixed_lengths && !keyed_mixed) return BBS_E_STATE;
-        if (n && !in.key_index) return BBS_E_ARG;
-    } else {
-        if (!ctx->gens_set || !ctx->pk_set) return BBS_E_STATE;
-    }
+    Form form;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form)) return rcf;
     if (!out || (n && ((!in.signatures && !in.signature_octets) || !in.msg_off))) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
@@ -44,28 +34,27 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
     auto job = std::unique_ptr<VfJob<C>>(new VfJob<C>(ctx));
     job->n = n;
+    job->jf.form = form;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->kj, kwords);
+    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
     // the batch as one staging image, one asynchronous copy; checks, range checks and the SoA transposition on the
     // device (stage VfIngest), as for proof_verify
     const bool raw = in.msg_byte_off != nullptr;
     RaggedIn ms{in.msg_off, in.messages, 32}, hb{in.hdr_off, in.headers, 1};
     ms.offsets_only = raw;
     if (!ms.measure(n) || !hb.measure(n) || hb.total > 0xF0000000ull) return BBS_E_ARG;
-    const size_t nm = raw ? (size_t)ms.total : 0;
-    // (message t of the batch is entry msg_off[0] + t of msg_byte_off: item offsets need not start at zero)
-    RaggedIn mb{raw ? (nm ? in.msg_byte_off + in.msg_off[0] : zero_off1()) : nullptr, in.msg_bytes, 1};   // nm == 0: msg_byte_off is never indexed
-    if (raw && (!mb.measure(nm) || mb.total > 0xF0000000ull)) return BBS_E_ARG;
+    RaggedIn mb{};
+    size_t nm;
+    if (!raw_message_section(ms, in.msg_byte_off, in.msg_bytes, mb, nm)) return BBS_E_ARG;
     if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &hb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
-    if constexpr (KEYED) keyed_bind<C>(job->kj, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
+    if constexpr (KEYED) keyed_bind<C>(job->jf, n, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     int rc = BBS_OK;
     const size_t Lw = (size_t)std::max(L, 1), nn = std::max<size_t>(n, 1);
     VfArgs<C>& a = job->a;
     a.n = n; a.L = L; a.cc = ctx->d_consts.template as<CtxConsts<C>>();
-    // wire form: the decoder has checked that A is in G1, so the GLV split is sound without the caller's word
-    a.glv = (C::K::HAS_GLV && (C::K::GLV_ALWAYS || ctx->points_in_subgroup || wire)) ? 1 : 0;
+    a.glv = glv_flag<C>(ctx, wire);
     uint32_t* sig_a = job->template scratch<uint32_t>((size_t)2 * NC * nn, rc);
     uint32_t* sig_e = job->template scratch<uint32_t>((size_t)8 * nn, rc);
     uint32_t* smsgs = job->template scratch<uint32_t>(Lw * 8 * nn, rc);
@@ -101,15 +90,10 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     }
     ia.sig_a = sig_a; ia.sig_e = sig_e; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
-    // mixed lengths: the job's stages are chosen here, once; a later change of the switch does not reach it
-    const bool mixed = !KEYED && ctx->mixed_lengths;
-    const bool mixed_ingest = mixed || keyed_mixed;                   // the MIXED ingest body serves both
-    if (mixed && (rc = mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (keyed_mixed && (rc = keyed_mixed_bind<C>(job.get(), ctx, nn, job->mx))) return rc;
-    if (mixed_ingest && rt::launch<VfIngestMixed<C>>(job->stream(), MixedIngestArgs<VfIngestArgs<C>>{ia, job->mx.len}, n)) return BBS_E_HIP;
-    if (!mixed_ingest && rt::launch<VfIngest<C>>(job->stream(), ia, n)) return BBS_E_HIP;
+    if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if ((rc = launch_ingest<VfIngest<C>, VfIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->kj.kidx, ia.status0))) return rc;
+        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, ia.status0))) return rc;
     }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.aff; pa.pb = a.aff + (size_t)2 * N * n; pa.negate_b = 0;
@@ -122,19 +106,11 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     // by the dozen and must own ONE hardware queue each (32 in flight: 4.2 M/s on one stream, 3.1 M/s on two).
     const int side = (!KEYED && ctx->batch_verify && !job->latency_form) ? 0 : 1;
     j->stages.push_back({"vf_var_mul", [j, side]() { return rt::launch<VfVarMul<C>>(side ? j->stream_aux(1) : j->stream(), j->a, j->n); }, side, 0});
-    if constexpr (KEYED) {
-        if (keyed_mixed)
-            j->stages.push_back({"vf_scalars_keyed_mixed", [j]() { return rt::launch<VfScalarsKeyedMixed<C>>(j->stream(), KeyedMixedScalarArgs<C, VfArgs<C>>{j->a, j->mx.pref, j->mx.stride, j->kj.kidx, j->mx.len}, j->n); }});
-        else
-            j->stages.push_back({"vf_scalars_keyed", [j]() { return rt::launch<VfScalarsKeyed<C>>(j->stream(), KeyedScalarArgs<C, VfArgs<C>>{j->a, j->kj.keys, j->kj.kidx}, j->n); }});
-    } else if (mixed)
-        j->stages.push_back({"vf_scalars_mixed", [j]() { return rt::launch<VfScalarsMixed<C>>(j->stream(), MixedScalarArgs<VfArgs<C>>{j->a, j->mx.pref, j->mx.len}, j->n); }});
-    else
-        j->stages.push_back({"vf_scalars", [j]() { return rt::launch<VfScalars<C>>(j->stream(), j->a, j->n); }});
+    add_scalar_stage<C, KEYED, VfScalars<C>, VfScalarsIn>(j, VF_SCALARS);
     j->stages.push_back({"vf_fixed_chunks", [j]() { return rt::launch<VfFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});
     j->stages.push_back({"vf_combine", [j]() { return rt::launch<VfCombine<C>>(j->stream(), j->a, j->n); }, 0, 1});
     if constexpr (KEYED) {
-        add_keyed_pairing_stages<C>(j, &j->kj, &j->pa, 0);
+        add_keyed_pairing_stages<C>(j, &j->jf, &j->pa, 0);
     } else if (!ctx->batch_verify) {
         add_pairing_stages<C>(j, &j->pa, 0, "pair_miller", "pair_final_exp", "pairing_6lane");
     } else {

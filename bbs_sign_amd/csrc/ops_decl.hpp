@@ -1,5 +1,5 @@
 #pragma once
-#include "runtime.hpp"
+#include "job_form.hpp"
 // ---- inputs of the four upload templates: one field per pointer of the C ABI, named as in include/bbs_sign_amd.h.  A field
 // that is left null selects the form (core / octets / wire / keyed); the upload functions deduce it from that alone.
 struct PvIn {

@@ -1283,6 +1283,23 @@ inline int stage_image(J* job, size_t n, const uint8_t* records, size_t rec_byte
     return rt::h2d_async(job->d_raw.p, img, cur, job->stream()) ? BBS_E_HIP : BBS_OK;
 }
 
+// The raw-message section `mb` of an upload (msg_byte_off != nullptr: the messages arrive as raw bytes) and nm, the messages of
+// the whole batch (0: scalars).  `items` is the measured per-item section of message counts: message t of the batch is entry
+// items.off[0] + t of msg_byte_off (item offsets need not start at zero; nm == 0: msg_byte_off is never indexed).  The section
+// is ragged over MESSAGES, not items: stage_image places and fills it with nm as its count.  false: BBS_E_ARG.
+inline bool raw_message_section(const RaggedIn& items, const uint64_t* msg_byte_off, const uint8_t* msg_bytes, RaggedIn& mb, size_t& nm) {
+    const bool raw = msg_byte_off != nullptr;
+    nm = raw ? (size_t)items.total : 0;
+    mb = RaggedIn{raw ? (nm ? msg_byte_off + items.off[0] : zero_off1()) : nullptr, msg_bytes, 1};
+    return !raw || (mb.measure(nm) && mb.total <= 0xF0000000ull);
+}
+// the GLV split of a variable-base scalar is sound for points of the subgroup: always (BN254), on the caller's word, or in the
+// wire forms, where the decoder has checked every point
+template <class C>
+inline int glv_flag(const Ctx<C>* ctx, bool wire) {
+    return (C::K::HAS_GLV && (C::K::GLV_ALWAYS || ctx->points_in_subgroup || wire)) ? 1 : 0;
+}
+
 // msg_to_scalars on the device (codec_dev.hpp MsgHash): the nm raw messages of a batch, placed in the staging image as
 // section `mb`, become nm canonical scalars [message][8 words] -- the array the ingest stages read messages from.
 // dst_too_long = 1 (and no launch): api_id || "MAP_MSG_TO_SCALAR_AS_HASH_" exceeds 255 bytes, the reference panics.
@@ -1434,159 +1451,4 @@ void add_batch_decision(J* j, BvState<C>* bv, PairArgs<C>* fallback, int joins_a
     // no kernel of its own: the per-item kernel's lanes read the 16 verdicts first -- all passed: write Ok(true) and leave
     fallback->batch_ok = bv->batch_ok; fallback->n_checks = bv->n_checks;
     add_pairing_stages<C>(j, fallback, 0, "fallback_pair_miller", "fallback_pair_final_exp", "fallback_pairing_6lane", PairSplit::ByJobForm, joins_aux);
-}
-
-// =============================================================================================
-// keyed jobs (keyed.hpp): per-item key indexes and the pairing order, built on the host at upload
-// =============================================================================================
-template <class C>
-struct KeyedJob {
-    const KeyEntry<C>* keys = nullptr;
-    const uint32_t* kidx = nullptr;          // [n] key of item i, KEY_NONE: unknown / refused (decided by KeyGate)
-    PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
-    bool unit = false;                       // line form of the key set the job holds (KeySet::unit)
-};
-// The host half, before the staging image is built: item i -> its key (KEY_NONE: unknown / refused) and the pairing order.
-// Items are sorted by key, stably (a counting sort); key k with c items fills floor(c / 10) key-uniform wavefronts, its c mod
-// 10 remaining items go to the mixed wavefronts behind them.  `words` = [kidx n][uniform slots][mixed slots][wave keys]; it
-// travels in the job's staging image (the one asynchronous copy), keyed_bind points the job at it.
-template <class C, class J>
-void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words) {
-    constexpr uint32_t W = (uint32_t)KEY_SLOTS_PER_WAVE;
-    const auto ks = ctx->keys;
-    j->key_set = ks;
-    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
-    std::vector<uint32_t> cnt(nk, 0);
-    words.assign(3 * n + n / W + 1, 0);
-    uint32_t* kid = words.data();
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = key_index[i];
-        const bool ok = k < nk && ks->status[k] == 1;
-        kid[i] = ok ? k : KEY_NONE;
-        if (ok) cnt[k]++;
-    }
-    std::vector<uint32_t> ufirst(nk), mfirst(nk), seen(nk, 0);
-    size_t nu = 0, nm = 0;
-    for (size_t k = 0; k < nk; k++) {
-        ufirst[k] = (uint32_t)nu; nu += cnt[k] / W * W;
-        mfirst[k] = (uint32_t)nm; nm += cnt[k] % W;
-    }
-    uint32_t* uslot = words.data() + n;
-    uint32_t* mslot = uslot + nu;
-    uint32_t* wkey = mslot + nm;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = kid[i];
-        if (k == KEY_NONE) continue;
-        const uint32_t full = cnt[k] / W * W, s = seen[k]++;
-        if (s < full) uslot[ufirst[k] + s] = (uint32_t)i;
-        else mslot[mfirst[k] + s - full] = (uint32_t)i;
-    }
-    for (size_t k = 0, w = 0; k < nk; k++)
-        for (uint32_t q = 0; q < cnt[k] / W; q++) wkey[w++] = (uint32_t)k;
-    words.resize(n + nu + nm + nu / W);
-    kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
-    kj.pair.keys = kj.keys; kj.pair.n_uni = nu; kj.pair.n_slots = nu + nm;
-    kj.unit = ks ? ks->unit : ctx->lines_unit();
-}
-// the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
-template <class C, class J>
-void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words) {
-    const auto ks = ctx->keys;
-    j->key_set = ks;
-    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
-    words.resize(n);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = key_index[i];
-        words[i] = (k < nk && ks->status[k] == 1) ? k : KEY_NONE;
-    }
-    kj.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
-    kj.pair.keys = kj.keys; kj.pair.n_uni = 0; kj.pair.n_slots = 0;
-}
-// keyed sign: the same look at the key set AND at the signing set (Ctx::SignSet) -- KEY_NONE as above, KEY_NO_SECRET for an
-// accepted key without a secret half; only an index that names a secret row is passed on.  BBS_E_STATE (fail closed) where the
-// two sets do not belong together: a set that was replaced between the two looks.  *sks = the rows on the device (null: none).
-template <class C, class J>
-int keyed_sign_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, KeyedJob<C>& kj, std::vector<uint32_t>& words, const uint32_t** sks) {
-    const auto ss = ctx->sign_keys;
-    keyed_indexes<C>(j, ctx, n, key_index, kj, words);
-    const auto ks = std::static_pointer_cast<const typename Ctx<C>::KeySet>(j->key_set);
-    if (ss && (!ks || ss->lineage != ks->lineage || ss->n > ks->n)) return BBS_E_STATE;
-    j->sign_key_set = ss;
-    // (no signing set: only where bbs_ctx_set_keyed_mixed_lengths is on -- the empty set, every index is unknown)
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = words[i];
-        if (!ss) words[i] = KEY_NONE;
-        else if (k != KEY_NONE && !(k < ss->n && ss->has[k])) words[i] = KEY_NO_SECRET;
-    }
-    *sks = ss ? ss->d.template as<uint32_t>() : nullptr;
-    return BBS_OK;
-}
-// the device half: d = the words' place in the device copy of the staging image
-template <class C>
-void keyed_bind(KeyedJob<C>& kj, size_t n, const uint32_t* d) {
-    kj.kidx = d;
-    kj.pair.kidx = d; kj.pair.slot_item = d + n; kj.pair.wave_key = d + n + kj.pair.n_slots;
-}
-// behind the ingest stage: items with an unknown key are decided (BBS_ST_UNKNOWN_KEY)
-template <class J>
-int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
-    return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
-}
-// the pairing step of a keyed job on the main (aux = 0) or second stream, as add_pairing_stages: the fused kernel in both job
-// forms.  kj->pair.p is copied from *pa when the stage is launched.
-template <class C, class J>
-void add_keyed_pairing_stages(J* j, KeyedJob<C>* kj, const PairArgs<C>* pa, int aux) {
-#ifdef BBS_HOST_TWIN
-    j->stages.push_back({"pair_miller_keyed", [j, kj, pa, aux]() {
-        kj->pair.p = *pa;
-        return rt::launch<PairMillerKeyed<C>>(aux ? j->stream_aux() : j->stream(), kj->pair, kj->pair.n_slots * 2);
-    }, aux, 0});
-    j->stages.push_back({"pair_final_exp", [j, pa, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pa, pa->n); }, aux, 0});
-#else
-    j->stages.push_back({"pairing_6lane_keyed", [j, kj, pa, aux]() {
-        kj->pair.p = *pa;
-        // the key set the job holds and BP2's table on the device must agree (they do unless the form was switched under the job)
-        if (kj->unit != j->ctx->dev_lines_unit) return -1;
-        rt::Stream& st = aux ? j->stream_aux() : j->stream();
-        const size_t nt = ((kj->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
-        return kj->unit ? rt::launch<PairDistKeyed<C, true>>(st, kj->pair, nt) : rt::launch<PairDistKeyed<C, false>>(st, kj->pair, nt);
-    }, aux, 0});
-#endif
-}
-
-// =============================================================================================
-// mixed-length jobs (bbs_ctx_set_mixed_lengths): the per-item length array and the context's prefixes per length
-// =============================================================================================
-struct MixedJob {
-    const HashCtx* pref = nullptr;           // [L + 1] domain prefix of length l (the context's LenSet, held by the job)
-    uint32_t* len = nullptr;                 // [n] written by the ingest stage
-    uint32_t stride = 0;                     // keyed jobs of mixed counts only: pref is [n_keys][stride], stride = L + 1
-};
-template <class J>
-int mixed_len_scratch(J* j, size_t nn, MixedJob& mx) {
-    int rc = BBS_OK;
-    mx.len = j->template scratch<uint32_t>(nn, rc);
-    return rc;
-}
-template <class C, class J>
-int mixed_bind(J* j, Ctx<C>* ctx, size_t nn, MixedJob& mx) {
-    std::shared_ptr<const typename Ctx<C>::LenSet> ls;
-    if (const int rc = ctx->sync_lengths(ls)) return rc;
-    j->len_set = ls;
-    mx.pref = ls->d.template as<HashCtx>();
-    return mixed_len_scratch(j, nn, mx);
-}
-// keyed jobs of mixed counts (bbs_ctx_set_keyed_mixed_lengths): the prefixes per (key, length) instead of the context's per
-// length; they must be the rows of the key set keyed_order bound the job to (fail closed otherwise: a set that was replaced
-// between the two looks)
-template <class C, class J>
-int keyed_mixed_bind(J* j, Ctx<C>* ctx, size_t nn, MixedJob& mx) {
-    const auto kl = ctx->key_lens;
-    mx.stride = (uint32_t)ctx->L + 1;
-    if (j->key_set) {         // (an empty set has no rows and no item that reads one: KeyGate decides every item)
-        if (!kl || kl->of.get() != j->key_set.get() || kl->stride != (size_t)mx.stride) return BBS_E_STATE;
-        j->key_len_set = kl;
-        mx.pref = kl->d.template as<HashCtx>();
-    }
-    return mixed_len_scratch(j, nn, mx);
 }

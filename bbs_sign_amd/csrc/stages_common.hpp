@@ -146,14 +146,46 @@ BBS_HD void g1j_store(uint32_t* base, size_t n, size_t i, const G1Jac<C>& p) {
     soa_st<N>(base + (size_t)2 * N * n, n, i, p.z.v);
 }
 
-// ---- mixed message counts (bbs_ctx_set_mixed_lengths) -----------------------------------------
-// The stages of a mixed-length job take the arguments of their fixed-length neighbours plus the job's per-item length array
-// (written by the ingest stage: the item's count l <= L, 0 for an item that is decided before or by the length check) and,
-// for the scalar stage, the context's domain prefixes per length (runtime.hpp LenSet).
+// ---- job forms ----------------------------------------------------------------------------------
+// The scalar stage is the only stage that knows a job's form: where item i's domain prefix comes from and how many messages
+// it has.  Single: the context's prefix, L.  Mixed (bbs_ctx_set_mixed_lengths, .._gen): item i has its own count l = len[i]
+// <= L (written by the MIXED ingest bodies; 0 for an item decided before or by the length check) and starts from the prefix of
+// that length, pref[l] (runtime.hpp LenSet).  Keyed (bbs_*_keyed_*): the midstate of the item's key-set entry, L.  KeyedMixed
+// (bbs_ctx_set_keyed_mixed_lengths): the prefix of THAT key and THAT length, pref[kidx * stride + l] (runtime.hpp KeyLenSet,
+// stride = L + 1).  DESIGN.md 8 has the table; job_form.hpp decides and binds the form on the host.
+enum class Form { Single, Mixed, Keyed, KeyedMixed };
+constexpr bool form_mixed(Form f) { return f == Form::Mixed || f == Form::KeyedMixed; }
+constexpr bool form_keyed(Form f) { return f == Form::Keyed || f == Form::KeyedMixed; }
+// what a key set holds per key (keyed.hpp): the only two things of a verification that depend on the key
+template <class C>
+struct KeyEntry {
+    LineTable<C> tab;            // lines of W = this key
+    HashCtx hash;                // domain prefix midstate with this key (dst_h2s as the context's)
+};
+template <class C>
+struct DomainSrc {
+    const HashCtx* pref; uint32_t stride;                  // Mixed: [L + 1]; KeyedMixed: [n_keys][stride]
+    const KeyEntry<C>* keys; const uint32_t* kidx;         // Keyed, KeyedMixed: [n] key of item i
+    const uint32_t* len;                                   // Mixed, KeyedMixed: [n]
+    const uint32_t* sks;                                   // keyed sign only: rows of the signing set
+};
+// the arguments of a scalar stage in a derived form: its fixed-length neighbour's plus the source of the domains
+template <class C, class A>
+struct FormArgs { A a; DomainSrc<C> d; };
 template <class A>
 struct MixedIngestArgs { A a; uint32_t* len; };
-template <class A>
-struct MixedScalarArgs { A a; const HashCtx* pref; const uint32_t* len; };   // pref: [L + 1]
+// Item i's prefix and (l) its count.  Only a pending item is looked at: KEY_NONE (decided by KeyGate) and l > L (decided at
+// ingest, len = 0) never index anything.  In every derived form the index diverges per lane, so the 368 bytes of the HashCtx
+// are read with vector loads through a per-lane pointer: the struct is returned and passed on BY REFERENCE, never copied into
+// a local (368 B of scratch per lane).
+template <Form F, class C>
+BBS_HD const HashCtx& form_domain(const CtxConsts<C>* cc, const DomainSrc<C>& d, size_t i, int L, int& l) {
+    if constexpr (form_mixed(F)) l = (int)d.len[i]; else l = L;
+    if constexpr (F == Form::Single) return cc->hash;
+    else if constexpr (F == Form::Mixed) return d.pref[l];
+    else if constexpr (F == Form::Keyed) return d.keys[d.kidx[i]].hash;
+    else return d.pref[(size_t)d.kidx[i] * d.stride + (size_t)l];
+}
 // the scalars of the bases H_{l+1} .. H_L of an item with l messages: written as zero, never assumed
 BBS_HD void mixed_zero_scalars(uint32_t* fscal, size_t n, size_t i, int l, int L) {
     const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};

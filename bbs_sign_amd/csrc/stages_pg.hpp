@@ -240,18 +240,21 @@ struct PgScalars {
         pg_scalars_item<C>(a, i, a.cc->hash, a.L);
     }
 };
-// Mixed lengths (bbs_ctx_set_mixed_lengths_gen): as PvScalarsMixed (stages_pv.hpp) -- the domain from the prefix of the item's
-// own length, B's scalars and T2's for its l messages, and zeros WRITTEN for the bases H_{l+1} .. H_L in BOTH arrays (the
-// buffers come from the pools and hold what the last job left), so PgBPart runs unchanged.  The HashCtx is read through the
-// per-lane pointer and passed on by reference, never copied into a local.
-template <class C>
-struct PgScalarsMixed {
-    static __host__ __device__ void run(const MixedScalarArgs<PgArgs<C>>& m, size_t i) {
-        if (m.a.status[i] != ST_PENDING) return;
-        const int l = (int)m.len[i];
-        pg_scalars_item<C>(m.a, i, m.pref[l], l);
-        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
-        mixed_zero_scalars(m.a.fscal2, m.a.n, i, l, m.a.L);
+// The derived forms, as PvScalarsIn (stages_pv.hpp).  A key enters a proof in calculate_domain alone (no pairing, no W), so
+// this stage is all a keyed producing job has of its own.  Mixed forms: B's scalars and T2's for the item's l messages, and
+// zeros WRITTEN for the bases H_{l+1} .. H_L in BOTH arrays (B's sum and T2's run over the same bases; the buffers come from
+// the pools and hold what the last job left), so PgBPart runs unchanged.
+template <class C, Form F>
+struct PgScalarsIn {
+    static __host__ __device__ void run(const FormArgs<C, PgArgs<C>>& f, size_t i) {
+        if (f.a.status[i] != ST_PENDING) return;
+        int l;
+        const HashCtx& h = form_domain<F, C>(f.a.cc, f.d, i, f.a.L, l);
+        pg_scalars_item<C>(f.a, i, h, l);
+        if constexpr (form_mixed(F)) {
+            mixed_zero_scalars(f.a.fscal, f.a.n, i, l, f.a.L);
+            mixed_zero_scalars(f.a.fscal2, f.a.n, i, l, f.a.L);
+        }
     }
 };
 

@@ -152,7 +152,7 @@ struct PvIngestMixed {
 };
 
 // stage 1 (lane per item): domain, fixed-base scalars.  h: the domain prefix of the item's key (the context's, or its key-set
-// entry in a keyed job: keyed.hpp PvScalarsKeyed); l: the item's message count (a.L unless the job is a mixed-length one)
+// entry in a keyed job: stages_common.hpp form_domain); l: the item's message count (a.L unless the job is a mixed-length one)
 template <class C>
 BBS_HD void pv_scalars_item(const PvArgs<C>& a, size_t i, const HashCtx& h, int l) {
     using R = typename C::FrP;
@@ -180,18 +180,18 @@ struct PvScalars {
         pv_scalars_item<C>(a, i, a.cc->hash, a.L);
     }
 };
-// Mixed lengths (bbs_ctx_set_mixed_lengths): item i has its own count l = len[i] <= L.  Its domain starts from the prefix of
-// ITS length (pref[l]: the context keeps one midstate per length, runtime.hpp LenSet), its scalars fill fscal[2 .. 2 + l) and
-// the scalars of the bases H_{l+1} .. H_L are WRITTEN as zero (the buffers come from the pools and hold anything): a zero
-// scalar biased by K has the digit 0 in every window (fixed_digit), so the fixed-base kernels add nothing for those bases and
-// run unchanged.  DESIGN.md 8 "Mixed message counts".
-template <class C>
-struct PvScalarsMixed {
-    static __host__ __device__ void run(const MixedScalarArgs<PvArgs<C>>& m, size_t i) {
-        if (m.a.status[i] != ST_PENDING) return;
-        const int l = (int)m.len[i];
-        pv_scalars_item<C>(m.a, i, m.pref[l], l);
-        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
+// The derived forms (stages_common.hpp Form): the item's prefix and count from the job's DomainSrc.  In the two mixed forms the
+// item's scalars fill fscal[2 .. 2 + l) and the scalars of the bases H_{l+1} .. H_L are WRITTEN as zero (the buffers come from
+// the pools and hold anything): a zero scalar biased by K has the digit 0 in every window (fixed_digit), so the fixed-base
+// kernels add nothing for those bases and run unchanged.  DESIGN.md 8 "Job forms".
+template <class C, Form F>
+struct PvScalarsIn {
+    static __host__ __device__ void run(const FormArgs<C, PvArgs<C>>& f, size_t i) {
+        if (f.a.status[i] != ST_PENDING) return;
+        int l;
+        const HashCtx& h = form_domain<F, C>(f.a.cc, f.d, i, f.a.L, l);
+        pv_scalars_item<C>(f.a, i, h, l);
+        if constexpr (form_mixed(F)) mixed_zero_scalars(f.a.fscal, f.a.n, i, l, f.a.L);
     }
 };
 

@@ -68,17 +68,27 @@ struct SgScalars {
         sg_scalars_item<C>(a, i, a.cc->hash, a.sk, a.L);
     }
 };
-// Mixed lengths (bbs_ctx_set_mixed_lengths_gen): as PvScalarsMixed (stages_pv.hpp) -- the domain from the prefix of the item's
-// own length, e over its l messages, its scalars in fscal[2 .. 2 + l) and zeros WRITTEN for the bases behind them (also for an
-// item that ends here with -20: nothing reads its scalars, and nothing stale stays behind).  The HashCtx is read through the
-// per-lane pointer and passed on by reference, never copied into a local.
-template <class C>
-struct SgScalarsMixed {
-    static __host__ __device__ void run(const MixedScalarArgs<SgArgs<C>>& m, size_t i) {
-        if (m.a.status[i] != ST_PENDING) return;
-        const int l = (int)m.len[i];
-        sg_scalars_item<C>(m.a, i, m.pref[l], m.a.sk, l);
-        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
+// row k of the signing set (runtime.hpp SignSet: the 8 canonical words of sk_k, 32 bytes, 32-byte aligned).  The index
+// diverges per lane, so the row is read with vector loads into the lane's registers; it is the caller's public key_index.
+BBS_HD void sign_key_row(const uint32_t* sks, uint32_t k, uint32_t* sk) {
+    const uint32_t* row = static_cast<const uint32_t*>(__builtin_assume_aligned(sks + (size_t)8 * k, 32));
+    for (int j = 0; j < 8; j++) sk[j] = row[j];
+}
+// The derived forms, as PvScalarsIn (stages_pv.hpp).  core_sign meets the key in the domain, in the hash that gives e and in
+// 1 / (sk + e): the keyed forms take the lane's own secret row where the single-key forms take a.sk; SgMsmPart .. SgEmit never
+// see a key.  Mixed forms: e over the item's l messages, its scalars in fscal[2 .. 2 + l) and zeros WRITTEN for the bases
+// behind them (also for an item that ends here with -20: nothing reads its scalars, and nothing stale stays behind).
+template <class C, Form F>
+struct SgScalarsIn {
+    static __host__ __device__ void run(const FormArgs<C, SgArgs<C>>& f, size_t i) {
+        if (f.a.status[i] != ST_PENDING) return;
+        uint32_t row[8];
+        const uint32_t* sk = f.a.sk;
+        if constexpr (form_keyed(F)) { sign_key_row(f.d.sks, f.d.kidx[i], row); sk = row; }
+        int l;
+        const HashCtx& h = form_domain<F, C>(f.a.cc, f.d, i, f.a.L, l);
+        sg_scalars_item<C>(f.a, i, h, sk, l);
+        if constexpr (form_mixed(F)) mixed_zero_scalars(f.a.fscal, f.a.n, i, l, f.a.L);
     }
 };
 

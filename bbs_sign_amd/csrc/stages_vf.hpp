@@ -140,15 +140,16 @@ struct VfScalars {
         vf_scalars_item<C>(a, i, a.cc->hash, a.L);
     }
 };
-// mixed lengths (bbs_ctx_set_mixed_lengths): as PvScalarsMixed (stages_pv.hpp) -- the prefix of the item's own length, its l
-// messages, and zeros WRITTEN for the bases behind them
-template <class C>
-struct VfScalarsMixed {
-    static __host__ __device__ void run(const MixedScalarArgs<VfArgs<C>>& m, size_t i) {
-        if (m.a.status[i] != ST_PENDING) return;
-        const int l = (int)m.len[i];
-        vf_scalars_item<C>(m.a, i, m.pref[l], l);
-        mixed_zero_scalars(m.a.fscal, m.a.n, i, l, m.a.L);
+// the derived forms, as PvScalarsIn (stages_pv.hpp): the item's own prefix, its l messages, and in the mixed forms zeros
+// WRITTEN for the bases behind them
+template <class C, Form F>
+struct VfScalarsIn {
+    static __host__ __device__ void run(const FormArgs<C, VfArgs<C>>& f, size_t i) {
+        if (f.a.status[i] != ST_PENDING) return;
+        int l;
+        const HashCtx& h = form_domain<F, C>(f.a.cc, f.d, i, f.a.L, l);
+        vf_scalars_item<C>(f.a, i, h, l);
+        if constexpr (form_mixed(F)) mixed_zero_scalars(f.a.fscal, f.a.n, i, l, f.a.L);
     }
 };
 
