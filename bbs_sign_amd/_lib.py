@@ -68,6 +68,10 @@ SIGNATURES = {
     "bbs_ctx_set_mixed_lengths_gen": (ci, [vp, ci]),
     "bbs_ctx_set_keyed_mixed_lengths": (ci, [vp, ci]),
     "bbs_ctx_set_unit_lines": (ci, [vp, ci]),
+    # keyed batch verification: the switch, the report of a job, the segmented sums alone
+    "bbs_ctx_set_keyed_batch_verification": (ci, [vp, ci, c_u8p, sz]),
+    "bbs_job_bv_report": (ci, [vp, c_u32p, c_u32p, c_u32p]),
+    "bbs_selftest_segmented_sums": (ci, [vp, sz, c_u8p, c_u8p, sz, c_u64p, c_u64p, c_u8p]),
     "bbs_selftest_glv_split": (ci, [ci, c_u8p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "bbs_selftest_lin_pm": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),
     "bbs_selftest_mul3": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),

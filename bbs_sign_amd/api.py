@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import secrets
+import threading
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -390,6 +391,7 @@ class _IssuerEngine:
 
 
 _issuer_cache: Dict[tuple, _IssuerEngine] = {}
+_bv_lock = threading.Lock()          # _many_issuers: one call at a time switches keyed batch verification on a cached engine
 
 
 def _issuer_engine(curve, device, lib_path, L, pks) -> _IssuerEngine:
@@ -430,8 +432,16 @@ def sign_many_issuers(items: Sequence[tuple]) -> list:
     return out
 
 
-def _many_issuers(items, count, to_octets, run):
-    """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms."""
+def _many_issuers(items, count, to_octets, run, batch_verification=False):
+    """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms.
+    batch_verification: bbs_ctx_set_keyed_batch_verification on the cached engine for this call -- True: the library's default
+    threshold; an integer >= 1: that many items per key -- with a fresh seed from the operating system, and off again
+    afterwards.  Off is the state the cache keeps its engines in (nothing else holds them), so that is the prior state.  Calls
+    that ask for it take ``_bv_lock`` in turn; a call WITHOUT it that runs on the same engine meanwhile may find the switch on,
+    which changes how its items are decided, not what is decided."""
+    min_items = 0 if batch_verification is True else int(batch_verification)
+    if min_items < 0:
+        raise ValueError("batch_verification: True, False or a number of items per key")
     out: list = [None] * len(items)
     groups: Dict[tuple, List[int]] = {}
     for i, it in enumerate(items):
@@ -439,31 +449,45 @@ def _many_issuers(items, count, to_octets, run):
     for (curve, device, lib_path), idx in groups.items():
         its = [items[i] for i in idx]
         ie = _issuer_engine(curve, device, lib_path, max(count(it) for it in its), [it[0].pk for it in its])
-        got = _many(its, lambda obj: to_octets(curve, obj, lib_path),
-                    lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
+        call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path),
+                             lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
+        if batch_verification:
+            with _bv_lock:
+                ie.eng.set_keyed_batch_verification(True, None, min_items)
+                try:
+                    got = call()
+                finally:
+                    ie.eng.set_keyed_batch_verification(False)
+        else:
+            got = call()
         for i, g in zip(idx, got):
             out[i] = g
     return out
 
 
-def verify_many_issuers(items: Sequence[tuple]) -> list:
+def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False) -> list:
     """PublicKey.verify for many items ``(pk, signature, header, messages)`` of ANY issuers and ANY message counts, in ONE
     device call per (curve, device, lib_path): one cached engine with bbs_ctx_set_keyed_mixed_lengths on, whose L is the
     largest count seen and whose key set grows by appending (a key is registered once).  Entry i is the boolean
     ``items[i][0].verify(*items[i][1:])`` returns, or the BbsError it raises (returned, not raised: the other items stand).
     One divergence: a ``pk`` the library refuses (not on the twist or outside the subgroup -- octets_to_public_key never returns
     one) is registered as a refused key, and its items get ``BbsError(-44)`` (BBS_ST_UNKNOWN_KEY), where the one-item form
-    fails with a BbsRuntimeError from bbs_ctx_set_public_key."""
+    fails with a BbsRuntimeError from bbs_ctx_set_public_key.
+    ``batch_verification=True`` switches bbs_ctx_set_keyed_batch_verification on for this call: the items of an issuer that
+    has enough of them in the list (the library's default threshold; an integer >= 1 instead of True: that many) are checked by
+    16 combined pairing products; the entries are the same."""
     return _many_issuers(items, lambda it: len(it[3]), signature_to_octets,
-                         lambda eng, kidx, octs, its: eng.verify_wire_keyed_batch(kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]))
+                         lambda eng, kidx, octs, its: eng.verify_wire_keyed_batch(kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]),
+                         batch_verification)
 
 
-def proof_verify_many_issuers(items: Sequence[tuple]) -> list:
+def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False) -> list:
     """proof_verify for many items ``(pk, proof, header, ph, disclosed_messages, disclosed_indexes)`` of any issuers and any
-    message counts (commitments + disclosed indexes each), as verify_many_issuers."""
+    message counts (commitments + disclosed indexes each), as verify_many_issuers (``batch_verification`` included)."""
     return _many_issuers(items, lambda it: len(it[1].commitments) + len(it[5]), proof_to_octets,
                          lambda eng, kidx, octs, its: eng.proof_verify_wire_keyed_batch(
-                             kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]))
+                             kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]),
+                         batch_verification)
 
 
 def proof_gen_many_issuers(items: Sequence[tuple]) -> list:

@@ -490,6 +490,17 @@ int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_keyed_mixed_lengths(enabled); });
 }
+int bbs_ctx_set_keyed_batch_verification(bbs_ctx* ctx, int enabled, const uint8_t* seed32, size_t min_items_per_key) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->set_keyed_batch_verification(enabled, seed32, min_items_per_key); });
+}
+int bbs_selftest_segmented_sums(bbs_ctx* ctx, size_t n, const uint8_t* points_affine, const uint8_t* digits, size_t n_groups,
+                                const uint64_t* group_first, const uint64_t* group_count, uint8_t* out_affine) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) {
+        return selftest_segmented_sums<curve_of<decltype(c)>>(c, n, points_affine, digits, n_groups, group_first, group_count, out_affine);
+    });
+}
 int bbs_ctx_set_unit_lines(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_unit_lines(enabled); });
@@ -616,6 +627,11 @@ int bbs_job_fetch_proofs(bbs_job* job, uint8_t* pf, uint8_t* cm, uint64_t* cmo) 
 void bbs_job_free(bbs_job* job) { delete job; }
 const char* bbs_job_stage_name(const bbs_job* job, int k) {
     return (job && k >= 0 && (size_t)k < job->stages.size()) ? job->stages[k].name : nullptr;
+}
+int bbs_job_bv_report(bbs_job* job, uint32_t* groups, uint32_t* groups_passed, uint32_t* items_in_groups) {
+    if (!job || !groups || !groups_passed || !items_in_groups) return BBS_E_ARG;
+    *groups = *groups_passed = *items_in_groups = 0;
+    return job->bv_report ? job->bv_report(groups, groups_passed, items_in_groups) : BBS_OK;
 }
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int cap, int* n_stages) {
     if (!job || reps < 1) return BBS_E_ARG;

@@ -13,11 +13,29 @@ struct JobForm {
     uint32_t* len = nullptr;                 // src.len as the MIXED ingest bodies write it
     bool mixed() const { return form_mixed(form); }
 };
+// keyed batch verification (bbs_ctx_set_keyed_batch_verification; pippenger.hpp): the plan keyed_bv_plan makes of a job whose
+// context has the switch on, and the arguments of the five stages add_keyed_bv_stages builds on it.  G == 0: no group formed.
+template <class C>
+struct KeyedBv {
+    uint32_t G = 0, n_segs = 0, items = 0;   // groups, segments, items that belong to a group
+    size_t n_pos = 0;                        // positions of the bv order (a multiple of 4)
+    // the plan's words in the job's staging image (offsets in words from `at`): pos_of_item[n], item_group[n], segs[3 n_segs],
+    // grp_seg[2 G], grp_run[2 G], the virtual items' kidx[16 G], their pairing order [slots][wave keys], their gates [16 G bytes]
+    size_t at = 0, o_grp = 0, o_segs = 0, o_gseg = 0, o_grun = 0, o_vkidx = 0, o_vslots = 0, o_gates = 0;
+    size_t v_uni = 0, v_slots = 0;           // the virtual items' pairing order: uniform slots, all slots
+    KeyedRlcPrepArgs<C> prep{};
+    PipSegArgs<C> seg{};
+    PairArgs<C> vpa{};                       // the 16 G virtual items: points = the groups' window sums, out = the verdicts
+    PairKeyedArgs<C> vpair{};
+    KeyedBvDecideArgs dec{};
+    int8_t* verdicts = nullptr;              // [16 G], cleared before every run: a check that never ran reads as failed
+};
 // verify / proof_verify: plus the keyed pairing order
 template <class C>
 struct PairedJobForm : JobForm<C> {
     PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
     bool unit = false;                       // line form of the key set the job holds (KeySet::unit)
+    KeyedBv<C> bv{};                         // keyed batch verification, where the context's switch was on at upload
 };
 
 // The form of an upload and its state checks.  The context's switches are read HERE, once: the checks, the stages and the
@@ -50,28 +68,19 @@ int decide_form(const Ctx<C>* ctx, FormOp op, size_t n, const uint32_t* key_inde
 // key k with c items fills floor(c / 10) key-uniform wavefronts, its c mod 10 remaining items go to the mixed wavefronts
 // behind them.  `words` = [kidx n][uniform slots][mixed slots][wave keys]; it travels in the job's staging image (the one
 // asynchronous copy), keyed_bind points the job at it.
-template <class C, class J>
-void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJobForm<C>& jf, std::vector<uint32_t>& words) {
+// The ordering itself, for n items with keys kid[i] (KEY_NONE: in no slot) and cnt[k] items per key: `order` = [uniform
+// slots][mixed slots][wave keys].  It orders the real items of a job and the virtual items of keyed batch verification alike.
+inline void keyed_slots(const uint32_t* kid, size_t n, const std::vector<uint32_t>& cnt, std::vector<uint32_t>& order, size_t& n_uni, size_t& n_slots) {
     constexpr uint32_t W = (uint32_t)KEY_SLOTS_PER_WAVE;
-    const auto ks = ctx->keys;
-    j->key_set = ks;
-    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
-    std::vector<uint32_t> cnt(nk, 0);
-    words.assign(3 * n + n / W + 1, 0);
-    uint32_t* kid = words.data();
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = key_index[i];
-        const bool ok = k < nk && ks->status[k] == 1;
-        kid[i] = ok ? k : KEY_NONE;
-        if (ok) cnt[k]++;
-    }
+    const size_t nk = cnt.size();
     std::vector<uint32_t> ufirst(nk), mfirst(nk), seen(nk, 0);
     size_t nu = 0, nm = 0;
     for (size_t k = 0; k < nk; k++) {
         ufirst[k] = (uint32_t)nu; nu += cnt[k] / W * W;
         mfirst[k] = (uint32_t)nm; nm += cnt[k] % W;
     }
-    uint32_t* uslot = words.data() + n;
+    order.assign(nu + nm + nu / W, 0);
+    uint32_t* uslot = order.data();
     uint32_t* mslot = uslot + nu;
     uint32_t* wkey = mslot + nm;
     for (size_t i = 0; i < n; i++) {
@@ -83,10 +92,87 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJ
     }
     for (size_t k = 0, w = 0; k < nk; k++)
         for (uint32_t q = 0; q < cnt[k] / W; q++) wkey[w++] = (uint32_t)k;
-    words.resize(n + nu + nm + nu / W);
+    n_uni = nu; n_slots = nu + nm;
+}
+// Keyed batch verification, beside the slot map: the BV ORDER of a job (pippenger.hpp).  Key k forms a group iff cnt[k] >=
+// min_items; the grouped items are sorted by key, stably, every group's run starting at a multiple of 4; a run is cut into
+// segments of at most PIP_TILE items; group g has the 16 virtual items g * 16 + w under its key, ordered for the pairing
+// kernel by keyed_slots as real items are.  Appends the plan to `words` (layout: KeyedBv) -- nothing where no group forms.
+template <class C>
+void keyed_bv_plan(size_t n, const std::vector<uint32_t>& cnt, size_t min_items, KeyedBv<C>& bv, std::vector<uint32_t>& words) {
+    const size_t nk = cnt.size();
+    std::vector<uint32_t> group_of(nk, BV_NONE), first, seen;
+    std::vector<uint32_t> vcnt(nk, 0);
+    size_t cur = 0, items = 0;
+    uint32_t G = 0;
+    for (size_t k = 0; k < nk; k++) {
+        if (!cnt[k] || cnt[k] < min_items) continue;
+        group_of[k] = G++;
+        vcnt[k] = 16;
+        first.push_back((uint32_t)cur);
+        cur += ((size_t)cnt[k] + 3) & ~(size_t)3;
+        items += cnt[k];
+    }
+    bv = KeyedBv<C>{};
+    if (!G || cur > 0xFFFFFFF0ull) return;
+    bv.G = G; bv.items = (uint32_t)items; bv.n_pos = cur;
+    seen.assign(G, 0);
+    std::vector<uint32_t> pw(2 * n, BV_NONE);           // pos_of_item, item_group
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = words[i];                     // (kidx of the real items)
+        const uint32_t g = k == KEY_NONE ? BV_NONE : group_of[k];
+        if (g == BV_NONE) continue;
+        pw[i] = first[g] + seen[g]++;
+        pw[n + i] = g;
+    }
+    bv.o_grp = n;
+    bv.o_segs = pw.size();
+    std::vector<uint32_t> gseg(2 * (size_t)G), grun(2 * (size_t)G), vkid(16 * (size_t)G);
+    uint32_t n_segs = 0;
+    for (size_t k = 0; k < nk; k++) {
+        const uint32_t g = group_of[k];
+        if (g == BV_NONE) continue;
+        gseg[2 * g] = n_segs;
+        for (uint32_t off = 0; off < cnt[k]; off += PIP_TILE) {
+            pw.push_back(first[g] + off); pw.push_back(std::min<uint32_t>(PIP_TILE, cnt[k] - off)); pw.push_back(g);
+            n_segs++;
+        }
+        gseg[2 * g + 1] = n_segs - gseg[2 * g];
+        grun[2 * g] = first[g]; grun[2 * g + 1] = cnt[k];
+        for (int w = 0; w < 16; w++) vkid[16 * (size_t)g + w] = (uint32_t)k;
+    }
+    bv.n_segs = n_segs;
+    bv.o_gseg = pw.size(); pw.insert(pw.end(), gseg.begin(), gseg.end());
+    bv.o_grun = pw.size(); pw.insert(pw.end(), grun.begin(), grun.end());
+    bv.o_vkidx = pw.size(); pw.insert(pw.end(), vkid.begin(), vkid.end());
+    std::vector<uint32_t> vorder;
+    keyed_slots(vkid.data(), vkid.size(), vcnt, vorder, bv.v_uni, bv.v_slots);
+    bv.o_vslots = pw.size(); pw.insert(pw.end(), vorder.begin(), vorder.end());
+    bv.o_gates = pw.size(); pw.insert(pw.end(), 4 * (size_t)G, 0x01010101u);       // 16 G gate bytes, all 1
+    bv.at = words.size();
+    words.insert(words.end(), pw.begin(), pw.end());
+}
+template <class C, class J>
+void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJobForm<C>& jf, std::vector<uint32_t>& words) {
+    const auto ks = ctx->keys;
+    j->key_set = ks;
+    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
+    std::vector<uint32_t> cnt(nk, 0);
+    words.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = key_index[i];
+        const bool ok = k < nk && ks->status[k] == 1;
+        words[i] = ok ? k : KEY_NONE;
+        if (ok) cnt[k]++;
+    }
+    std::vector<uint32_t> order;
+    size_t nu = 0, ns = 0;
+    keyed_slots(words.data(), n, cnt, order, nu, ns);
+    words.insert(words.end(), order.begin(), order.end());
     jf.src.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
-    jf.pair.keys = jf.src.keys; jf.pair.n_uni = nu; jf.pair.n_slots = nu + nm;
+    jf.pair.keys = jf.src.keys; jf.pair.n_uni = nu; jf.pair.n_slots = ns;
     jf.unit = ks ? ks->unit : ctx->lines_unit();
+    if (ctx->keyed_bv) keyed_bv_plan<C>(n, cnt, ctx->keyed_bv_min, jf.bv, words);
 }
 // the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
 template <class C, class J>
@@ -127,6 +213,16 @@ template <class C>
 void keyed_bind(PairedJobForm<C>& jf, size_t n, const uint32_t* d) {
     jf.src.kidx = d;
     jf.pair.kidx = d; jf.pair.slot_item = d + n; jf.pair.wave_key = d + n + jf.pair.n_slots;
+    KeyedBv<C>& bv = jf.bv;
+    if (!bv.G) return;
+    const uint32_t* b = d + bv.at;
+    bv.prep.pos_of_item = b;
+    bv.dec.item_group = b + bv.o_grp;
+    bv.seg.segs = b + bv.o_segs; bv.seg.grp_seg = b + bv.o_gseg; bv.seg.grp_run = b + bv.o_grun;
+    bv.vpair.keys = jf.pair.keys; bv.vpair.kidx = b + bv.o_vkidx;
+    bv.vpair.slot_item = b + bv.o_vslots; bv.vpair.wave_key = b + bv.o_vslots + bv.v_slots;
+    bv.vpair.n_uni = bv.v_uni; bv.vpair.n_slots = bv.v_slots;
+    bv.vpa.gate_arr = reinterpret_cast<const int8_t*>(b + bv.o_gates);
 }
 // behind the ingest stage: items with an unknown key are decided (BBS_ST_UNKNOWN_KEY)
 template <class J>
@@ -134,25 +230,91 @@ int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
     return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
 }
 // the pairing step of a keyed job on the main (aux = 0) or second stream, as add_pairing_stages: the fused kernel in both job
-// forms.  jf->pair.p is copied from *pa when the stage is launched.
+// forms.  pair->p is copied from *pa when the stage is launched.  pair = null: the job's real items (jf->pair) under the usual
+// stage names; keyed batch verification passes its virtual items and its own names.
 template <class C, class J>
-void add_keyed_pairing_stages(J* j, PairedJobForm<C>* jf, const PairArgs<C>* pa, int aux) {
+void add_keyed_pairing_stages(J* j, PairedJobForm<C>* jf, const PairArgs<C>* pa, int aux, PairKeyedArgs<C>* pair = nullptr,
+                              [[maybe_unused]] const char* nm = nullptr, [[maybe_unused]] const char* nm_final = nullptr) {
+    if (!pair) pair = &jf->pair;
 #ifdef BBS_HOST_TWIN
-    j->stages.push_back({"pair_miller_keyed", [j, jf, pa, aux]() {
-        jf->pair.p = *pa;
-        return rt::launch<PairMillerKeyed<C>>(aux ? j->stream_aux() : j->stream(), jf->pair, jf->pair.n_slots * 2);
+    j->stages.push_back({nm ? nm : "pair_miller_keyed", [j, pair, pa, aux]() {
+        pair->p = *pa;
+        return rt::launch<PairMillerKeyed<C>>(aux ? j->stream_aux() : j->stream(), *pair, pair->n_slots * 2);
     }, aux, 0});
-    j->stages.push_back({"pair_final_exp", [j, pa, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pa, pa->n); }, aux, 0});
+    j->stages.push_back({nm_final ? nm_final : "pair_final_exp", [j, pa, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pa, pa->n); }, aux, 0});
 #else
-    j->stages.push_back({"pairing_6lane_keyed", [j, jf, pa, aux]() {
-        jf->pair.p = *pa;
+    j->stages.push_back({nm ? nm : "pairing_6lane_keyed", [j, jf, pair, pa, aux]() {
+        pair->p = *pa;
         // the key set the job holds and BP2's table on the device must agree (they do unless the form was switched under the job)
         if (jf->unit != j->ctx->dev_lines_unit) return -1;
         rt::Stream& st = aux ? j->stream_aux() : j->stream();
-        const size_t nt = ((jf->pair.n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
-        return jf->unit ? rt::launch<PairDistKeyed<C, true>>(st, jf->pair, nt) : rt::launch<PairDistKeyed<C, false>>(st, jf->pair, nt);
+        const size_t nt = ((pair->n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
+        return jf->unit ? rt::launch<PairDistKeyed<C, true>>(st, *pair, nt) : rt::launch<PairDistKeyed<C, false>>(st, *pair, nt);
     }, aux, 0});
 #endif
+}
+
+// Keyed batch verification: the five stages of pippenger.hpp on the job's main stream, in front of the per-item keyed pairing
+// step.  pa / pb: the two points of every item, Montgomery SoA [2N][n]; the items that take part are those with status ==
+// ST_PAIRING.  No group (switch off, or no key reaches the threshold): nothing is added and the job is what it was.
+// The job must have been planned (keyed_order) and bound (keyed_bind).
+template <class C, class J>
+int add_keyed_bv_stages(J* j, Ctx<C>* ctx, PairedJobForm<C>* jf, size_t n, const CtxConsts<C>* cc, const uint32_t* pa, const uint32_t* pb,
+                        int negate_b, int8_t* status) {
+    constexpr int N = C::FpP::N;
+    constexpr int NW = 16, M = 2;
+    KeyedBv<C>* bv = &jf->bv;
+    if (!bv->G) return BBS_OK;
+    const size_t NV = (size_t)NW * bv->G;
+    int rc = BBS_OK;
+    uint8_t* dig = j->template scratch<uint8_t>((size_t)NW * bv->n_pos + 4, rc);
+    uint32_t* ppts = j->template scratch<uint32_t>((size_t)M * bv->n_pos * 2 * N, rc);
+    uint32_t* seg_sums = j->template scratch<uint32_t>((size_t)3 * N * M * NW * bv->n_segs, rc);
+    uint32_t* out = j->template scratch<uint32_t>((size_t)M * 2 * N * NV, rc);
+    bv->verdicts = j->template scratch<int8_t>(NV, rc);
+    if (rc) return rc;
+    // pad positions are never written: their digits stay 0 (and their points the identity) for every run of the job
+    if (rt::dmemset(dig, 0, (size_t)NW * bv->n_pos, j->stream()) || rt::dmemset(ppts, 0, (size_t)M * bv->n_pos * 2 * N * 4, j->stream())) return BBS_E_HIP;
+    j->zero_on_reset.push_back({bv->verdicts, NV});
+    RlcPrepArgs<C>& pr = bv->prep.r;
+    pr.n = n; pr.n_pad = bv->n_pos; pr.pa = pa; pr.pb = pb; pr.canonical = 0; pr.gate_arr = status; pr.gate = ST_PAIRING;
+    pr.dig = dig; pr.ppts = ppts;
+    ctx->next_rlc_seed(pr.seed);
+    PipSegArgs<C>& sg = bv->seg;
+    sg.n_pos = bv->n_pos; sg.M = M; sg.NW = NW; sg.n_segs = bv->n_segs; sg.n_groups = bv->G;
+    sg.ppts = ppts; sg.dig = dig; sg.seg_sums = seg_sums; sg.out = out;
+    PairArgs<C>& ps = bv->vpa;
+    ps.n = NV; ps.cc = cc; ps.pa = out; ps.pb = out + (size_t)2 * N * NV; ps.negate_b = negate_b; ps.canonical = 0;
+    ps.gate = 1; ps.out = bv->verdicts; ps.fmiller = nullptr; ps.single = 0; ps.batch_ok = nullptr; ps.n_checks = 0;
+#ifdef BBS_HOST_TWIN
+    ps.fmiller = j->template scratch<uint32_t>((size_t)2 * 12 * N * NV, rc);      // (the fused device kernel keeps the Miller values in registers)
+    if (rc) return rc;
+#endif
+    bv->dec.n = n; bv->dec.verdicts = bv->verdicts; bv->dec.status = status;
+    j->stages.push_back({"keyed_rlc_prep", [j, bv]() { return rt::launch<KeyedRlcPrep<C>>(j->stream(), bv->prep, j->n); }});
+#ifdef BBS_HOST_TWIN
+    j->stages.push_back({"keyed_pip_windows", [j, bv]() { return rt::launch<PipGroupSumsHost<C>>(j->stream(), bv->seg, (size_t)bv->seg.M * bv->seg.NW * bv->seg.n_groups); }});
+#else
+    j->stages.push_back({"keyed_pip_windows", [j, bv]() { return rt::launch_pip_window_segs<C>(j->stream(), bv->seg); }});
+#endif
+    j->stages.push_back({"keyed_pip_group_sums", [j, bv]() { return rt::launch<PipGroupSums<C>>(j->stream(), bv->seg, (size_t)bv->seg.M * bv->seg.NW * bv->seg.n_groups); }});
+    add_keyed_pairing_stages<C>(j, jf, &bv->vpa, 0, &bv->vpair, "keyed_rlc_pairing", "keyed_rlc_pair_final_exp");
+    j->stages.push_back({"keyed_bv_decide", [j, bv]() { return rt::launch<KeyedBvDecide>(j->stream(), bv->dec, j->n); }});
+    // bbs_job_bv_report: groups formed, groups whose 16 checks all passed (the verdicts read back on request), grouped items
+    j->bv_report = [j, bv](uint32_t* groups, uint32_t* passed, uint32_t* items) {
+        std::vector<int8_t> v((size_t)16 * bv->G);
+        if (j->use() || rt::sync(j->stream())) return (int)BBS_E_HIP;
+        if (rt::d2h(v.data(), bv->verdicts, v.size(), j->stream())) return (int)BBS_E_HIP;
+        uint32_t ok = 0;
+        for (uint32_t g = 0; g < bv->G; g++) {
+            bool all = true;
+            for (int w = 0; w < 16; w++) all &= v[(size_t)g * 16 + w] == 1;
+            ok += all ? 1u : 0u;
+        }
+        *groups = bv->G; *passed = ok; *items = bv->items;
+        return (int)BBS_OK;
+    };
+    return BBS_OK;
 }
 
 // ---- mixed forms: the per-item length array and the prefixes the scalar stage starts from ---------------------------------

@@ -29,7 +29,10 @@ constexpr const char* PV_SCALARS[4] = {"pv_scalars", "pv_scalars_mixed", "pv_sca
 
 // the form is deduced from the fields of PvIn that are set (ops_decl.hpp)
 // KEYED (bbs_*_keyed_*, instantiated in tu_pvk_*.hip): item i is verified under key key_index[i] of the context's key set
-// (keyed.hpp): its own domain and W line table; the fused pairing kernel in both job forms, no batch verification
+// (keyed.hpp): its own domain and W line table; the fused pairing kernel in both job forms.  bbs_ctx_set_batch_verification does
+// not apply; bbs_ctx_set_keyed_batch_verification does, per key: where a key reaches the threshold the job takes the layout of
+// the un-keyed throughput-form batch path (combination behind the challenge stage, per-item kernel over what stays pending)
+// in the latency form too
 template <class C, bool KEYED>
 int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     const bool wire = in.oct_off != nullptr;
@@ -173,7 +176,24 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         if (layout == 1) j->stages.push_back({"pv_chains", [j]() { return rt::launch<PvChains<C>>(j->stream(), j->a, j->n * PvChains<C>::units(j->a)); }});
     };
     const int join_chains = 2;      // Stage::join bit of the second side stream (ignored where nothing was forked onto it)
-    if (KEYED || !ctx->batch_verify) {
+    bool keyed_bv = false;
+    if constexpr (KEYED) keyed_bv = job->jf.bv.G != 0;
+    if (keyed_bv) {
+        if constexpr (KEYED) {
+            // keyed batch verification (bbs_ctx_set_keyed_batch_verification; pippenger.hpp): the MSM chain as a keyed job has it,
+            // the plain challenge stage (it leaves ST_PAIRING on the items whose challenge matched), then the combination per
+            // key and its decision, and behind them the per-item keyed kernel over the items still pending -- the layout of the
+            // un-keyed throughput-form batch path below (points = a.aff, Montgomery, stored by PvT1Chain; gate and verdict in
+            // the status array), here in BOTH job forms: the combination needs the challenge's verdict, so it cannot run
+            // beside the MSM chain as the per-item pairing of a keyed job does.  Everything on the main stream.
+            msm_chain(pv_msm_layout(false, job->latency_form));
+            j->stages.push_back({"pv_challenge", [j]() { return rt::launch<PvChallenge<C>>(j->stream(), j->a, j->n); }, 0, join_chains});
+            pa.pa = a.aff; pa.pb = a.aff + (size_t)2 * N * n; pa.canonical = 0;
+            pa.gate_arr = a.status; pa.gate = ST_PAIRING; pa.out = a.status;
+            if ((rc = add_keyed_bv_stages<C>(j, ctx, &j->jf, n, a.cc, pa.pa, pa.pb, 1, a.status))) return rc;
+            add_keyed_pairing_stages<C>(j, &j->jf, &j->pa, 0);
+        }
+    } else if (KEYED || !ctx->batch_verify) {
         // every item its own pairing product, on the job's second stream concurrently with the MSM / challenge
         // stages: it needs only the proof's own points (canonical, converted in the kernel) and the flag the ingest stage
         // left.  First in the list: the second stream forks where its first stage stands, i.e. before the MSM chain.

@@ -18,7 +18,8 @@ struct VfJob : JobBase<C> {
 constexpr const char* VF_SCALARS[4] = {"vf_scalars", "vf_scalars_mixed", "vf_scalars_keyed", "vf_scalars_keyed_mixed"};
 
 // KEYED (bbs_*_keyed_*, instantiated in tu_vfk_*.hip): item i is verified under key key_index[i] of the context's key set
-// (keyed.hpp); the fused pairing kernel in both job forms, no batch verification
+// (keyed.hpp); the fused pairing kernel in both job forms; bbs_ctx_set_batch_verification does not apply,
+// bbs_ctx_set_keyed_batch_verification puts the combination per key in front of it
 template <class C, bool KEYED>
 int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
@@ -110,6 +111,9 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     j->stages.push_back({"vf_fixed_chunks", [j]() { return rt::launch<VfFixedChunk<C>>(j->stream(), j->a, j->n * (size_t)NFIX); }});
     j->stages.push_back({"vf_combine", [j]() { return rt::launch<VfCombine<C>>(j->stream(), j->a, j->n); }, 0, 1});
     if constexpr (KEYED) {
+        // keyed batch verification (bbs_ctx_set_keyed_batch_verification): the combination per key and its decision go in front of
+        // the per-item kernel, which then computes only the items still pending (nothing is added where no group formed)
+        if ((rc = add_keyed_bv_stages<C>(j, ctx, &j->jf, n, a.cc, pa.pa, pa.pb, 0, a.status))) return rc;
         add_keyed_pairing_stages<C>(j, &j->jf, &j->pa, 0);
     } else if (!ctx->batch_verify) {
         add_pairing_stages<C>(j, &j->pa, 0, "pair_miller", "pair_final_exp", "pairing_6lane");
@@ -120,6 +124,80 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
         add_batch_decision<C>(j, &j->bv, &j->pa, 0);
     }
     *out = job.release();
+    return BBS_OK;
+}
+
+// ---- bbs_selftest_segmented_sums -------------------------------------------------------------------------------------------
+// Stages 2 - 3 of keyed batch verification alone (pippenger.hpp): n points in group order, 16 digit rows, G groups given as
+// runs of the input -> the 16 window sums of every group.  The bv order (runs at multiples of 4, segments of at most PIP_TILE
+// items) is built here as keyed_bv_plan builds it.  Product library: k_pip_window_seg; host twin: PipGroupSumsHost.
+// Instantiated in the keyed verify units, where the kernel lives.
+template <class C>
+int selftest_segmented_sums(Ctx<C>* ctx, size_t n, const uint8_t* points_affine, const uint8_t* digits, size_t n_groups,
+                            const uint64_t* group_first, const uint64_t* group_count, uint8_t* out_affine) {
+    constexpr int N = C::FpP::N;
+    constexpr int FPB = 4 * C::FpP::NC;
+    constexpr int NW = 16;
+    using P = typename C::FpP;
+    if (!n_groups) return BBS_OK;
+    if (!group_first || !group_count || !out_affine || (n && (!points_affine || !digits))) return BBS_E_ARG;
+    if (n > 0x7FFFFFFFull || n_groups > 0x00FFFFFFull) return BBS_E_ARG;
+    std::vector<uint32_t> segs, gseg(2 * n_groups), grun(2 * n_groups);
+    size_t n_pos = 0;
+    for (size_t g = 0; g < n_groups; g++) {
+        if (group_first[g] > n || group_count[g] > n - group_first[g]) return BBS_E_ARG;
+        const uint32_t cnt = (uint32_t)group_count[g];
+        gseg[2 * g] = (uint32_t)(segs.size() / 3);
+        for (uint32_t off = 0; off < cnt; off += PIP_TILE) {
+            segs.push_back((uint32_t)n_pos + off); segs.push_back(std::min<uint32_t>(PIP_TILE, cnt - off)); segs.push_back((uint32_t)g);
+        }
+        gseg[2 * g + 1] = (uint32_t)(segs.size() / 3) - gseg[2 * g];
+        grun[2 * g] = (uint32_t)n_pos; grun[2 * g + 1] = cnt;
+        n_pos += ((size_t)cnt + 3) & ~(size_t)3;
+        if (n_pos > 0x7FFFFFF0ull) return BBS_E_ARG;
+    }
+    const size_t n_segs = segs.size() / 3, NV = (size_t)NW * n_groups;
+    std::vector<uint32_t> hp(std::max<size_t>(n_pos, 1) * 2 * N, 0);
+    std::vector<uint8_t> hd((size_t)NW * n_pos + 4, 0);
+    for (size_t g = 0; g < n_groups; g++) {
+        for (size_t k = 0; k < group_count[g]; k++) {
+            const size_t i = group_first[g] + k, pos = grun[2 * g] + k;
+            G1Aff<C> pt;
+            if (!fe_from_le_bytes<P>(points_affine + i * 2 * FPB, pt.x) || !fe_from_le_bytes<P>(points_affine + i * 2 * FPB + FPB, pt.y)) return BBS_E_ARG;
+            if (!g1a_on_curve<C>(pt)) return BBS_E_ARG;           // ((0, 0) is the identity)
+            for (int j = 0; j < N; j++) { hp[pos * 2 * N + j] = pt.x.v[j]; hp[pos * 2 * N + N + j] = pt.y.v[j]; }
+            for (int w = 0; w < NW; w++) hd[(size_t)w * n_pos + pos] = digits[(size_t)w * n + i];
+        }
+    }
+    if (ctx->use()) return BBS_E_HIP;
+    std::vector<uint32_t> tab(segs);
+    if (tab.empty()) tab.push_back(0);
+    const size_t o_gseg = tab.size(); tab.insert(tab.end(), gseg.begin(), gseg.end());
+    const size_t o_grun = tab.size(); tab.insert(tab.end(), grun.begin(), grun.end());
+    DevBuf dTab, dP, dD, dS, dOut;
+    if (dTab.alloc(tab.size() * 4) || dP.alloc(hp.size() * 4) || dD.alloc(hd.size()) || dS.alloc(std::max<size_t>((size_t)3 * N * NW * n_segs, 1) * 4) ||
+        dOut.alloc((size_t)2 * N * NV * 4)) return BBS_E_NOMEM;
+    if (rt::h2d(dTab.p, tab.data(), tab.size() * 4, ctx->stream) || rt::h2d(dP.p, hp.data(), hp.size() * 4, ctx->stream) ||
+        rt::h2d(dD.p, hd.data(), hd.size(), ctx->stream)) return BBS_E_HIP;
+    PipSegArgs<C> a{};
+    a.n_pos = n_pos; a.M = 1; a.NW = NW; a.n_segs = (uint32_t)n_segs; a.n_groups = (uint32_t)n_groups;
+    a.segs = dTab.as<uint32_t>(); a.grp_seg = a.segs + o_gseg; a.grp_run = a.segs + o_grun;
+    a.ppts = dP.as<uint32_t>(); a.dig = dD.as<uint8_t>(); a.seg_sums = dS.as<uint32_t>(); a.out = dOut.as<uint32_t>();
+#ifdef BBS_HOST_TWIN
+    if (rt::launch<PipGroupSumsHost<C>>(ctx->stream, a, NV)) return BBS_E_HIP;
+#else
+    if (rt::launch_pip_window_segs<C>(ctx->stream, a)) return BBS_E_HIP;
+#endif
+    if (rt::launch<PipGroupSums<C>>(ctx->stream, a, NV) || rt::sync(ctx->stream)) return BBS_E_HIP;
+    std::vector<uint32_t> w((size_t)2 * N * NV);
+    if (rt::d2h(w.data(), dOut.p, w.size() * 4, ctx->stream)) return BBS_E_HIP;
+    for (size_t v = 0; v < NV; v++) {
+        G1Aff<C> r;
+        for (int j = 0; j < N; j++) { r.x.v[j] = w[(size_t)j * NV + v]; r.y.v[j] = w[(size_t)(N + j) * NV + v]; }
+        uint8_t* o = out_affine + v * 2 * FPB;
+        if (g1a_is_inf<C>(r)) std::memset(o, 0, 2 * FPB);
+        else { fe_to_le_bytes<P>(r.x, o); fe_to_le_bytes<P>(r.y, o + FPB); }
+    }
     return BBS_OK;
 }
 

@@ -127,6 +127,9 @@ extern template int Ctx<BnCurve>::add_keys(bool, size_t, const uint8_t*, const i
 extern template int Ctx<BnCurve>::set_keyed_mixed_lengths(int);
 extern template int Ctx<BnCurve>::rebuild_lines();
 extern template int selftest_key_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const int8_t*, const uint8_t*, int, uint8_t*, int8_t*, uint8_t*);
+template <class C> int selftest_segmented_sums(Ctx<C>*, size_t, const uint8_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, uint8_t*);
+extern template int selftest_segmented_sums<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, uint8_t*);
+extern template int selftest_segmented_sums<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, uint8_t*);
 template <class C> int key_gen_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint8_t*, int8_t*);
 template <class C> int sk_to_pk_batch(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*, int8_t*);
 template <class C> int add_secret_keys(Ctx<C>*, bool, size_t, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);

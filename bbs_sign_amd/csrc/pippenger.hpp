@@ -167,7 +167,7 @@ struct PipWindowSums {
 //      add up: PipTileSums (lane per window) adds the tiles and normalises (or shifts, for the plain MSM).
 // HBM traffic per workgroup: PIP_TILE digit bytes + its points once (112 B each on BLS12-381) -- the algorithmic minimum.
 constexpr int PIP_TILE = 4096;
-constexpr int PIP_WG = 256;
+constexpr int PIP_WG = 256;           // (k_pip_window_seg further down is k_pip_window's twin over a segment table: keep the two in step)
 
 template <class C>
 struct PipCoopArgs {
@@ -402,6 +402,263 @@ struct RlcPrep {
         g1a_store_mont<C>(a.ppts + (a.n + i) * 2 * N, 1, 0, q);
     }
 };
+
+// =============================================================================================
+// Keyed batch verification: one combination PER ISSUER KEY (bbs_ctx_set_keyed_batch_verification)
+// =============================================================================================
+// The argument of the head of this file, applied per key: for key k the library checks
+//   e(sum rho_i Abar_i, W_k) e(sum rho_i Bbar_i, -BP2) == 1   over the items i presented under k,
+// again as 16 independent 8-bit combinations.  The host (job_form.hpp keyed_bv_plan) sorts the grouped items by key into the
+// BV ORDER: every group's run starts at a multiple of 4 (pad positions keep digit 0), and is cut into SEGMENTS of at most
+// PIP_TILE items.  Stages, all on the job's main stream:
+//   keyed_rlc_prep       : KeyedRlcPrep, RlcPrep's logic with the digits and the item-major points written at the item's
+//                          POSITION in the bv order; rho_i stays SHA-256(seed || i) of the ITEM index;
+//   keyed_pip_windows    : k_pip_window_seg, k_pip_window's algorithm with the tile taken from the segment table -- one
+//                          workgroup per (set, window, segment); host twin: PipGroupSumsHost, double-and-add per group;
+//   keyed_pip_group_sums : PipGroupSums, lane per (set, window, group): adds the group's segment sums and normalises into the
+//                          SoA arrays the group's 16 VIRTUAL items read (entry g * 16 + w of [2N][16 G] per set);
+//   keyed_rlc_pairing    : the existing keyed pairing step over the virtual items (virtual item g * 16 + w under group g's key);
+//   keyed_bv_decide      : KeyedBvDecide, lane per item: pending, grouped and all 16 verdicts of its group 1 -> Ok(true).
+// The per-item keyed pairing kernel follows and finds those items decided; the items of a group that failed, and the items
+// of keys below the threshold, get their own product as before.  A failing key costs its own group, not the batch.
+constexpr uint32_t BV_NONE = 0xFFFFFFFFu;     // pos_of_item / item_group of an item that belongs to no group
+
+template <class C>
+struct PipSegArgs {
+    size_t n_pos;             // positions of the bv order (a multiple of 4): length of a digit row and of a point set
+    int M, NW;
+    uint32_t n_segs, n_groups;
+    const uint32_t* segs;     // [n_segs][3] first position, items (<= PIP_TILE), group
+    const uint32_t* grp_seg;  // [n_groups][2] first segment, segments
+    const uint32_t* grp_run;  // [n_groups][2] first position (a multiple of 4), items
+    const uint32_t* ppts;     // [M][n_pos][2N] Montgomery affine, item-major, (0,0) = identity
+    const uint8_t* dig;       // [NW][n_pos]
+    uint32_t* seg_sums;       // [3N][M*NW*n_segs] Jacobian (SoA over the work units (m * NW + w) * n_segs + segment)
+    uint32_t* out;            // [M][2N][NW*n_groups] Montgomery affine: entry g * NW + w = window w of group g
+};
+
+template <class C>
+struct KeyedRlcPrepArgs {
+    RlcPrepArgs<C> r;             // n = items (stride of pa / pb), n_pad = n_pos, dig [16][n_pos], ppts [2][n_pos][2N]
+    const uint32_t* pos_of_item;  // [n] position in the bv order, BV_NONE: not grouped
+};
+template <class C>
+struct KeyedRlcPrep {
+    static __host__ __device__ void run(const KeyedRlcPrepArgs<C>& ka, size_t i) {
+        constexpr int N = C::FpP::N;
+        const RlcPrepArgs<C>& a = ka.r;
+        const uint32_t pos = ka.pos_of_item[i];
+        if (pos == BV_NONE) return;
+        uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        G1Aff<C> p = g1a_inf<C>(), q = g1a_inf<C>();
+        bool in = a.gate_arr[i] == (int8_t)a.gate;
+        if (in) {
+            if (a.canonical) {
+                p = g1a_load_canon_to_mont<C>(a.pa, a.n, i);
+                q = g1a_load_canon_to_mont<C>(a.pb, a.n, i);
+                in = g1a_on_curve<C>(p) && g1a_on_curve<C>(q);
+            } else {
+                p = g1a_load_mont<C>(a.pa, a.n, i);
+                q = g1a_load_mont<C>(a.pb, a.n, i);
+            }
+        }
+        if (in) {
+            Sha256 s;
+            sha256_init(s);
+            for (int k = 0; k < 8; k++) sha256_word(s, a.seed[k]);
+            sha256_u64be(s, (uint64_t)i);
+            sha256_final(s, h);
+        } else {
+            p = g1a_inf<C>(); q = g1a_inf<C>();
+        }
+        for (int w = 0; w < 16; w++) a.dig[(size_t)w * a.n_pad + pos] = (uint8_t)(h[w >> 2] >> (8 * (w & 3)));
+        g1a_store_mont<C>(a.ppts + (size_t)pos * 2 * N, 1, 0, p);
+        g1a_store_mont<C>(a.ppts + (a.n_pad + (size_t)pos) * 2 * N, 1, 0, q);
+    }
+};
+
+// host twin of k_pip_window_seg: lane per (set, window, group), sum of digit * P over the group's run by double-and-add --
+// slow and obviously right.  The sum goes to the group's first segment, the identity to its other segments.
+template <class C>
+struct PipGroupSumsHost {
+    static __host__ __device__ void run(const PipSegArgs<C>& a, size_t t) {
+        constexpr int N = C::FpP::N;
+        const size_t TU = (size_t)a.M * a.NW * a.n_segs;
+        const size_t g = t % a.n_groups, mw = t / a.n_groups;
+        const size_t w = mw % (size_t)a.NW, m = mw / (size_t)a.NW;
+        const uint32_t first = a.grp_run[2 * g], cnt = a.grp_run[2 * g + 1];
+        G1Jac<C> acc = g1j_inf<C>();
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint32_t d = a.dig[w * a.n_pos + first + k];
+            if (!d) continue;
+            const G1Aff<C> P = g1a_load_mont<C>(a.ppts + (m * a.n_pos + first + k) * 2 * N, 1, 0);
+            G1Jac<C> r = g1j_inf<C>();
+            for (int bit = PIP_C - 1; bit >= 0; bit--) {
+                r = g1j_dbl<C>(r);
+                if ((d >> bit) & 1u) r = g1j_add_aff<C>(r, P);
+            }
+            acc = g1j_add<C>(acc, r);
+        }
+        const uint32_t s0 = a.grp_seg[2 * g], ns = a.grp_seg[2 * g + 1];
+        for (uint32_t s = 0; s < ns; s++) g1j_store<C>(a.seg_sums, TU, mw * a.n_segs + s0 + s, s ? g1j_inf<C>() : acc);
+    }
+};
+
+// lane per (set, window, group): the group's segment sums added and normalised for the group's virtual item of that window
+template <class C>
+struct PipGroupSums {
+    static __host__ __device__ void run(const PipSegArgs<C>& a, size_t t) {
+        constexpr int N = C::FpP::N;
+        const size_t TU = (size_t)a.M * a.NW * a.n_segs, NV = (size_t)a.NW * a.n_groups;
+        const size_t g = t % a.n_groups, mw = t / a.n_groups;
+        const size_t w = mw % (size_t)a.NW, m = mw / (size_t)a.NW;
+        const uint32_t s0 = a.grp_seg[2 * g], ns = a.grp_seg[2 * g + 1];
+        G1Jac<C> acc = g1j_inf<C>();
+        for (uint32_t s = 0; s < ns; s++) acc = g1j_add<C>(acc, g1j_load<C>(a.seg_sums, TU, mw * a.n_segs + s0 + s));
+        g1a_store_mont<C>(a.out + m * 2 * N * NV, NV, g * (size_t)a.NW + w, g1j_to_aff<C>(acc));
+    }
+};
+
+// lane per item, behind the groups' 16 combined checks: a pending item of a group whose checks all passed is Ok(true)
+struct KeyedBvDecideArgs {
+    size_t n;
+    const uint32_t* item_group;   // [n] group of item i, BV_NONE: none
+    const int8_t* verdicts;       // [16 G] verdict of virtual item g * 16 + w (0: failed or never ran)
+    int8_t* status;
+};
+struct KeyedBvDecide {
+    static __host__ __device__ void run(const KeyedBvDecideArgs& a, size_t i) {
+        const uint32_t g = a.item_group[i];
+        if (g == BV_NONE || a.status[i] != ST_PAIRING) return;
+        bool all = true;
+        for (int w = 0; w < 16; w++) all &= a.verdicts[(size_t)g * 16 + w] == 1;
+        if (all) a.status[i] = 1;
+    }
+};
+
+#if !defined(BBS_HOST_TWIN)
+// k_pip_window with the tile taken from the segment table: one workgroup per (point set m, window w, segment); thread b owns
+// bucket b.  A segment starts at a multiple of 4 of its digit row (runs start at multiples of 4, PIP_TILE is one) and a row
+// is n_pos = a multiple of 4 long, so the 4-byte digit loads are aligned and stay inside the row.  Steps 1 - 4 are
+// k_pip_window's; step 5 always stores the segment's window sum Jacobian (PipGroupSums adds a group's segments).
+template <class C>
+__global__ void __launch_bounds__(PIP_WG) k_pip_window_seg(PipSegArgs<C> a) {
+    constexpr int N = C::FpP::N;
+    static_assert(PIP_TILE % 4 == 0, "a segment starts at a multiple of 4");
+    __shared__ __attribute__((aligned(16))) uint8_t s_dig[PIP_TILE];
+    __shared__ uint16_t s_list[PIP_TILE];
+    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_pt[4][3 * N];
+    const int b = (int)threadIdx.x, lane = b & 63, wv = b >> 6;
+    const size_t unit = blockIdx.x;                          // (m * NW + w) * n_segs + segment
+    const uint32_t seg = (uint32_t)(unit % (size_t)a.n_segs);
+    const size_t mw = unit / (size_t)a.n_segs;
+    const int w = (int)(mw % (size_t)a.NW), m = (int)(mw / (size_t)a.NW);
+    const size_t i0 = a.segs[3 * seg];
+    // (the host builds the table inside the order; a segment that is not ends at the row's end and is never longer than a tile)
+    size_t n_seg = a.segs[3 * seg + 1];
+    if (n_seg > (size_t)PIP_TILE) n_seg = PIP_TILE;
+    if (n_seg > (i0 < a.n_pos ? a.n_pos - i0 : 0)) n_seg = i0 < a.n_pos ? a.n_pos - i0 : 0;
+    const int n_t = (int)n_seg;
+    // 1. digits -> LDS: the 64-digit chunks the segment reaches into, zeros behind its last item
+    {
+        const uint8_t* row = a.dig + (size_t)w * a.n_pos + i0;
+        uint32_t* s32 = reinterpret_cast<uint32_t*>(s_dig);
+        for (int q = b; 4 * q < ((n_t + 63) & ~63); q += PIP_WG) {
+            uint32_t v = 0;
+            if (4 * q < n_t) {
+                v = *reinterpret_cast<const uint32_t*>(row + 4 * q);
+                const int rem = n_t - 4 * q;
+                if (rem < 4) v &= (1u << (8 * rem)) - 1u;
+            }
+            s32[q] = v;
+        }
+    }
+    __syncthreads();
+    const int n_chunks = (n_t + 63) >> 6;
+    auto members = [&](int q) -> uint64_t {
+        const uint32_t d = s_dig[q * 64 + lane];
+        uint64_t mk = ~(uint64_t)0;
+#pragma unroll
+        for (int j = 0; j < PIP_C; j++) {
+            const uint64_t bj = __ballot((d >> j) & 1u);
+            mk &= ((b >> j) & 1) ? bj : ~bj;
+        }
+        return b ? mk : (uint64_t)0;                         // digit 0 contributes nothing
+    };
+    // 2a. counts
+    uint32_t cnt = 0;
+    for (int q = 0; q < n_chunks; q++) cnt += (uint32_t)__popcll(members(q));
+    // 2b. exclusive scan of the 256 counts
+    uint32_t inc = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)inc, off, 64);
+        if (lane >= off) inc += v;
+    }
+    if (lane == 63) s_wave[wv] = inc;
+    __syncthreads();
+    uint32_t start = inc - cnt;
+    for (int k = 0; k < wv; k++) start += s_wave[k];
+    // 2c. fill (item order)
+    {
+        uint32_t pos = start;
+        for (int q = 0; q < n_chunks; q++) {
+            uint64_t mk = members(q);
+            while (mk) {
+                const int l = __ffsll((unsigned long long)mk) - 1;
+                mk &= mk - 1;
+                s_list[pos++] = (uint16_t)(q * 64 + l);
+            }
+        }
+    }
+    __syncthreads();
+    // 3. bucket sum
+    G1Jac<C> acc = g1j_inf<C>();
+    {
+        const uint32_t* pts = a.ppts + ((size_t)m * a.n_pos + i0) * (2 * N);
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint4* e = reinterpret_cast<const uint4*>(pts + (size_t)s_list[start + k] * (2 * N));
+            uint32_t wds[2 * N];
+            static_assert((2 * N) % 4 == 0, "a point is a whole number of 16-byte vectors");
+#pragma unroll
+            for (int v = 0; v < (2 * N) / 4; v++) { const uint4 t = e[v]; wds[4 * v] = t.x; wds[4 * v + 1] = t.y; wds[4 * v + 2] = t.z; wds[4 * v + 3] = t.w; }
+            G1Aff<C> pnt;
+#pragma unroll
+            for (int j = 0; j < N; j++) { pnt.x.v[j] = wds[j]; pnt.y.v[j] = wds[N + j]; }
+            acc = g1j_add_aff<C>(acc, pnt);
+        }
+    }
+    // 4a. suffix sums T_b = sum_{j >= b} B_j
+#pragma unroll 1
+    for (int off = 1; off < 64; off <<= 1) {
+        const G1Jac<C> o = g1j_shfl_down<C>(acc, off);
+        if (lane + off < 64) acc = g1j_add<C>(acc, o);
+    }
+    if (lane == 0) g1j_to_lds<C>(s_pt[wv], acc);
+    __syncthreads();
+    {
+        G1Jac<C> above = g1j_inf<C>();
+        for (int k = 3; k > wv; k--) above = g1j_add<C>(above, g1j_from_lds<C>(s_pt[k]));
+        acc = g1j_add<C>(acc, above);
+    }
+    __syncthreads();
+    // 4b. sum_{b >= 1} T_b
+    if (b == 0) acc = g1j_inf<C>();
+#pragma unroll 1
+    for (int off = 32; off >= 1; off >>= 1) {
+        const G1Jac<C> o = g1j_shfl_down<C>(acc, off);
+        if (lane < off) acc = g1j_add<C>(acc, o);
+    }
+    if (lane == 0) g1j_to_lds<C>(s_pt[wv], acc);
+    __syncthreads();
+    // 5. thread 0: the segment's window sum
+    if (b == 0) {
+        for (int k = 1; k < 4; k++) acc = g1j_add<C>(acc, g1j_from_lds<C>(s_pt[k]));
+        g1j_store<C>(a.seg_sums, (size_t)a.M * a.NW * a.n_segs, unit, acc);
+    }
+}
+#endif
 
 // generic digits for the unit-parity primitive: 256-bit canonical scalars -> 32 byte digits
 struct PipDigitArgs { size_t n, n_pad; const uint32_t* scal; /* [8][n] */ const int8_t* status; uint8_t* dig; /* [32][n_pad] */ };

@@ -726,20 +726,45 @@ struct Ctx : bbs_ctx {
         sha256_u64be(s, rlc_counter++);
         sha256_final(s, out8);
     }
+    // the context's secret seed: the caller's 32 bytes, or (NULL) the operating system's
+    int set_rlc_seed(const uint8_t* seed32) {
+        uint8_t buf[32];
+        if (seed32) std::memcpy(buf, seed32, 32);
+        else {
+            FILE* f = std::fopen("/dev/urandom", "rb");
+            const size_t got = f ? std::fread(buf, 1, 32, f) : 0;
+            if (f) std::fclose(f);
+            if (got != 32) return BBS_E_STATE;
+        }
+        for (int k = 0; k < 8; k++) rlc_seed[k] = le32(buf + 4 * k);
+        rlc_counter = 0;
+        return BBS_OK;
+    }
     int set_batch_verification(int enabled, const uint8_t* seed32) {
         if (enabled) {
-            uint8_t buf[32];
-            if (seed32) std::memcpy(buf, seed32, 32);
-            else {
-                FILE* f = std::fopen("/dev/urandom", "rb");
-                const size_t got = f ? std::fread(buf, 1, 32, f) : 0;
-                if (f) std::fclose(f);
-                if (got != 32) return BBS_E_STATE;
-            }
-            for (int k = 0; k < 8; k++) rlc_seed[k] = le32(buf + 4 * k);
-            rlc_counter = 0;
+            if (const int rc = set_rlc_seed(seed32)) return rc;
         }
         batch_verify = enabled != 0;
+        return BBS_OK;
+    }
+    // keyed batch verification (bbs_ctx_set_keyed_batch_verification; pippenger.hpp, job_form.hpp keyed_bv_plan): off by
+    // default, independent of batch_verify -- single-key jobs never look at it, keyed jobs never look at batch_verify.  A
+    // key forms a group in a job iff at least keyed_bv_min of the job's items name it.  The seed is the context's ONE seed
+    // (next_rlc_seed): enabling either switch sets it and restarts the counter.
+    // KEYED_BV_MIN_DEFAULT: measured (tools/keyed_bv_bench.py, profiles/keyed_bv_bench.json; DESIGN.md 8 has the table).  On the
+    // 4096-item loop the combination LOSES at 64 and at 128 items per key (the bucket kernel spends a 256-bucket suffix sum on
+    // every segment, however short) and wins for proof_verify at 256 items per key, the smallest size measured at which it
+    // does; verify is even there and wins at 4096.  Never below 17 -- a group of 16 or fewer items costs more pairing products
+    // combined than alone.
+    static constexpr size_t KEYED_BV_MIN_DEFAULT = 256;
+    bool keyed_bv = false;
+    size_t keyed_bv_min = KEYED_BV_MIN_DEFAULT;
+    int set_keyed_batch_verification(int enabled, const uint8_t* seed32, size_t min_items_per_key) {
+        if (enabled) {
+            if (const int rc = set_rlc_seed(seed32)) return rc;
+            keyed_bv_min = min_items_per_key ? min_items_per_key : KEYED_BV_MIN_DEFAULT;
+        }
+        keyed_bv = enabled != 0;
         return BBS_OK;
     }
 
@@ -1032,6 +1057,8 @@ struct bbs_job {
     virtual void set_result_targets(uint8_t*, uint8_t*, uint64_t*) {}
     virtual int set_octet_form() { return BBS_E_ARG; }    // sign / proof_gen: results leave as octet strings (before run)
     virtual size_t device_bytes() const { return 0; }     // device memory this job holds (allocation size classes)
+    // bbs_job_bv_report: set by a keyed job that formed groups (job_form.hpp add_keyed_bv_stages); no groups: zeros
+    std::function<int(uint32_t*, uint32_t*, uint32_t*)> bv_report;
     virtual int fetch_signatures(uint8_t*) { return BBS_E_ARG; }
     virtual int fetch_proofs(uint8_t*, uint8_t*, uint64_t*) { return BBS_E_ARG; }
     // One pass over the stages.  ev != nullptr: one event before the first stage, then a (start, stop) pair around
@@ -1345,6 +1372,18 @@ inline int launch_pip_windows(Stream& s, const PipCoopArgs<C>& a) {
     (void)&PipKernelEntry<C>::token;
     if (!units || !a.n) return 0;
     hipLaunchKernelGGL((k_pip_window<C>), dim3((unsigned)units), dim3(PIP_WG), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// the segmented form (keyed batch verification): used, and so instantiated, by the keyed translation units only
+template <class C> struct PipSegKernelEntry { static const int token; };
+template <class C> const int PipSegKernelEntry<C>::token = register_kernel(reinterpret_cast<const void*>(&k_pip_window_seg<C>));
+template <class C>
+inline int launch_pip_window_segs(Stream& s, const PipSegArgs<C>& a) {
+    const size_t units = (size_t)a.M * a.NW * a.n_segs;
+    (void)&PipSegKernelEntry<C>::token;
+    if (!units) return 0;
+    if (units > 0x7FFFFFFFull) return -1;
+    hipLaunchKernelGGL((k_pip_window_seg<C>), dim3((unsigned)units), dim3(PIP_WG), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace rt

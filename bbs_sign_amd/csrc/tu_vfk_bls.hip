@@ -1,3 +1,4 @@
 // explicit instantiation: keyed verify for BlsCurve (keyed.hpp; its own unit so that the build stays parallel)
 #include "op_vf.hpp"
 template int vf_upload<BlsCurve, true>(Ctx<BlsCurve>*, size_t, const VfIn&, bbs_job**);
+template int selftest_segmented_sums<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint8_t*, size_t, const uint64_t*, const uint64_t*, uint8_t*);

@@ -427,6 +427,35 @@ class Engine:
         self._chk(self.lib.bbs_ctx_set_batch_verification(self.h, 1 if enabled else 0, _u8(buf) if buf is not None else None),
                   "bbs_ctx_set_batch_verification")
 
+    def set_keyed_batch_verification(self, enabled: bool, seed: Optional[bytes] = None, min_items: int = 0):
+        """bbs_ctx_set_keyed_batch_verification: in the keyed verify / proof_verify jobs created afterwards, a key that at
+        least ``min_items`` of a job's items name (0: the library's default) is checked by 16 combined pairing products instead
+        of one product per item; same statuses.  seed=None draws the secret seed from the operating system."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        if min_items < 0:
+            raise ValueError("min_items must not be negative")
+        buf = _bytes_arr(seed) if seed is not None else None
+        self._chk(self.lib.bbs_ctx_set_keyed_batch_verification(self.h, 1 if enabled else 0, _u8(buf) if buf is not None else None,
+                                                                min_items), "bbs_ctx_set_keyed_batch_verification")
+
+    def segmented_sums(self, points, digits, groups):
+        """bbs_selftest_segmented_sums: ``points`` (affine pairs, None = the identity) in group order, ``digits`` as 16 rows of
+        len(points) bytes, ``groups`` as (first, count) pairs -> per group its 16 window sums (None = the identity)."""
+        n, G = len(points), len(groups)
+        pts = np.zeros(max(n, 1) * 2 * self.fpb, dtype=np.uint8)
+        for i, p in enumerate(points):
+            if p is not None:
+                pts[i * 2 * self.fpb:(i + 1) * 2 * self.fpb] = np.frombuffer(self._g1(p), dtype=np.uint8)
+        dg = np.ascontiguousarray(np.asarray(digits, dtype=np.uint8).reshape(16, n)) if n else np.zeros(16, dtype=np.uint8)
+        first = np.array([g[0] for g in groups] or [0], dtype=np.uint64)
+        count = np.array([g[1] for g in groups] or [0], dtype=np.uint64)
+        out = np.zeros(max(G, 1) * 16 * 2 * self.fpb, dtype=np.uint8)
+        self._chk(self.lib.bbs_selftest_segmented_sums(self.h, n, _u8(pts), _u8(dg), G, _u64(first), _u64(count), _u8(out)),
+                  "bbs_selftest_segmented_sums")
+        ob = out.tobytes()
+        return [[self._g1_dec(ob[(g * 16 + w) * 2 * self.fpb:(g * 16 + w + 1) * 2 * self.fpb]) for w in range(16)] for g in range(G)]
+
     def set_stage_timing(self, enabled: bool):
         """bbs_ctx_set_stage_timing: jobs created afterwards record HIP events around every stage (Job.stage_times)."""
         self._chk(self.lib.bbs_ctx_set_stage_timing(self.h, 1 if enabled else 0), "bbs_ctx_set_stage_timing")
@@ -1194,6 +1223,22 @@ class Job:
         cmo = np.zeros(self.n + 1, dtype=np.uint64)
         Engine._chk(self.eng.lib.bbs_job_fetch_proofs(self.h, _u8(pf), _u8(cm), _u64(cmo)), "bbs_job_fetch_proofs")
         return self.eng._dec_proofs(pf, cm, cmo, st, self.n), st
+
+    def bv_report(self):
+        """bbs_job_bv_report, after wait(): (groups formed, groups whose 16 combined checks all passed, items in groups) of a
+        keyed job under Engine.set_keyed_batch_verification; zeros for a job without groups."""
+        g, p, it = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        Engine._chk(self.eng.lib.bbs_job_bv_report(self.h, ctypes.byref(g), ctypes.byref(p), ctypes.byref(it)), "bbs_job_bv_report")
+        return g.value, p.value, it.value
+
+    def stage_names(self):
+        """bbs_job_stage_name of every stage of the job, in launch order."""
+        names = []
+        while True:
+            s = self.eng.lib.bbs_job_stage_name(self.h, len(names))
+            if s is None:
+                return names
+            names.append(s.decode())
 
     def run_timed(self, reps: int = 1, per_stage: bool = True):
         """-> (total_ms, {stage: ms}) measured with HIP events on the context's own stream."""

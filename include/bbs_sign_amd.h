@@ -268,6 +268,28 @@ int bbs_ctx_set_unit_lines(bbs_ctx* ctx, int enabled);
  * system; a caller-supplied seed must be secret and fresh.  Takes effect for jobs uploaded afterwards. */
 int bbs_ctx_set_batch_verification(bbs_ctx* ctx, int enabled, const uint8_t* seed32);
 
+/* Batch verification for the KEYED entry points, per issuer key (off by default; with it off nothing changes anywhere).
+ * Independent of bbs_ctx_set_batch_verification: single-key jobs never look at this switch and keyed jobs keep ignoring that
+ * one.  enabled = 1: in every keyed verify and proof_verify job created afterwards -- the eight bbs_*verify*_keyed_* exports:
+ * core and wire forms, _submit and _batch, both job forms -- a key that at least min_items_per_key of the job's items name
+ * forms a GROUP.  For the group of key k the library checks  e(sum rho_i Abar_i, W_k) e(sum rho_i Bbar_i, -BP2) == 1  (verify:
+ * A_i and e_i A_i - B_i) over the group's items that passed every earlier check, as 16 independent 8-bit combinations
+ * (rho_i from the secret seed and the item's index, as above), each one ordinary item of the keyed pairing kernel under key k.
+ * If all 16 pass, every such item of the group is true except with probability 2^-128; otherwise the group's items are
+ * decided one by one by the exact kernel, as are the items of keys below the threshold.  The statuses are therefore those of
+ * the switch-off job, and a failing key costs only its own group.
+ * min_items_per_key = 0: the library's default (256, the smallest group size at which the combination was measured to win:
+ * DESIGN.md 8); any value >= 1 is taken as given (groups below the default are slower combined than alone on the measured
+ * loop, and a group of 16 or fewer items costs more pairing products combined than alone: small values are for tests).
+ * seed32 as for bbs_ctx_set_batch_verification; the context has ONE seed: enabling either switch sets it.  A job draws its
+ * coefficients once, when it is created (as a job of bbs_ctx_set_batch_verification does): bbs_job_run again repeats the same
+ * combination, so the 2^-128 bound is per job, not per run -- an input that is to be checked afresh is uploaded afresh.
+ * Composes with bbs_ctx_set_keyed_mixed_lengths, subgroup vouching and both line-table forms.  Costs no stream and no hardware
+ * queue: everything runs on the job's main stream.  BBS_E_ARG for a NULL ctx.
+ * NOT covered: one combined check across keys; a narrower-window form for small groups; bbs_issuer and bbs_pool do not route
+ * through it; the C++ wrapper and the Rust shim do not expose the switch or the report. */
+int bbs_ctx_set_keyed_batch_verification(bbs_ctx* ctx, int enabled, const uint8_t* seed32, size_t min_items_per_key);
+
 /* generators = [Q1, H_1 .. H_L] (count = L+1 affine G1 points) and the api_id they belong to:
  * the `generators: &[E::G1]` and `api_id: &[u8]` arguments of every reference core_* function
  * (src/sign.rs:63-69, src/verify.rs:53-60, src/proof_gen.rs:116-125, src/proof_verify.rs:64-73). */
@@ -707,6 +729,12 @@ void bbs_job_free(bbs_job* job);
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int kernel_cap,
                       int* n_stages_out);
 const char* bbs_job_stage_name(const bbs_job* job, int stage);
+/* Keyed batch verification (bbs_ctx_set_keyed_batch_verification), after bbs_job_wait: the groups the job formed, the groups whose
+ * 16 combined checks all passed in the last run (the verdict flags are read back from the device by this call), and the items
+ * that belong to a group.  Zeros for a job without groups.  It tells the combined path from the per-item one; the stages of the
+ * combined path are keyed_rlc_prep, keyed_pip_windows, keyed_pip_group_sums, keyed_rlc_pairing and keyed_bv_decide
+ * (bbs_job_stage_name).  BBS_E_ARG for a NULL argument. */
+int bbs_job_bv_report(bbs_job* job, uint32_t* groups, uint32_t* groups_passed, uint32_t* items_in_groups);
 /* Throughput form: `njobs` device-resident batches in flight, step k runs on jobs[k % njobs] (every
  * job owns a HIP stream pair, so independent batches overlap on the GPU).  total_ms = first event to
  * the latest last-stage event; kernel_ms[s] = sum over all steps of stage s's own duration. */
@@ -930,6 +958,16 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
                              const uint8_t* pk_octets, int path, uint8_t* entries_out, int8_t* status_out,
                              uint8_t* pk_affine_out);
 size_t bbs_selftest_key_entry_bytes(int curve);
+/* Keyed batch verification self-test: the segmented bucket kernel and the group sums alone (stages keyed_pip_windows and
+ * keyed_pip_group_sums).  n affine G1 points (2 * fp_bytes each, canonical LE, zeros = the identity) given in group order,
+ * digits[w * n + i] = the 8-bit coefficient of point i in window w (16 windows), and n_groups groups, group g = the points
+ * group_first[g] .. group_first[g] + group_count[g] - 1.  out_affine[(g * 16 + w) * 2 * fp_bytes ..] = sum_i digits[w][i] * P_i
+ * over group g (zeros = the identity).  The product library runs the device kernel, one workgroup per (window, segment of at
+ * most 4096 points); the host twin its plain double-and-add twin.  BBS_E_ARG for a point that is not canonical or not on the
+ * curve, or a group that reaches past n.  Needs no generators and no key. */
+int bbs_selftest_segmented_sums(bbs_ctx* ctx, size_t n, const uint8_t* points_affine, const uint8_t* digits /* [16][n] */,
+                                size_t n_groups, const uint64_t* group_first, const uint64_t* group_count,
+                                uint8_t* out_affine /* [n_groups][16] */);
 /* GPU self-test: one Fp12 operation per item (12 Fp values a, b per item, canonical LE, tower order) computed by the
  * one-lane code (on the host) and by the six-lane wavefront-cooperative code; the caller compares the outputs.
  * op: 0 mul, 1..3 Frobenius^k, 4 inverse, 5 conjugate, 6 line multiplication (the point is (b[0], b[1]), any pair of field
