@@ -66,6 +66,7 @@ SIGNATURES = {
     "bbs_ctx_set_fixed_base_tree": (ci, [vp, ci]),
     "bbs_ctx_set_mixed_lengths": (ci, [vp, ci]),
     "bbs_ctx_set_mixed_lengths_gen": (ci, [vp, ci]),
+    "bbs_ctx_set_seeded_random_scalars": (ci, [vp, ci, c_u8p, sz]),
     "bbs_ctx_set_keyed_mixed_lengths": (ci, [vp, ci]),
     "bbs_ctx_set_unit_lines": (ci, [vp, ci]),
     # keyed batch verification: the switch, the report of a job, the segmented sums alone
@@ -192,6 +193,7 @@ SIGNATURES = {
     "bbs_ctx_set_stage_timing": (ci, [vp, ci]),
     "bbs_job_stage_times": (ci, [vp, c_f32p, c_f32p, ci, ctypes.POINTER(ci)]),
     "bbs_hash_to_scalar_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u8p, sz, c_u8p]),
+    "bbs_seeded_random_scalars_batch": (ci, [vp, sz, c_u8p, c_u64p, c_u32p, c_u8p, sz, c_u8p, c_i8p]),
     "bbs_g1_msm_batch": (ci, [vp, sz, c_u8p, sz, c_u8p, c_u8p, sz, c_u8p, c_i8p]),
     "bbs_g1_msm_pippenger": (ci, [vp, sz, c_u8p, c_u8p, c_u8p, ctypes.POINTER(ci), c_i8p]),
     "bbs_pairing_product2_is_one_batch": (ci, [vp, sz, c_u8p, c_u8p, c_i8p]),

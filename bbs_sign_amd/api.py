@@ -312,16 +312,29 @@ def sign_many(sk: SecretKey, items: Sequence[tuple]) -> list:
     return [BbsError(int(s)) if s < 0 else octets_to_signature(sk.curve, o, sk.lib_path) for o, s in zip(octs, st)]
 
 
-def proof_gen_many(pk: PublicKey, items: Sequence[tuple]) -> list:
+def _device_draw(eng: Engine, curve: str, call):
+    """``call(job_seed)`` with bbs_ctx_set_seeded_random_scalars on for its duration: ONE fresh 32-byte job seed from the
+    operating system per device call (a seed never serves two jobs), DST = api_id || "SEEDED_RANDOM_SCALARS_"."""
+    eng.set_seeded_random_scalars(True, api_id(curve) + b"SEEDED_RANDOM_SCALARS_")
+    try:
+        return call(secrets.token_bytes(32))
+    finally:
+        eng.set_seeded_random_scalars(False)
+
+
+def proof_gen_many(pk: PublicKey, items: Sequence[tuple], device_random: bool = False) -> list:
     """proof_gen for many items ``(signature, header, ph, messages, disclosed_indexes[, random_scalars])`` of any message
     counts, in ONE device call, as sign_many.  Entry i is the Proof ``proof_gen(pk, *items[i])`` returns with the same random
     scalars (drawn here, as there, where an item has none), or the BbsError it raises (returned, not raised).  A wrong number of
-    random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as it fails the one-item call."""
+    random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as it fails the one-item call.
+    ``device_random=True``: when NO item gives scalars of its own, the scalars are drawn on the device from one fresh job seed
+    (bbs_ctx_set_seeded_random_scalars) instead of one by one here; a list in which an item brings its own is served as before."""
     if not items:
         return []
     eng = _mixed_gen_engine(pk, max(len(it[3]) for it in items))
-    rnds = [list(it[5]) if len(it) > 5 and it[5] is not None else
-            calculate_random_scalars(pk.curve, max(5 + len(it[3]) - len(it[4]), 0)) for it in items]
+    on_device = device_random and not any(len(it) > 5 and it[5] is not None for it in items)
+    rnds = [] if on_device else [list(it[5]) if len(it) > 5 and it[5] is not None else
+                                 calculate_random_scalars(pk.curve, max(5 + len(it[3]) - len(it[4]), 0)) for it in items]
     out: list = [None] * len(items)
     octs, idx = [], []
     for i, it in enumerate(items):
@@ -332,8 +345,9 @@ def proof_gen_many(pk: PublicKey, items: Sequence[tuple]) -> list:
             out[i] = e
     if idx:
         its = [items[i] for i in idx]
-        po, st = eng.proof_gen_wire_batch(octs, [list(it[3]) for it in its], [list(it[4]) for it in its], [rnds[i] for i in idx],
-                                          [it[1] for it in its], [it[2] for it in its])
+        def call(r):
+            return eng.proof_gen_wire_batch(octs, [list(it[3]) for it in its], [list(it[4]) for it in its], r, [it[1] for it in its], [it[2] for it in its])
+        po, st = _device_draw(eng, pk.curve, call) if on_device else call([rnds[i] for i in idx])
         for i, o, s in zip(idx, po, st):
             out[i] = BbsError(int(s)) if s < 0 else octets_to_proof(pk.curve, o, pk.lib_path)
     return out
@@ -490,15 +504,18 @@ def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool =
                          batch_verification)
 
 
-def proof_gen_many_issuers(items: Sequence[tuple]) -> list:
+def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) -> list:
     """proof_gen for many items ``(pk, signature, header, ph, messages, disclosed_indexes[, random_scalars])`` of ANY issuers
     and ANY message counts, in ONE device call per (curve, device, lib_path): the cached engine of verify_many_issuers (its
     keys are registered once, whichever side meets them first), through bbs_proof_gen_wire_keyed_batch.  Entry i is the Proof
     ``proof_gen(*items[i])`` returns with the same random scalars (drawn here, as there, where an item has none), or the
     BbsError it raises (returned, not raised: the other items stand).  A signature that cannot be written as octets keeps the
     codec's error; a wrong number of random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as in
-    proof_gen_many; a ``pk`` the library refuses gives ``BbsError(-44)``, the divergence verify_many_issuers describes."""
+    proof_gen_many; a ``pk`` the library refuses gives ``BbsError(-44)``, the divergence verify_many_issuers describes.
+    ``device_random=True``: as proof_gen_many -- when no item gives scalars of its own they are drawn on the device, from one
+    fresh job seed per device call."""
     out: list = [None] * len(items)
+    on_device = device_random and not any(len(it) > 6 and it[6] is not None for it in items)
     groups: Dict[tuple, List[int]] = {}
     for i, it in enumerate(items):
         groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
@@ -514,10 +531,14 @@ def proof_gen_many_issuers(items: Sequence[tuple]) -> list:
         if not idx:
             continue
         its = [items[i] for i in idx]
-        rnds = [list(it[6]) if len(it) > 6 and it[6] is not None else
-                calculate_random_scalars(curve, max(5 + len(it[4]) - len(it[5]), 0)) for it in its]
-        po, st = ie.eng.proof_gen_wire_keyed_batch([ie.index[ie.name(it[0].pk)] for it in its], octs, [list(it[4]) for it in its],
-                                                   [list(it[5]) for it in its], rnds, [it[2] for it in its], [it[3] for it in its])
+        def call(r, ie=ie, its=its, octs=octs):
+            return ie.eng.proof_gen_wire_keyed_batch([ie.index[ie.name(it[0].pk)] for it in its], octs, [list(it[4]) for it in its],
+                                                     [list(it[5]) for it in its], r, [it[2] for it in its], [it[3] for it in its])
+        if on_device:
+            po, st = _device_draw(ie.eng, curve, call)
+        else:
+            po, st = call([list(it[6]) if len(it) > 6 and it[6] is not None else
+                           calculate_random_scalars(curve, max(5 + len(it[4]) - len(it[5]), 0)) for it in its])
         for i, o, s in zip(idx, po, st):
             out[i] = BbsError(int(s)) if s < 0 else octets_to_proof(curve, o, lib_path)
     return out

@@ -486,6 +486,14 @@ int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_mixed_lengths_gen(enabled); });
 }
+int bbs_ctx_set_seeded_random_scalars(bbs_ctx* ctx, int enabled, const uint8_t* dst, size_t dst_len) {
+    if (!ctx || (dst_len && !dst)) return BBS_E_ARG;
+    with_curve(ctx, [&](auto* c) {
+        c->seeded_rnd = enabled != 0;
+        if (c->seeded_rnd) c->seeded_dst.assign(dst, dst + dst_len); else c->seeded_dst.clear();
+    });
+    return BBS_OK;
+}
 int bbs_ctx_set_keyed_mixed_lengths(bbs_ctx* ctx, int enabled) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return c->set_keyed_mixed_lengths(enabled); });
@@ -1021,6 +1029,12 @@ int bbs_core_proof_gen_batch(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const 
 int bbs_hash_to_scalar_batch(bbs_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* off, const uint8_t* dst, size_t dst_len, uint8_t* out) {
     if (!ctx) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return h2s_batch(c, n, msgs, off, dst, dst_len, out); });
+}
+
+int bbs_seeded_random_scalars_batch(bbs_ctx* ctx, size_t n, const uint8_t* seeds, const uint64_t* seed_off, const uint32_t* counts,
+                                    const uint8_t* dst, size_t dst_len, uint8_t* out, int8_t* status) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return seeded_scalars_batch(c, n, seeds, seed_off, counts, dst, dst_len, out, status); });
 }
 
 int bbs_g1_msm_batch(bbs_ctx* ctx, size_t n, const uint8_t* fs, size_t nf, const uint8_t* vp, const uint8_t* vs, size_t nv, uint8_t* out, int8_t* status) {

@@ -12,6 +12,7 @@ struct PgJob : JobBase<C> {
     VfOctArgs<C> oct{};               // signature octets in (wire form) only
     MsgHashArgs mh{};                 // raw-message form only
     JobForm<C> jf{};                  // the job's form (job_form.hpp)
+    PgDrawArgs<C> draw{};             // seeded random scalars only (bbs_ctx_set_seeded_random_scalars)
     // The proofs come off the device in the caller's layout (stage PgEmit): records, the m^ of the undisclosed messages
     // in ascending index order (L slots per item, the first ucount[i] used) and those counts.  Host side of a delivery:
     // one copy of the records, one contiguous copy per item of its commitments, the running offsets.
@@ -100,7 +101,10 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     Form form;
     if (const int rcf = decide_form<KEYED>(ctx, FormOp::ProofGen, n, in.key_index, form)) return rcf;
     const bool wire = in.signature_octets != nullptr, raw = in.msg_byte_off != nullptr;
-    if (!out || (n && ((!in.signatures && !wire) || !in.msg_off || !in.didx_off || !in.rnd_off || !in.random_scalars))) return BBS_E_ARG;
+    // SEEDED (bbs_ctx_set_seeded_random_scalars): random_scalars / rnd_off are seeds -- bytes per item, or with rnd_off == nullptr
+    // one 32-byte job seed -- and the scalars are drawn on the device in front of the ingest stage (stages_draw.hpp PgDraw)
+    const bool seeded = ctx->seeded_rnd, job_seed = seeded && !in.rnd_off;
+    if (!out || (n && ((!in.signatures && !wire) || !in.msg_off || !in.didx_off || (!seeded && !in.rnd_off) || (!in.random_scalars && !(seeded && in.rnd_off))))) return BBS_E_ARG;
     const uint8_t* sigs = wire ? in.signature_octets : in.signatures;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
@@ -111,7 +115,14 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     RaggedIn ms{in.msg_off, in.messages, 32}, di{in.didx_off, reinterpret_cast<const uint8_t*>(in.disclosed_idx), 8}, rs{in.rnd_off, in.random_scalars, 32},
              hb{in.hdr_off, in.headers, 1}, pb{in.ph_off, in.ph, 1};
     ms.offsets_only = raw;
+    // seeded: rs becomes the offsets of the scalars that will be drawn (computed below, no data behind them) and sd the seeds.
+    // A job seed travels as a section whose data are its 32 bytes; its offsets {0, .., 0, 32} only size it and are not read.
+    RaggedIn sd{in.rnd_off, in.random_scalars, 1};
+    std::vector<uint64_t> sc_off, js_off;
+    if (job_seed) { js_off.assign(n + 1, 0); js_off[n] = n ? 32 : 0; sd.off = js_off.data(); }
+    if (seeded) { rs = RaggedIn{nullptr, nullptr, 32}; rs.offsets_only = true; }
     if (!ms.measure(n) || !di.measure(n) || !rs.measure(n) || !hb.measure(n) || !pb.measure(n)) return BBS_E_ARG;
+    if (seeded && (!sd.measure(n) || sd.total > 0xF0000000ull)) return BBS_E_ARG;
     RaggedIn mb{};
     size_t nm;
     if (!raw_message_section(ms, in.msg_byte_off, in.msg_bytes, mb, nm)) return BBS_E_ARG;
@@ -120,7 +131,7 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     // scalars (proof_gen.rs:145-149; checked where the reference would have got that far).  Everything else -- the
     // reference's checks, range checks, deduplication, unpacking, SoA transposition, and the layout of the results
     // (stage PgEmit) -- happens on the device.
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < n && !seeded; i++) {
         const size_t l = (size_t)(in.msg_off[i + 1] - in.msg_off[i]);
         const size_t r = (size_t)(in.didx_off[i + 1] - in.didx_off[i]);
         const size_t nr = (size_t)(in.rnd_off[i + 1] - in.rnd_off[i]);
@@ -131,10 +142,25 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
         if (bad) continue;                                            // -> InvalidDisclosedIndex
         if (nr != 5 + l - r) return BBS_E_ARG;
     }
+    if (seeded) {
+        // room for 5 + l - r scalars for every item that the two checks above let through, in the order PgDraw applies them.
+        // An item that PgDraw refuses (-23, -24) or that is decided elsewhere keeps its room: PgIngest may read it (never
+        // written, any content) before PgDrawGate or KeyGate overrides what it made of it.
+        sc_off.assign(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t l = in.msg_off[i + 1] - in.msg_off[i], r = in.didx_off[i + 1] - in.didx_off[i];
+            bool draws = r <= l;
+            for (uint64_t k = 0; draws && k < r; k++) draws = in.disclosed_idx[in.didx_off[i] + k] < l;
+            sc_off[i + 1] = sc_off[i] + (draws ? 5 + l - r : 0);
+        }
+        rs.off = sc_off.data();
+        if (!rs.measure(n)) return BBS_E_ARG;
+    }
     std::vector<uint32_t> kwords;     // keyed: the key indexes, in the staging image
     size_t kwords_at = 0;
     if constexpr (KEYED) keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
-    if (int rc0 = stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
+    if (int rc0 = seeded ? stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb, &sd}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)
+                         : stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
     if constexpr (KEYED) keyed_bind<C>(job->jf, reinterpret_cast<const uint32_t*>(dimg + kwords_at));
     auto d64 = [&](size_t at) { return reinterpret_cast<const uint64_t*>(dimg + at); };
@@ -171,6 +197,22 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     if (raw) {
         ia.m = hash_raw_messages<C>(job.get(), ctx, mb, nm, job->mh, ia.msg_dst_too_long, rc);
         if (rc) return rc;
+    }
+    if (seeded) {
+        PgDrawArgs<C>& da = job->draw;
+        uint32_t* drawn = job->template scratch<uint32_t>(std::max<size_t>((size_t)rs.total, 1) * 8, rc);
+        da.dcode = job->template scratch<int8_t>(nn, rc);
+        if (rc) return rc;
+        da.n = n; da.oct = ia.oct; da.pcode = ia.pcode; da.msg_dst_too_long = ia.msg_dst_too_long;
+        da.kidx = nullptr;
+        if constexpr (KEYED) da.kidx = job->jf.src.kidx;
+        da.m_off = ia.m_off; da.di_off = ia.di_off; da.di = ia.di;
+        da.seeds = dimg + sd.at_data; da.seed_off = d64(sd.at_off); da.job_seed = job_seed ? 1 : 0;
+        da.dst_too_long = ctx->seeded_dst.size() > 255 ? 1 : 0;
+        draw_dst_build(da.d, ctx->seeded_dst.data(), ctx->seeded_dst.size());
+        da.sc_off = ia.rnd_off; da.out = drawn;
+        ia.rnd = drawn;
+        if (rt::launch<PgDraw<C>>(job->stream(), da, n)) return BBS_E_HIP;
     }
     ia.hdr_off = offs; ia.hdr_len = offs + nn; ia.ph_off = offs + 2 * nn; ia.ph_len = offs + 3 * nn;
     a.sig_a = ia.sig_a; a.sig_e = ia.sig_e; a.msgs = ia.msgs; a.dmask = ia.dmask; a.didx = ia.didx; a.rcount = ia.rcount;
@@ -213,6 +255,7 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     ia.status0 = job->d_status0.template as<int8_t>();
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
     if ((rc = launch_ingest<PgIngest<C>, PgIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
+    if (seeded && rt::launch<PgDrawGate>(job->stream(), PgDrawGateArgs{n, job->draw.dcode, ia.status0}, n)) return BBS_E_HIP;
     if constexpr (KEYED) {
         if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, ia.status0))) return rc;
     }

@@ -94,6 +94,47 @@ int h2s_batch(Ctx<C>* ctx, size_t n, const uint8_t* msgs, const uint64_t* off, c
     for (size_t i = 0; i < n; i++) unpack_words_le(w, n, 0, i, 8, out + i * 32);
     return BBS_OK;
 }
+// seeded_random_scalars of n seeds (stages_draw.hpp DrawItem: the body of proof_gen's stage PgDraw).  On the device the items
+// that draw are packed; the caller's array is packed by counts, refused items included (zeros).
+template <class C>
+int seeded_scalars_batch(Ctx<C>* ctx, size_t n, const uint8_t* seeds, const uint64_t* seed_off, const uint32_t* counts, const uint8_t* dst,
+                         size_t dst_len, uint8_t* out, int8_t* status) {
+    if ((dst_len && !dst) || (n && (!seed_off || !counts || !out || !status))) return BBS_E_ARG;
+    if (!n) return BBS_OK;
+    const bool too_long = dst_len > 255;
+    std::vector<uint64_t> so(n + 1), oo(n + 1);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (counts[i] == 0 || seed_off[i + 1] < seed_off[i]) return BBS_E_ARG;
+        so[i] = seed_off[i] - seed_off[0];
+        oo[i] = total;
+        if (!too_long && counts[i] <= DRAW_MAX_COUNT) total += counts[i];
+    }
+    so[n] = seed_off[n] - seed_off[0];
+    oo[n] = total;
+    if (so[n] > 0xF0000000ull || (so[n] && !seeds)) return BBS_E_ARG;
+    if (ctx->use()) return BBS_E_HIP;
+    DevBuf d_seeds, d_so, d_oo, d_cnt, d_out, d_st;
+    if (d_seeds.alloc((size_t)so[n] + 4) || d_so.alloc((n + 1) * 8) || d_oo.alloc((n + 1) * 8) || d_cnt.alloc(n * 4) ||
+        d_out.alloc((size_t)total * 32 + 4) || d_st.alloc(n)) return BBS_E_NOMEM;
+    if (rt::h2d(d_seeds.p, seeds + seed_off[0], (size_t)so[n], ctx->stream) || rt::h2d(d_so.p, so.data(), (n + 1) * 8, ctx->stream) ||
+        rt::h2d(d_oo.p, oo.data(), (n + 1) * 8, ctx->stream) || rt::h2d(d_cnt.p, counts, n * 4, ctx->stream)) return BBS_E_HIP;
+    DrawArgs a;
+    a.n = n; a.seeds = d_seeds.as<uint8_t>(); a.seed_off = d_so.as<uint64_t>(); a.counts = d_cnt.as<uint32_t>(); a.out_off = d_oo.as<uint64_t>();
+    a.dst_too_long = too_long ? 1 : 0;
+    draw_dst_build(a.d, dst, dst_len);
+    a.out = d_out.as<uint32_t>(); a.status = d_st.as<int8_t>();
+    if (rt::launch<DrawItem<C>>(ctx->stream, a, n) || rt::sync(ctx->stream)) return BBS_E_HIP;
+    std::vector<uint8_t> w((size_t)total * 32);
+    if (rt::d2h(w.data(), d_out.p, w.size(), ctx->stream) || rt::d2h(status, d_st.p, n, ctx->stream)) return BBS_E_HIP;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {           // (a little-endian host: the words are the bytes)
+        const size_t nb = (size_t)counts[i] * 32;
+        if (oo[i + 1] > oo[i]) std::memcpy(out + at, w.data() + oo[i] * 32, nb); else std::memset(out + at, 0, nb);
+        at += nb;
+    }
+    return BBS_OK;
+}
 template <class C>
 int msm_batch(Ctx<C>* ctx, size_t n, const uint8_t* fs, size_t nf, const uint8_t* vp, const uint8_t* vs, size_t nv,
                      uint8_t* out, int8_t* status) {

@@ -74,6 +74,7 @@ template <class C, bool KEYED = false> int vf_upload(Ctx<C>*, size_t, const VfIn
 template <class C, bool KEYED = false> int sg_upload(Ctx<C>*, size_t, const SgIn&, bbs_job**);
 template <class C, bool KEYED = false> int pg_upload(Ctx<C>*, size_t, const PgIn&, bbs_job**);
 template <class C> int h2s_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
+template <class C> int seeded_scalars_batch(Ctx<C>*, size_t, const uint8_t*, const uint64_t*, const uint32_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 template <class C> int msm_batch(Ctx<C>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 template <class C> int selftest_f12(Ctx<C>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 template <class C> int selftest_f12_batch(Ctx<C>*, int, size_t, const uint8_t*, const uint8_t*, const int8_t*, int, int, uint8_t*, uint8_t*, int8_t*);
@@ -101,6 +102,7 @@ extern template int pg_upload<BnCurve>(Ctx<BnCurve>*, size_t, const PgIn&, bbs_j
 extern template int pg_upload<BnCurve, true>(Ctx<BnCurve>*, size_t, const PgIn&, bbs_job**);
 extern template int Ctx<BlsCurve>::set_generators(const uint8_t*, size_t, const uint8_t*, size_t);
 extern template int h2s_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
+extern template int seeded_scalars_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint64_t*, const uint32_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 extern template int msm_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 extern template int pairing_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint8_t*, int8_t*);
 extern template int msm_pippenger<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint8_t*, uint8_t*, int*, int8_t*);
@@ -109,6 +111,7 @@ extern template int signatures_from_octets_batch<BlsCurve>(Ctx<BlsCurve>*, size_
 extern template int proofs_from_octets_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint64_t*, uint8_t*, uint8_t*, uint64_t*, int8_t*);
 extern template int Ctx<BnCurve>::set_generators(const uint8_t*, size_t, const uint8_t*, size_t);
 extern template int h2s_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*);
+extern template int seeded_scalars_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, const uint32_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 extern template int msm_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 extern template int pairing_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, int8_t*);
 extern template int msm_pippenger<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, uint8_t*, int*, int8_t*);

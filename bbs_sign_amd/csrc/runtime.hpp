@@ -678,6 +678,10 @@ struct Ctx : bbs_ctx {
     // key: set_secret_key derives sk * BP2 and goes through set_pk_internal, so rebuild_hash sees pk_set on the signing side too.)
     bool mixed_lengths_gen = false;
     bool any_mixed_lengths() const { return mixed_lengths || mixed_lengths_gen; }
+    // bbs_ctx_set_seeded_random_scalars: proof_gen jobs created while it is on read random_scalars / rnd_off as seeds and draw
+    // on the device (stages_draw.hpp PgDraw) under this DST, kept as given (more than 255 bytes: every draw is refused)
+    bool seeded_rnd = false;
+    std::vector<uint8_t> seeded_dst;
     struct LenSet { DevBuf d; };     // [L + 1] HashCtx
     std::vector<HashCtx> len_hash;   // host mirror; empty unless one of the two switches is on and generators and key are set
     std::shared_ptr<const LenSet> len_set;      // null: to be uploaded from len_hash
@@ -793,7 +797,8 @@ struct Ctx : bbs_ctx {
 
     int use() { return rt::set_device(device) ? BBS_E_HIP : BBS_OK; }
     size_t table_bytes() const {
-        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (any_mixed_lengths() ? len_hash.size() * sizeof(HashCtx) : 0) + key_lens_bytes();
+        return d_tables.bytes + d_winbase.bytes + d_bases.bytes + d_consts.bytes + (any_mixed_lengths() ? len_hash.size() * sizeof(HashCtx) : 0) + key_lens_bytes() +
+               seeded_dst.size();
     }
 
     // domain prefix:  Z_pad || compress(pk) || I2OSP(L,8) || compress(Q1) || compress(H_i).. || api_id

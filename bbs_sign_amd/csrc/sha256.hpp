@@ -18,7 +18,8 @@ struct Sha256 {
 
 BBS_HD uint32_t rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 
-BBS_HD_NOINLINE void sha256_compress(uint32_t* h, const uint32_t* blk) {
+// (the body; sha256_compress below is the one out-of-line copy every streaming caller shares)
+BBS_HD void sha256_compress_body(uint32_t* h, const uint32_t* blk) {
     const uint32_t K[64] = {
         0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
         0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
@@ -50,6 +51,7 @@ BBS_HD_NOINLINE void sha256_compress(uint32_t* h, const uint32_t* blk) {
     }
     h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
 }
+BBS_HD_NOINLINE void sha256_compress(uint32_t* h, const uint32_t* blk) { sha256_compress_body(h, blk); }
 
 BBS_HD void sha256_init(Sha256& s) {
     const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
@@ -195,6 +197,63 @@ BBS_HD_NOINLINE void xmd48_finish(Sha256& s, const uint8_t* dst, uint32_t dst_le
     for (int i = 0; i < 8; i++) out12[i] = b1[i];
 #pragma unroll
     for (int i = 0; i < 4; i++) out12[8 + i] = b2[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// expand_message_xmd for any len_in_bytes with ell = ceil(len / 32) <= 255 and any DST of up to 255 bytes
+// (utilities_helper.rs:42-97), STREAMING: no output buffer, every finished b_i is handed to the caller.
+// Usage: xmd_begin(s) ; absorb msg bytes into s ; xmd_b0(s, len, dst, dst_len, b0) ; b = 0 ;
+//        for i = 1 .. ell: xmd_next(tail, b0, b, i)       -- b is b_i afterwards, 32 uniform bytes as 8 big-endian words
+// Every b_i with i >= 1 hashes 32 bytes || I2OSP(i, 1) || DST' : 34 + dst_len bytes whose last 2 + dst_len and whose padding do
+// not depend on the item.  XmdTail holds them as finished blocks (at most five), built once per job on the host
+// (xmd_tail_build) and read from the kernel's arguments: a b_i costs nblk compressions and no byte is shuffled for it.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t XMD_MAX_ELL = 255;
+BBS_HD uint32_t xmd_ell(uint32_t len_in_bytes) { return (len_in_bytes + 31) / 32; }
+
+struct XmdTail {
+    uint32_t w[5][16];      // the padded message 0^32 || I2OSP(0, 1) || dst || I2OSP(dst_len, 1) as big-endian words
+    uint32_t nblk;          // blocks of it: ceil((34 + dst_len + 9) / 64)
+};
+// dst_len <= 255
+inline void xmd_tail_build(XmdTail& t, const uint8_t* dst, uint32_t dst_len) {
+    for (int k = 0; k < 5; k++) for (int j = 0; j < 16; j++) t.w[k][j] = 0;
+    const uint32_t total = 34 + dst_len;
+    auto put = [&t](uint32_t pos, uint32_t b) { t.w[pos >> 6][(pos >> 2) & 15] |= b << ((3 - (pos & 3)) * 8); };
+    for (uint32_t k = 0; k < dst_len; k++) put(33 + k, dst[k]);
+    put(33 + dst_len, dst_len);
+    put(total, 0x80);
+    t.nblk = (total + 9 + 63) / 64;
+    t.w[t.nblk - 1][15] = total * 8;
+}
+
+BBS_HD void xmd_begin(Sha256& s) { xmd48_begin(s); }
+
+// b_0 = H(Z_pad || msg || I2OSP(len_in_bytes, 2) || I2OSP(0, 1) || DST')
+BBS_HD_NOINLINE void xmd_b0(Sha256& s, uint32_t len_in_bytes, const uint8_t* dst, uint32_t dst_len, uint32_t* b0) {
+    sha256_byte(s, (len_in_bytes >> 8) & 0xff); sha256_byte(s, len_in_bytes & 0xff); sha256_byte(s, 0);
+    xmd_dst_prime(s, dst, dst_len);
+    sha256_final(s, b0);
+}
+
+// b = b_{i-1} in (all zero for i = 1: b_1 hashes b_0 itself), b_i out.  Reached with lanes of a wavefront at different trip
+// counts: the compression function is INLINED here, at one place (g1.hpp g1_mul_aff_naf on calls from several divergent
+// places), so that the state and the block stay in registers: the chain is one lane's serial work and its latency is the stage's.
+BBS_HD void xmd_next(const XmdTail& t, const uint32_t* b0, uint32_t* b, uint32_t i) {
+    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    for (uint32_t k = 0; k < t.nblk; k++) {
+        uint32_t w[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) w[j] = t.w[k][j];
+        if (k == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) w[j] = b0[j] ^ b[j];
+            w[8] |= i << 24;
+        }
+        sha256_compress_body(h, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) b[j] = h[j];
 }
 
 // 48 big-endian bytes (12 BE words) -> scalar mod r, Montgomery form

@@ -30,4 +30,5 @@
 #include "stages_vf.hpp"
 #include "stages_sg.hpp"
 #include "stages_pg.hpp"
+#include "stages_draw.hpp"
 #include "stages_prim.hpp"

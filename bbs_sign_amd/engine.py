@@ -85,7 +85,7 @@ def _u8(buf) -> "ctypes.POINTER(ctypes.c_uint8)":
 
 
 def _u64(buf):
-    return buf.ctypes.data_as(_lib.c_u64p)
+    return None if buf is None else buf.ctypes.data_as(_lib.c_u64p)
 
 
 def _bytes_arr(b: bytes) -> np.ndarray:
@@ -128,6 +128,7 @@ class Engine:
         self.h = h
         self.L = None
         self.device = device
+        self._seeded = False             # set_seeded_random_scalars
         if window_bits is not None:
             self._chk(self.lib.bbs_ctx_set_window_bits(self.h, window_bits), "bbs_ctx_set_window_bits")
 
@@ -176,6 +177,17 @@ class Engine:
             off[i + 1] = off[i] + len(row)
             chunks.extend(self._fr(s) for s in row)
         return _bytes_arr(b"".join(chunks)), off
+
+    def _rnd(self, random_scalars):
+        """The random_scalars / rnd_off pair of a proof_gen call: rows of scalars, or, while set_seeded_random_scalars is on,
+        a list of per-item seeds (bytes, offsets in bytes) or ONE bytes object, the 32-byte job seed (rnd_off = NULL)."""
+        if not self._seeded:
+            return self._scalars(random_scalars)
+        if isinstance(random_scalars, (bytes, bytearray)):
+            if len(random_scalars) != 32:
+                raise ValueError("a job seed has exactly 32 bytes")
+            return _bytes_arr(random_scalars), None
+        return _ragged_bytes(random_scalars)
 
     @staticmethod
     def _indexes(rows: Sequence[Sequence[int]]):
@@ -397,6 +409,34 @@ class Engine:
         set_mixed_lengths."""
         self._chk(self.lib.bbs_ctx_set_mixed_lengths_gen(self.h, 1 if on else 0), "bbs_ctx_set_mixed_lengths_gen")
 
+    def set_seeded_random_scalars(self, enabled: bool, dst: Optional[bytes] = None):
+        """bbs_ctx_set_seeded_random_scalars: the proof_gen methods of this engine (jobs created afterwards) take
+        ``random_scalars`` as a list of per-item seeds (bytes of any length) or as ONE 32-byte job seed (bytes; item i draws from
+        job_seed || I2OSP(i, 8)) and draw item i's 5 + l_i - r_i scalars on the device: the reference's
+        seeded_random_scalars(seed_i, dst, count).  A seed is a secret and must never serve two different proofs."""
+        d = bytes(dst or b"")
+        buf = _bytes_arr(d)
+        self._chk(self.lib.bbs_ctx_set_seeded_random_scalars(self.h, 1 if enabled else 0, _u8(buf), len(d)), "bbs_ctx_set_seeded_random_scalars")
+        self._seeded = bool(enabled)
+
+    def seeded_random_scalars_batch(self, seeds: Sequence[bytes], counts: Sequence[int], dst: bytes):
+        """bbs_seeded_random_scalars_batch -> (rows of counts[i] scalars; an empty row where status != 1, statuses)."""
+        n = len(seeds)
+        sb, so = _ragged_bytes(seeds)
+        cn = np.ascontiguousarray(list(counts) + [0], dtype=np.uint32)
+        d = _bytes_arr(dst)
+        total = int(sum(int(c) for c in counts))
+        out = np.zeros(max(total, 1) * 32, dtype=np.uint8)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        self._chk(self.lib.bbs_seeded_random_scalars_batch(self.h, n, _u8(sb), _u64(so), cn.ctypes.data_as(_lib.c_u32p), _u8(d), len(dst), _u8(out),
+                                                           st.ctypes.data_as(_lib.c_i8p)), "bbs_seeded_random_scalars_batch")
+        rows, at = [], 0
+        for i in range(n):
+            c = int(counts[i])
+            rows.append([int.from_bytes(out[(at + k) * 32:(at + k + 1) * 32].tobytes(), "little") for k in range(c)] if st[i] == 1 else [])
+            at += c
+        return rows, st[:n]
+
     def set_keyed_mixed_lengths(self, on: bool):
         """bbs_ctx_set_keyed_mixed_lengths: the keyed verify / proof_verify batches of this engine accept item i under its own
         key with its own message count 0 .. L (jobs created afterwards); independent of set_mixed_lengths."""
@@ -568,7 +608,7 @@ class Engine:
         ob, bad = self._sig_octets(sig_octets)
         mb, mbo, mio = self._raw_msgs(messages_raw)
         di, dio = self._indexes(disclosed_idx)
-        rs, ro = self._scalars(random_scalars)
+        rs, ro = self._rnd(random_scalars)
         hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
         pb, po = _ragged_bytes(phs if phs is not None else [b""] * n)
         cap = sum(3 * self.fpb + 32 * (4 + len(m)) for m in messages_raw)
@@ -833,7 +873,7 @@ class Engine:
         sg = self._sigs(signatures)
         ms, mo = self._scalars(messages)
         di, dio = self._indexes(disclosed_idx)
-        rs, ro = self._scalars(random_scalars)
+        rs, ro = self._rnd(random_scalars)
         hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
         pb, po = _ragged_bytes(phs if phs is not None else [b""] * n)
         keep = (sg, ms, mo, di, dio, rs, ro, hb, ho, pb, po)
@@ -923,7 +963,7 @@ class Engine:
         ob, bad = self._sig_octets(sig_octets)
         mb, mbo, mio = self._raw_msgs(messages_raw)
         di, dio = self._indexes(disclosed_idx)
-        rs, ro = self._scalars(random_scalars)
+        rs, ro = self._rnd(random_scalars)
         hb, ho = _ragged_bytes(headers if headers is not None else [b""] * n)
         pb, po = _ragged_bytes(phs if phs is not None else [b""] * n)
         cap = sum(3 * self.fpb + 32 * (4 + len(m)) for m in messages_raw)

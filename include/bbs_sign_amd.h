@@ -56,6 +56,8 @@ extern "C" {
 #define BBS_ST_PANIC_R2_ZERO (-21)            /* src/proof_gen.rs:346 unwrap on inverse of 0 */
 #define BBS_ST_PANIC_INDEX_OUT_OF_BOUNDS (-22)/* src/proof_verify.rs:177-179 commitments[i] */
 #define BBS_ST_PANIC_DST_TOO_LONG (-23)       /* src/utils/utilities_helper.rs:46-52 */
+#define BBS_ST_PANIC_ELL_TOO_BIG (-24)        /* src/utils/utilities_helper.rs:46-48: expand_message of more than 255 * 32 bytes
+                                                (seeded random scalars only: more than 170 scalars for one item) */
 /* inputs arkworks' types cannot represent */
 #define BBS_ST_NONCANONICAL (-40)             /* scalar >= r or coordinate >= p */
 #define BBS_ST_NOT_ON_CURVE (-41)            /* also: not in the prime-order subgroup (codec) */
@@ -221,6 +223,30 @@ int bbs_ctx_set_mixed_lengths(bbs_ctx* ctx, int enabled);
  * switch; with this switch on and that one off they return BBS_E_STATE and enqueue nothing; bbs_issuer and bbs_pool keep one
  * context per count; the C++ wrapper and the Rust shim do not expose the switch. */
 int bbs_ctx_set_mixed_lengths_gen(bbs_ctx* ctx, int enabled);
+/* Seeded random scalars for proof_gen, drawn on the device (off by default; with it off nothing changes anywhere).  enabled = 1:
+ * every proof_gen entry point of the context -- the nine single-key and the four keyed exports: core, octets and wire forms;
+ * _upload, _batch and _submit; both job forms; bbs_ctx_set_mixed_lengths_gen and bbs_ctx_set_keyed_mixed_lengths on or off --
+ * reads its random_scalars / rnd_off pair as SEEDS, in one of two shapes:
+ *   per-item seeds (rnd_off != NULL): item i's seed is the BYTES random_scalars[rnd_off[i] .. rnd_off[i + 1]); offsets in
+ *       bytes, any length, 0 included;
+ *   job seed (rnd_off == NULL): random_scalars is ONE job seed of which exactly 32 bytes are read (fewer readable bytes cannot
+ *       be checked); item i's seed is job_seed || I2OSP(i, 8), i the item's position in the call.
+ * Item i's scalars are seeded_random_scalars(seed_i, dst, 5 + l_i - r_i) of the reference (src/utils/core_utilities.rs:84-100:
+ * expand_message_xmd(SHA-256) of 48 bytes per scalar, each through FromOkm), r_i counted before deduplication as the reference
+ * sizes its draw and l_i the item's own count in a mixed-length job, and dst[0 .. dst_len) is copied into the context.  The
+ * status AND the output bytes of an item are, bit for bit, those of the call with the switch off that is given those scalars,
+ * but for two codes the reference's draw (proof_gen.rs:145-149) raises before proof_init's checks (:229-239).  After -2 and -3
+ * and before every other code of core_proof_gen an item is BBS_ST_PANIC_ELL_TOO_BIG when 5 + l_i - r_i > 170 (ell > 255) and
+ * BBS_ST_PANIC_DST_TOO_LONG when dst_len > 255 (utilities_helper.rs:46-52, in that order).  What is decided ahead of core_proof_gen stays ahead: the codes
+ * of signature decoding (wire form), msg_to_scalars' -23, and BBS_ST_UNKNOWN_KEY, which overrides everything in a keyed job.  An
+ * item that is decided before the draw draws nothing and its seed is not read.  The contract of the switch-off call on the
+ * number of random scalars (BBS_E_ARG) does not apply; the staged image carries the seeds instead of the scalars.
+ * Memory: the stored dst, counted in bbs_ctx_table_bytes.  Applies to jobs created afterwards; a job keeps what it was created
+ * with.  BBS_E_ARG for a NULL ctx, or a NULL dst with dst_len > 0.
+ * SECURITY: a seed is a secret exactly as the scalars are, and it must never serve two different proofs: the same job seed in
+ * two jobs repeats nonces, which gives away e and the hidden messages.  The caller owns freshness.
+ * NOT covered: bbs_issuer_*, bbs_pool_*, the C++ wrapper and the Rust shim do not expose the switch. */
+int bbs_ctx_set_seeded_random_scalars(bbs_ctx* ctx, int enabled, const uint8_t* dst, size_t dst_len);
 /* Mixed message counts for the KEYED entry points (off by default; with it off nothing changes anywhere, the BBS_E_STATE above
  * included).  enabled = 1: every keyed verify and proof_verify job created from now on -- the eight bbs_*_keyed_* exports: core
  * and wire forms, _submit and _batch, both job forms -- takes item i under its own key key_index[i] AND with its own count l_i,
@@ -754,6 +780,13 @@ int bbs_job_stage_times(bbs_job* job, float* total_ms, float* kernel_ms, int ker
 /* hash_to_scalar (src/utils/core_utilities.rs:11-21) of n ragged messages under one dst. */
 int bbs_hash_to_scalar_batch(bbs_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
                              const uint8_t* dst, size_t dst_len, uint8_t* scalars_out);
+/* seeded_random_scalars (src/utils/core_utilities.rs:84-100) of n ragged seeds under one dst: the device body of
+ * bbs_ctx_set_seeded_random_scalars on its own.  Item i's seed is seeds[seed_off[i] .. seed_off[i + 1]) and it produces counts[i]
+ * scalars, 32 bytes little-endian each, packed in item order: item i's start at scalar sum(counts[0 .. i)).  status[i]: 1,
+ * BBS_ST_PANIC_ELL_TOO_BIG (counts[i] > 170) or, looked at second as in the reference, BBS_ST_PANIC_DST_TOO_LONG (dst_len > 255); the scalars of a refused item are
+ * zero.  BBS_E_ARG for the call if a count is 0 (the reference divides by zero there). */
+int bbs_seeded_random_scalars_batch(bbs_ctx* ctx, size_t n, const uint8_t* seeds, const uint64_t* seed_off, const uint32_t* counts,
+                                    const uint8_t* dst, size_t dst_len, uint8_t* scalars_out, int8_t* status);
 /* out[i] = sum_k fixed_scalars[i][k] * G_k  +  sum_m var_scalars[i][m] * var_points[i][m]
  * with G = [P1, Q1, H_1..H_L] of the context (n_fixed <= L+2), affine output. */
 int bbs_g1_msm_batch(bbs_ctx* ctx, size_t n, const uint8_t* fixed_scalars, size_t n_fixed,
