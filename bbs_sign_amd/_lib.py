@@ -199,6 +199,7 @@ SIGNATURES = {
     "bbs_pairing_product2_is_one_batch": (ci, [vp, sz, c_u8p, c_u8p, c_i8p]),
     "bbs_selftest_f12": (ci, [vp, ci, c_u8p, c_u8p, c_u8p, c_u8p]),
     "bbs_selftest_f12_batch": (ci, [vp, ci, sz, c_u8p, c_u8p, c_i8p, ci, ci, c_u8p, c_u8p, c_i8p]),
+    "bbs_selftest_pairing_split": (ci, [vp, sz, c_u8p, c_u8p, ci, c_i8p, c_u8p, c_u8p, c_u8p, c_i8p]),
     "bbs_selftest_inv": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),
     "bbs_selftest_fp4sqr": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),
     "bbs_selftest_f2dot": (ci, [ci, sz, c_u8p, c_u8p, c_u8p, c_u8p]),

@@ -1268,6 +1268,12 @@ int bbs_selftest_f12_batch(bbs_ctx* ctx, int op, size_t n, const uint8_t* a, con
     return with_curve(ctx, [&](auto* c) { return selftest_f12_batch(c, op, n, a, b, active, line_table, line_index, out_single, out_dist, flag_out); });
 }
 
+int bbs_selftest_pairing_split(bbs_ctx* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, int negate_b, const int8_t* active,
+                               const uint8_t* miller_in, uint8_t* miller_single, uint8_t* miller_dist, int8_t* status) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return selftest_pairing_split(c, n, pa, pb, negate_b, active, miller_in, miller_single, miller_dist, status); });
+}
+
 int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, const int8_t* is_identity, const uint8_t* pk_octets, int path,
                              uint8_t* entries_out, int8_t* status_out, uint8_t* pk_affine_out) {
     if (!ctx || (path != 0 && path != 1) || (n && ((!pk_affine && !pk_octets) || !entries_out || !status_out))) return BBS_E_ARG;

@@ -524,6 +524,146 @@ int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const
 #endif
 }
 
+// Pairing self-test: the Miller values and the statuses of the latency-form kernels (stages_pair.hpp PairMillerHalf,
+// PairFinalDist), launched as add_pairing_stages launches them, beside the one-lane stages run on the host over ctx->hc.
+// The host twin has only the one-lane stages.  Nothing is written to the caller's buffers before every step has succeeded.
+template <class C>
+int selftest_pairing_split(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, int negate_b, const int8_t* active,
+                           const uint8_t* miller_in, uint8_t* miller_single, uint8_t* miller_dist, int8_t* status) {
+    constexpr int N = C::FpP::N;
+    constexpr int NC = C::FpP::NC;
+    constexpr int FPB = 4 * NC;
+    constexpr int8_t INACTIVE = -126;                 // matches no gate: neither PairPrep's (ST_PENDING) nor the kernels' (ST_PAIRING)
+    using P = typename C::FpP;
+    static_assert(INACTIVE != ST_PENDING && INACTIVE != ST_PAIRING, "an inactive item must match no gate");
+    if (!status || (negate_b != 0 && negate_b != 1) || (n && !miller_in && (!pa || !pb))) return BBS_E_ARG;
+#ifdef BBS_HOST_TWIN
+    if (miller_dist) return BBS_E_ARG;                 // (no six-lane code in this build)
+#endif
+    if (!ctx->pk_set) return BBS_E_STATE;
+    if (!n) return BBS_OK;
+    if (ctx->use()) return BBS_E_HIP;
+    std::vector<int8_t> act(n, 1), st0(n, ST_PENDING);
+    if (active) for (size_t i = 0; i < n; i++) act[i] = active[i] ? 1 : 0;
+    const size_t fwords = (size_t)2 * 12 * N * n;
+    // ---- the one-lane stages on the host: hF is [pair][12 Fp, tower order][N][n] (f12_store)
+    Soa A, B;
+    std::vector<uint32_t> hAm((size_t)2 * N * n), hBm((size_t)2 * N * n), hF(fwords, 0u);
+    std::vector<int8_t> hst(n);
+    PairArgs<C> h{};
+    h.n = n; h.cc = &ctx->hc; h.pa = hAm.data(); h.pb = hBm.data(); h.negate_b = negate_b; h.gate_arr = hst.data(); h.gate = ST_PAIRING;
+    h.out = hst.data(); h.fmiller = hF.data();
+    std::vector<Fp<C>> given;                          // miller_in as normal Montgomery limbs, [n][2][12] tower order
+    if (miller_in) {
+        given.resize(n * 24);
+        for (size_t k = 0; k < n * 24; k++) if (!fe_from_le_bytes<P>(miller_in + k * FPB, given[k])) return BBS_E_ARG;
+        for (size_t i = 0; i < n; i++) st0[i] = act[i] ? ST_PAIRING : INACTIVE;
+    } else {
+        A.init(2 * NC, n); B.init(2 * NC, n);
+        for (size_t i = 0; i < n; i++) {
+            const bool ok = pack_g1<C>(A, 0, i, pa + i * 2 * FPB) & pack_g1<C>(B, 0, i, pb + i * 2 * FPB);
+            if (!act[i]) st0[i] = INACTIVE;
+            else if (!ok) st0[i] = BBS_ST_NONCANONICAL;
+        }
+    }
+    hst = st0;
+#ifdef BBS_HOST_TWIN
+    const bool one_lane_miller = !miller_in;
+#else
+    const bool one_lane_miller = !miller_in && miller_single;
+#endif
+    if (one_lane_miller) {
+        PairPrep<C> pp{A.soa().data(), B.soa().data(), hAm.data(), hBm.data(), hst.data(), n};
+        for (size_t i = 0; i < n; i++) PairPrep<C>::run(pp, i);
+        for (size_t t = 0; t < 2 * n; t++) PairMiller<C>::run(h, t);
+    }
+    std::vector<int8_t> processed(n, 0);               // items whose Miller values exist: they passed PairPrep
+    for (size_t i = 0; i < n; i++) processed[i] = !miller_in && hst[i] == ST_PAIRING;
+    auto put_single = [&]() {
+        if (!miller_single || miller_in) return;
+        for (size_t i = 0; i < n; i++) {
+            if (!processed[i]) continue;
+            for (int pair = 0; pair < 2; pair++) {
+                Fp<C> e[12];
+                f12_to_array<C>(f12_load<C>(hF.data() + (size_t)pair * 12 * N * n, n, i), e);
+                for (int k = 0; k < 12; k++) fe_to_le_bytes<P>(e[k], miller_single + ((i * 2 + pair) * 12 + k) * FPB);
+            }
+        }
+    };
+#ifdef BBS_HOST_TWIN
+    if (miller_in)
+        for (size_t i = 0; i < n; i++) for (int pair = 0; pair < 2; pair++)
+            f12_store<C>(hF.data() + (size_t)pair * 12 * N * n, n, i, f12_from_array<C>(&given[(i * 2 + pair) * 12]));
+    for (size_t i = 0; i < n; i++) PairFinal<C>::run(h, i);
+    for (size_t i = 0; i < n; i++) if (act[i] && (hst[i] == ST_PENDING || hst[i] == ST_PAIRING)) return BBS_E_STATE;
+    put_single();
+    for (size_t i = 0; i < n; i++) if (act[i]) status[i] = hst[i];
+    return BBS_OK;
+#else
+    // ---- the six-lane kernels: dF is [pair][lane m][2N][n], lane m = w-basis coefficient m = the tower's Fp2 number
+    // (m & 1) * 3 + (m >> 1) (stages_prim.hpp SelfTestDist)
+    constexpr uint32_t PATTERN = 0xA5A5A5A5u;          // (no limb of a stored value has bits above 28)
+    auto slot = [&](int pair, int m, int j, size_t i) { return (((size_t)pair * GRP + m) * 2 * N + j) * n + i; };
+    std::vector<uint32_t> F(fwords, PATTERN);
+    if (miller_in)
+        for (size_t i = 0; i < n; i++) for (int pair = 0; pair < 2; pair++) for (int m = 0; m < GRP; m++) {
+            const int k = (m & 1) * 3 + (m >> 1);
+            const Fp<C>* g = &given[(i * 2 + pair) * 12 + 2 * k];
+            for (int j = 0; j < N; j++) { F[slot(pair, m, j, i)] = g[0].v[j]; F[slot(pair, m, N + j, i)] = g[1].v[j]; }
+        }
+    DevBuf dA, dB, dAm, dBm, dSt, dF;
+    if (dAm.alloc((size_t)2 * N * n * 4 + 4) || dBm.alloc((size_t)2 * N * n * 4 + 4) || dSt.alloc(n + 4) || dF.alloc(fwords * 4 + 4)) return BBS_E_NOMEM;
+    if (rt::h2d(dSt.p, st0.data(), n, ctx->stream) || rt::h2d(dF.p, F.data(), fwords * 4, ctx->stream)) return BBS_E_HIP;
+    int rc = ctx->sync_consts();
+    if (rc) return rc;
+    PairArgs<C> a{};
+    a.n = n; a.cc = ctx->d_consts.template as<CtxConsts<C>>(); a.pa = dAm.as<uint32_t>(); a.pb = dBm.as<uint32_t>();
+    a.negate_b = negate_b; a.canonical = 0; a.gate_arr = dSt.as<int8_t>(); a.gate = ST_PAIRING; a.out = dSt.as<int8_t>(); a.fmiller = dF.as<uint32_t>();
+    a.single = 0;
+    const size_t waves = (n + GRP_PER_WAVE - 1) / GRP_PER_WAVE;
+    std::vector<int8_t> mid(st0), fin(n);
+    if (!miller_in) {
+        if (dA.alloc(A.bytes()) || dB.alloc(B.bytes())) return BBS_E_NOMEM;
+        if (rt::h2d(dA.p, A.soa().data(), A.bytes(), ctx->stream) || rt::h2d(dB.p, B.soa().data(), B.bytes(), ctx->stream)) return BBS_E_HIP;
+        PairPrep<C> pp{dA.as<uint32_t>(), dB.as<uint32_t>(), dAm.as<uint32_t>(), dBm.as<uint32_t>(), dSt.as<int8_t>(), n};
+        if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) ||
+            (ctx->dev_lines_unit ? rt::launch<PairMillerHalf<C, true>>(ctx->stream, a, waves * 128)
+                                 : rt::launch<PairMillerHalf<C, false>>(ctx->stream, a, waves * 128)) ||
+            rt::sync(ctx->stream)) return BBS_E_HIP;
+        if (rt::d2h(F.data(), dF.p, fwords * 4, ctx->stream) || rt::d2h(mid.data(), dSt.p, n, ctx->stream)) return BBS_E_HIP;
+        for (size_t i = 0; i < n; i++) {
+            if (one_lane_miller && mid[i] != hst[i]) return BBS_E_STATE;       // PairPrep on the device and on the host disagree
+            processed[i] = mid[i] == ST_PAIRING;
+            if (!act[i] && mid[i] != INACTIVE) return BBS_E_STATE;
+            if (processed[i]) continue;
+            for (int q = 0; q < 2 * GRP * 2 * N; q++)                          // a gated item's slots are still the pattern
+                if (F[(size_t)q * n + i] != PATTERN) return BBS_E_STATE;
+        }
+    }
+    if (rt::launch<PairFinalDist<C>>(ctx->stream, a, waves * 64) || rt::sync(ctx->stream)) return BBS_E_HIP;
+    if (rt::d2h(fin.data(), dSt.p, n, ctx->stream)) return BBS_E_HIP;
+    for (size_t i = 0; i < n; i++) {
+        if (!act[i] && fin[i] != INACTIVE) return BBS_E_STATE;
+        if (act[i] && (fin[i] == ST_PENDING || fin[i] == ST_PAIRING)) return BBS_E_STATE;
+        if (mid[i] != ST_PAIRING && fin[i] != mid[i]) return BBS_E_STATE;      // the final stage touched a gated item
+    }
+    put_single();
+    if (miller_dist && !miller_in)
+        for (size_t i = 0; i < n; i++) {
+            if (!processed[i]) continue;
+            for (int pair = 0; pair < 2; pair++) for (int m = 0; m < GRP; m++) {
+                const int k = (m & 1) * 3 + (m >> 1);
+                Fe<P> c0, c1;
+                for (int j = 0; j < N; j++) { c0.v[j] = F[slot(pair, m, j, i)]; c1.v[j] = F[slot(pair, m, N + j, i)]; }
+                fe_to_le_bytes<P>(c0, miller_dist + ((i * 2 + pair) * 12 + 2 * k) * FPB);
+                fe_to_le_bytes<P>(c1, miller_dist + ((i * 2 + pair) * 12 + 2 * k + 1) * FPB);
+            }
+        }
+    for (size_t i = 0; i < n; i++) if (act[i]) status[i] = fin[i];
+    return BBS_OK;
+#endif
+}
+
 template <class C>
 int selftest_f12(Ctx<C>* ctx, int op, const uint8_t* a_le, const uint8_t* b_le, uint8_t* out_single, uint8_t* out_dist) {
     if (op == 12) return BBS_E_ARG;                     // (the boolean has no place in this entry's outputs)

@@ -78,6 +78,7 @@ template <class C> int seeded_scalars_batch(Ctx<C>*, size_t, const uint8_t*, con
 template <class C> int msm_batch(Ctx<C>*, size_t, const uint8_t*, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, int8_t*);
 template <class C> int selftest_f12(Ctx<C>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 template <class C> int selftest_f12_batch(Ctx<C>*, int, size_t, const uint8_t*, const uint8_t*, const int8_t*, int, int, uint8_t*, uint8_t*, int8_t*);
+template <class C> int selftest_pairing_split(Ctx<C>*, size_t, const uint8_t*, const uint8_t*, int, const int8_t*, const uint8_t*, uint8_t*, uint8_t*, int8_t*);
 template <class C> int pairing_batch(Ctx<C>*, size_t, const uint8_t*, const uint8_t*, int8_t*);
 template <class C> int msm_pippenger(Ctx<C>*, size_t, const uint8_t*, const uint8_t*, uint8_t*, int*, int8_t*);
 template <class C> int g1_decompress_batch(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*);
@@ -121,7 +122,9 @@ extern template int proofs_from_octets_batch<BnCurve>(Ctx<BnCurve>*, size_t, con
 extern template int selftest_f12<BlsCurve>(Ctx<BlsCurve>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 extern template int selftest_f12<BnCurve>(Ctx<BnCurve>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 extern template int selftest_f12_batch<BlsCurve>(Ctx<BlsCurve>*, int, size_t, const uint8_t*, const uint8_t*, const int8_t*, int, int, uint8_t*, uint8_t*, int8_t*);
+extern template int selftest_pairing_split<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, const uint8_t*, int, const int8_t*, const uint8_t*, uint8_t*, uint8_t*, int8_t*);
 extern template int selftest_f12_batch<BnCurve>(Ctx<BnCurve>*, int, size_t, const uint8_t*, const uint8_t*, const int8_t*, int, int, uint8_t*, uint8_t*, int8_t*);
+extern template int selftest_pairing_split<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, int, const int8_t*, const uint8_t*, uint8_t*, uint8_t*, int8_t*);
 extern template int Ctx<BlsCurve>::add_keys(bool, size_t, const uint8_t*, const int8_t*, const uint8_t*, int8_t*, uint8_t*, int8_t*, uint32_t*);
 extern template int Ctx<BlsCurve>::set_keyed_mixed_lengths(int);
 extern template int Ctx<BlsCurve>::rebuild_lines();

@@ -7,6 +7,7 @@ template int msm_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, size_t, c
 template int pairing_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, int8_t*);
 template int selftest_f12<BnCurve>(Ctx<BnCurve>*, int, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
 template int selftest_f12_batch<BnCurve>(Ctx<BnCurve>*, int, size_t, const uint8_t*, const uint8_t*, const int8_t*, int, int, uint8_t*, uint8_t*, int8_t*);
+template int selftest_pairing_split<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, int, const int8_t*, const uint8_t*, uint8_t*, uint8_t*, int8_t*);
 template int msm_pippenger<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint8_t*, uint8_t*, int*, int8_t*);
 template int proofs_from_octets_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, uint8_t*, uint8_t*, uint64_t*, int8_t*);
 template int g1_decompress_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*);

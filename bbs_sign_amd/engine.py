@@ -1194,6 +1194,29 @@ class Engine:
                   "bbs_pairing_product2_is_one_batch")
         return st[:n]
 
+    def selftest_pairing_split(self, pa=None, pb=None, negate_b=False, active=None, miller_in=None, single=True, dist=True,
+                               fill=0xA5):
+        """bbs_selftest_pairing_split: the latency-form pairing kernels beside the one-lane code.  ``pa`` / ``pb``: G1 points
+        (None = the identity), or ``miller_in``: n x 2 x 12 x fp_bytes bytes, the values the final stage runs on.  Returns
+        (rc, status, miller_single, miller_dist): int8 statuses and (n, 2, 12 * fp_bytes) uint8 rows, every output prefilled
+        with ``fill`` (what the library did not write still holds it); a row array is None where ``single`` / ``dist`` is
+        off (the host twin has no six-lane values: ``dist=False``).  The return code is returned, not raised."""
+        row = 12 * self.fpb
+        n = len(miller_in) // (2 * row) if miller_in is not None else len(pa)
+        a = None if pa is None else _bytes_arr(b"".join(self._g1(p) for p in pa))
+        b = None if pb is None else _bytes_arr(b"".join(self._g1(p) for p in pb))
+        mi = None if miller_in is None else _bytes_arr(bytes(miller_in))
+        act = None if active is None else np.array(active, dtype=np.int8)
+        st = np.full(max(n, 1), fill, dtype=np.uint8).view(np.int8)
+        ms = np.full(max(n, 1) * 2 * row, fill, dtype=np.uint8) if single else None
+        md = np.full(max(n, 1) * 2 * row, fill, dtype=np.uint8) if dist else None
+        u8 = lambda v: None if v is None else _u8(v)
+        rc = self.lib.bbs_selftest_pairing_split(self.h, n, u8(a), u8(b), int(bool(negate_b)),
+                                                 None if act is None else act.ctypes.data_as(_lib.c_i8p), u8(mi), u8(ms), u8(md),
+                                                 st.ctypes.data_as(_lib.c_i8p))
+        shape = lambda v: None if v is None else v[:n * 2 * row].reshape(n, 2, row)
+        return rc, st[:n], shape(ms), shape(md)
+
 
 class Job:
     """A device-resident batch (bbs_job): run() is asynchronous on the context's stream."""

@@ -1020,6 +1020,25 @@ int bbs_selftest_f12_batch(bbs_ctx* ctx, int op, size_t n, const uint8_t* a, con
 /* The same for one item (ops 0..11) in group 0 of one wavefront, line entry 3 of BP2's table. */
 int bbs_selftest_f12(bbs_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint8_t* out_single,
                      uint8_t* out_dist);
+/* Pairing self-test: the Miller values and the statuses of the latency-form pairing kernels (the two Miller loops of an item
+ * on separate wavefronts, then product + final exponentiation), launched unchanged and with the geometry a job gives them,
+ * beside the one-lane code run on the host; the caller compares the outputs.  The check is e(Pa, pk) e(+-Pb, BP2) == 1 for
+ * the context's public key (BBS_E_STATE without one), in the context's line form (bbs_ctx_set_unit_lines).
+ * pa, pb: n affine records each, as bbs_pairing_product2_is_one_batch takes them; negate_b = 1 uses -Pb.  active (n entries,
+ * or NULL = all): an item with active[i] = 0 is gated out of every stage and nothing of it is written.
+ * miller_in == NULL: on-curve check, both Miller loops, final stage.  status[i] = 1 / 0, or -40 / -41 for a refused item.
+ *   miller_dist (may be NULL): for every item that reached the Miller loops, the values of pair 0 = (Pa, pk) and pair
+ *   1 = (+-Pb, BP2) as the six-lane kernel left them for the final stage, n x 2 x 12 Fp, canonical LE, tower order;
+ *   miller_single (may be NULL): the same two values by the one-lane code.  Rows of inactive and refused items are left as
+ *   the caller passed them.  BBS_E_STATE if the device wrote a value or a status for an item that was gated out.
+ * miller_in != NULL (n x 2 x 12 Fp, canonical LE, tower order; BBS_E_ARG for a value >= p): no Miller loop; the final stage
+ *   alone runs on these values for the active items.  pa / pb are ignored and may be NULL; miller_single and miller_dist
+ *   are not written.  The final exponentiation inverts: a pair whose product is zero has no defined status.
+ * The CPU test build runs its one-lane stages and fills miller_single only: miller_dist must be NULL there (BBS_E_ARG).
+ * n = 0: BBS_OK, nothing written.  A call that returns an error has written nothing. */
+int bbs_selftest_pairing_split(bbs_ctx* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, int negate_b,
+                               const int8_t* active, const uint8_t* miller_in, uint8_t* miller_single,
+                               uint8_t* miller_dist, int8_t* status);
 /* Host arithmetic self-test (no GPU): out = sum_k w_k * a_k * b_k in Fp2 computed by the lazily reduced column
  * accumulators the pairing kernel uses (one Montgomery reduction pair per dot product).  a, b: n_terms records
  * c0 || c1 (canonical LE); weights[k] = 1, 2, or 0 for "b_k is its c0 in Fp"; total weight <= 6. */
