@@ -229,6 +229,13 @@ template <class J>
 int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
     return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
 }
+#if !defined(BBS_HOST_TWIN)
+// the keyed fused kernel over the slots of the pairing order (runtime.hpp launch_line_form)
+template <class C>
+inline int launch_pair_fused_keyed(rt::Stream& st, bool unit, const PairKeyedArgs<C>& ka) {
+    return launch_line_form<PairDistKeyed, C>(st, unit, ka, pair6_threads(ka.n_slots));
+}
+#endif
 // the pairing step of a keyed job on the main (aux = 0) or second stream, as add_pairing_stages: the fused kernel in both job
 // forms.  pair->p is copied from *pa when the stage is launched.  pair = null: the job's real items (jf->pair) under the usual
 // stage names; keyed batch verification passes its virtual items and its own names.
@@ -247,9 +254,7 @@ void add_keyed_pairing_stages(J* j, PairedJobForm<C>* jf, const PairArgs<C>* pa,
         pair->p = *pa;
         // the key set the job holds and BP2's table on the device must agree (they do unless the form was switched under the job)
         if (jf->unit != j->ctx->dev_lines_unit) return -1;
-        rt::Stream& st = aux ? j->stream_aux() : j->stream();
-        const size_t nt = ((pair->n_slots + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
-        return jf->unit ? rt::launch<PairDistKeyed<C, true>>(st, *pair, nt) : rt::launch<PairDistKeyed<C, false>>(st, *pair, nt);
+        return launch_pair_fused_keyed<C>(aux ? j->stream_aux() : j->stream(), jf->unit, *pair);
     }, aux, 0});
 #endif
 }
@@ -285,7 +290,7 @@ int add_keyed_bv_stages(J* j, Ctx<C>* ctx, PairedJobForm<C>* jf, size_t n, const
     sg.ppts = ppts; sg.dig = dig; sg.seg_sums = seg_sums; sg.out = out;
     PairArgs<C>& ps = bv->vpa;
     ps.n = NV; ps.cc = cc; ps.pa = out; ps.pb = out + (size_t)2 * N * NV; ps.negate_b = negate_b; ps.canonical = 0;
-    ps.gate = 1; ps.out = bv->verdicts; ps.fmiller = nullptr; ps.single = 0; ps.batch_ok = nullptr; ps.n_checks = 0;
+    ps.gate = 1; ps.out = bv->verdicts; ps.fmiller = nullptr; ps.batch_ok = nullptr; ps.n_checks = 0;
 #ifdef BBS_HOST_TWIN
     ps.fmiller = j->template scratch<uint32_t>((size_t)2 * 12 * N * NV, rc);      // (the fused device kernel keeps the Miller values in registers)
     if (rc) return rc;

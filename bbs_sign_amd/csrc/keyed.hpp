@@ -75,19 +75,8 @@ struct PairMillerKeyed {
         if (a.gate_arr[i] != a.gate) return;
         G1Aff<C> P = pair_load_point<C>(a, pair == 0 ? a.pa : a.pb, i);
         if (pair == 1 && a.negate_b) P = g1a_neg<C>(P);
-        const LineTable<C>* tab = pair == 0 ? &ka.keys[pair_keyed_key<C>(ka, s, i)].tab : &a.cc->tab_bp2;
-        Fp12<C> f = f12_one<C>();
-        const bool skip = g1a_is_inf<C>(P) | (tab->q_is_identity != 0);
-        if (!skip) {
-            int li = 0;
-            const int nops = a.cc->sched.n_ops;
-            for (int k = 0; k < nops; k++) {
-                if (a.cc->sched.op[k] == 0) f = f12_sqr<C>(f);
-                else f = f12_mul_line<C>(f, tab->e[li++], P, tab->unit != 0);
-            }
-            if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
-        }
-        f12_store<C>(a.fmiller + (size_t)pair * 12 * N * n, n, i, f);
+        const LineTable<C>& tab = pair == 0 ? ka.keys[pair_keyed_key<C>(ka, s, i)].tab : a.cc->tab_bp2;
+        f12_store<C>(a.fmiller + (size_t)pair * 12 * N * n, n, i, miller_one_pair<C>(tab, P, a.cc->sched));
     }
 };
 
@@ -100,41 +89,20 @@ template <class C, bool UNIT, bool UNIFORM>
 __device__ __forceinline__ void pair_dist_keyed(const PairKeyedArgs<C>& ka, size_t t) {
     const PairArgs<C>& a = ka.p;
     const int lane = (int)(t & 63);
-    const int grp = lane / GRP;
-    if (grp >= GRP_PER_WAVE) return;
-    const size_t s = (t >> 6) * GRP_PER_WAVE + grp;
+    const int grp = pair6_group(lane);
+    if (grp < 0) return;
+    const size_t s = pair6_item(t >> 6, grp);
     if (s >= ka.n_slots) return;
     const size_t i = ka.slot_item[s];
     if (a.gate_arr[i] != a.gate) return;
-    Lane6 L{grp * GRP, lane - grp * GRP};
-    const CtxConsts<C>* cc = a.cc;
+    const Lane6 L = pair6_lanes(lane, grp);
     const LineTable<C>* tw;
     if constexpr (UNIFORM) tw = &ka.keys[__builtin_amdgcn_readfirstlane(ka.wave_key[t >> 6])].tab;
     else tw = &ka.keys[ka.kidx[i]].tab;
     G1Aff<C> Pa = pair_load_point<C>(a, a.pa, i);
     G1Aff<C> Pb = pair_load_point<C>(a, a.pb, i);
     if (a.negate_b) Pb = g1a_neg<C>(Pb);
-    const bool skipA = g1a_is_inf<C>(Pa) | (tw->q_is_identity != 0);
-    const bool skipB = g1a_is_inf<C>(Pb) | (cc->tab_bp2.q_is_identity != 0);
-    Fp2<C> f = d_one<C>(L);
-    if (!(skipA & skipB)) {
-        Fp2<C> m = d_one<C>(L);
-        int li = 0;
-        const int nops = cc->sched.n_ops;
-        for (int k = 0; k < nops; k++) {
-            if (cc->sched.op[k] == 0) {
-                m = d_sqr<C>(L, m);
-            } else {
-                if (!skipA) m = d_mul_line<C, UNIT>(L, m, tw->e[li], Pa);
-                if (!skipB) m = d_mul_line<C, UNIT>(L, m, cc->tab_bp2.e[li], Pb);
-                li++;
-            }
-        }
-        if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
-        const Fp2<C> mf = m;
-        f = d_final_exp<C>(L, mf, &cc->frob[0][0][0][0]);
-    }
-    const bool one = d_is_one<C>(L, f);
+    const bool one = pair6_product_is_one<C, UNIT>(L, a.cc, tw, Pa, Pb);
     if (L.m == 0) a.out[i] = one ? 1 : 0;
 }
 // UNIT: the form of every table of the key set and of BP2's (one form per context: runtime.hpp Ctx::rebuild_lines)

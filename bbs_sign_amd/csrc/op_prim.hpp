@@ -403,10 +403,7 @@ int pairing_batch(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, i
     if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) || rt::launch<PairMiller<C>>(ctx->stream, a, n * 2) ||
         rt::launch<PairFinal<C>>(ctx->stream, a, n) || rt::sync(ctx->stream)) return BBS_E_HIP;
 #else
-    if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) ||
-        (ctx->dev_lines_unit ? rt::launch<PairDist<C, true>>(ctx->stream, a, ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64)
-                             : rt::launch<PairDist<C, false>>(ctx->stream, a, ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64)) ||
-        rt::sync(ctx->stream)) return BBS_E_HIP;
+    if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) || launch_pair_fused<C>(ctx->stream, ctx->dev_lines_unit, a) || rt::sync(ctx->stream)) return BBS_E_HIP;
 #endif
     if (rt::d2h(status, dSt.p, n, ctx->stream)) return BBS_E_HIP;
     return statuses_final(status, n) ? BBS_OK : BBS_E_STATE;
@@ -493,9 +490,8 @@ int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const
     if (rc) return rc;
     SelfTestArgs<C> a{op, n, ctx->d_consts.template as<CtxConsts<C>>(), dB.as<uint32_t>(), dAct.as<int8_t>(), line_table, line_index,
                       dD.as<uint32_t>(), dFlag.as<int8_t>()};
-    const size_t nthreads = ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
     int lrc = -1;
-#define BBS_ST_CASE(K) case K: lrc = rt::launch<SelfTestDist<C, K>>(ctx->stream, a, nthreads); break;
+#define BBS_ST_CASE(K) case K: lrc = rt::launch<SelfTestDist<C, K>>(ctx->stream, a, pair6_threads(n)); break;
     switch (op) {
         BBS_ST_CASE(0) BBS_ST_CASE(1) BBS_ST_CASE(2) BBS_ST_CASE(3) BBS_ST_CASE(4) BBS_ST_CASE(5)
         BBS_ST_CASE(6) BBS_ST_CASE(7) BBS_ST_CASE(8) BBS_ST_CASE(10) BBS_ST_CASE(11) BBS_ST_CASE(12)
@@ -525,7 +521,7 @@ int selftest_f12_batch(Ctx<C>* ctx, int op, size_t n, const uint8_t* a_le, const
 }
 
 // Pairing self-test: the Miller values and the statuses of the latency-form kernels (stages_pair.hpp PairMillerHalf,
-// PairFinalDist), launched as add_pairing_stages launches them, beside the one-lane stages run on the host over ctx->hc.
+// PairFinalDist), launched by the launchers add_pairing_stages uses (runtime.hpp), beside the one-lane stages run on the host over ctx->hc.
 // The host twin has only the one-lane stages.  Nothing is written to the caller's buffers before every step has succeeded.
 template <class C>
 int selftest_pairing_split(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8_t* pb, int negate_b, const int8_t* active,
@@ -600,16 +596,14 @@ int selftest_pairing_split(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8
     for (size_t i = 0; i < n; i++) if (act[i]) status[i] = hst[i];
     return BBS_OK;
 #else
-    // ---- the six-lane kernels: dF is [pair][lane m][2N][n], lane m = w-basis coefficient m = the tower's Fp2 number
-    // (m & 1) * 3 + (m >> 1) (stages_prim.hpp SelfTestDist)
+    // ---- the six-lane kernels: dF is laid out by fmiller_slot (stages_pair.hpp), lane m = the tower's Fp2 number (m & 1) * 3 + (m >> 1)
     constexpr uint32_t PATTERN = 0xA5A5A5A5u;          // (no limb of a stored value has bits above 28)
-    auto slot = [&](int pair, int m, int j, size_t i) { return (((size_t)pair * GRP + m) * 2 * N + j) * n + i; };
     std::vector<uint32_t> F(fwords, PATTERN);
     if (miller_in)
         for (size_t i = 0; i < n; i++) for (int pair = 0; pair < 2; pair++) for (int m = 0; m < GRP; m++) {
             const int k = (m & 1) * 3 + (m >> 1);
             const Fp<C>* g = &given[(i * 2 + pair) * 12 + 2 * k];
-            for (int j = 0; j < N; j++) { F[slot(pair, m, j, i)] = g[0].v[j]; F[slot(pair, m, N + j, i)] = g[1].v[j]; }
+            fmiller_store<C>(F.data(), n, pair, m, i, Fp2<C>{g[0], g[1]});
         }
     DevBuf dA, dB, dAm, dBm, dSt, dF;
     if (dAm.alloc((size_t)2 * N * n * 4 + 4) || dBm.alloc((size_t)2 * N * n * 4 + 4) || dSt.alloc(n + 4) || dF.alloc(fwords * 4 + 4)) return BBS_E_NOMEM;
@@ -619,28 +613,23 @@ int selftest_pairing_split(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8
     PairArgs<C> a{};
     a.n = n; a.cc = ctx->d_consts.template as<CtxConsts<C>>(); a.pa = dAm.as<uint32_t>(); a.pb = dBm.as<uint32_t>();
     a.negate_b = negate_b; a.canonical = 0; a.gate_arr = dSt.as<int8_t>(); a.gate = ST_PAIRING; a.out = dSt.as<int8_t>(); a.fmiller = dF.as<uint32_t>();
-    a.single = 0;
-    const size_t waves = (n + GRP_PER_WAVE - 1) / GRP_PER_WAVE;
     std::vector<int8_t> mid(st0), fin(n);
     if (!miller_in) {
         if (dA.alloc(A.bytes()) || dB.alloc(B.bytes())) return BBS_E_NOMEM;
         if (rt::h2d(dA.p, A.soa().data(), A.bytes(), ctx->stream) || rt::h2d(dB.p, B.soa().data(), B.bytes(), ctx->stream)) return BBS_E_HIP;
         PairPrep<C> pp{dA.as<uint32_t>(), dB.as<uint32_t>(), dAm.as<uint32_t>(), dBm.as<uint32_t>(), dSt.as<int8_t>(), n};
-        if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) ||
-            (ctx->dev_lines_unit ? rt::launch<PairMillerHalf<C, true>>(ctx->stream, a, waves * 128)
-                                 : rt::launch<PairMillerHalf<C, false>>(ctx->stream, a, waves * 128)) ||
-            rt::sync(ctx->stream)) return BBS_E_HIP;
+        if (rt::launch<PairPrep<C>>(ctx->stream, pp, n) || launch_pair_miller_split<C>(ctx->stream, ctx->dev_lines_unit, a) || rt::sync(ctx->stream)) return BBS_E_HIP;
         if (rt::d2h(F.data(), dF.p, fwords * 4, ctx->stream) || rt::d2h(mid.data(), dSt.p, n, ctx->stream)) return BBS_E_HIP;
         for (size_t i = 0; i < n; i++) {
             if (one_lane_miller && mid[i] != hst[i]) return BBS_E_STATE;       // PairPrep on the device and on the host disagree
             processed[i] = mid[i] == ST_PAIRING;
             if (!act[i] && mid[i] != INACTIVE) return BBS_E_STATE;
             if (processed[i]) continue;
-            for (int q = 0; q < 2 * GRP * 2 * N; q++)                          // a gated item's slots are still the pattern
-                if (F[(size_t)q * n + i] != PATTERN) return BBS_E_STATE;
+            for (int pair = 0; pair < 2; pair++) for (int m = 0; m < GRP; m++) for (int row = 0; row < 2 * N; row++)
+                if (F[fmiller_slot<C>(n, pair, m, row, i)] != PATTERN) return BBS_E_STATE;      // a gated item's slots are still the pattern
         }
     }
-    if (rt::launch<PairFinalDist<C>>(ctx->stream, a, waves * 64) || rt::sync(ctx->stream)) return BBS_E_HIP;
+    if (launch_pair_final<C>(ctx->stream, a) || rt::sync(ctx->stream)) return BBS_E_HIP;
     if (rt::d2h(fin.data(), dSt.p, n, ctx->stream)) return BBS_E_HIP;
     for (size_t i = 0; i < n; i++) {
         if (!act[i] && fin[i] != INACTIVE) return BBS_E_STATE;
@@ -653,10 +642,9 @@ int selftest_pairing_split(Ctx<C>* ctx, size_t n, const uint8_t* pa, const uint8
             if (!processed[i]) continue;
             for (int pair = 0; pair < 2; pair++) for (int m = 0; m < GRP; m++) {
                 const int k = (m & 1) * 3 + (m >> 1);
-                Fe<P> c0, c1;
-                for (int j = 0; j < N; j++) { c0.v[j] = F[slot(pair, m, j, i)]; c1.v[j] = F[slot(pair, m, N + j, i)]; }
-                fe_to_le_bytes<P>(c0, miller_dist + ((i * 2 + pair) * 12 + 2 * k) * FPB);
-                fe_to_le_bytes<P>(c1, miller_dist + ((i * 2 + pair) * 12 + 2 * k + 1) * FPB);
+                const Fp2<C> g = fmiller_load<C>(F.data(), n, pair, m, i);
+                fe_to_le_bytes<P>(g.c0, miller_dist + ((i * 2 + pair) * 12 + 2 * k) * FPB);
+                fe_to_le_bytes<P>(g.c1, miller_dist + ((i * 2 + pair) * 12 + 2 * k + 1) * FPB);
             }
         }
     for (size_t i = 0; i < n; i++) if (act[i]) status[i] = fin[i];

@@ -26,11 +26,22 @@ namespace bbs {
 
 constexpr int GRP = 6;                 // lanes per item
 constexpr int GRP_PER_WAVE = 10;
+// threads of a launch over n items: one wavefront per GRP_PER_WAVE items (the fused and the final kernels), or one per pair of
+// them (PairMillerHalf: wavefront 2 v for pair 0 and 2 v + 1 for pair 1 of the same items)
+constexpr size_t pair6_threads(size_t n) { return ((n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64; }
+constexpr size_t pair6_split_threads(size_t n) { return 2 * pair6_threads(n); }
+static_assert(pair6_threads(0) == 0 && pair6_threads(1) == 64 && pair6_threads(10) == 64 && pair6_threads(11) == 128, "one wavefront per ten items");
+static_assert(pair6_split_threads(0) == 0 && pair6_split_threads(1) == 128 && pair6_split_threads(10) == 128 && pair6_split_threads(11) == 256,
+              "two wavefronts per ten items");
 
 struct Lane6 {
     int base;     // first lane of the group inside the wavefront
     int m;        // coefficient index 0..5 held by this lane
 };
+// lane of a wavefront -> its group, -1 for the idle lanes 60..63; (wavefront's number among those of its pair, group) -> item
+__device__ __forceinline__ int pair6_group(int lane) { const int grp = lane / GRP; return grp < GRP_PER_WAVE ? grp : -1; }
+__device__ __forceinline__ size_t pair6_item(size_t wave, int grp) { return wave * GRP_PER_WAVE + grp; }
+__device__ __forceinline__ Lane6 pair6_lanes(int lane, int grp) { return Lane6{grp * GRP, lane - grp * GRP}; }
 
 template <class P>
 __device__ __forceinline__ Fe<P> fe_shfl(const Fe<P>& v, int src_lane) {

@@ -1392,6 +1392,26 @@ inline int launch_pip_window_segs(Stream& s, const PipSegArgs<C>& a) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace rt
+
+// The six-lane pairing kernels take the form of the line tables as a template parameter: launch_line_form is the one place
+// that turns the run-time `unit` into it.  The launchers of the single-key kernels (stages_pair.hpp) follow, with the geometry
+// of pairing_dist.hpp; the keyed one is job_form.hpp launch_pair_fused_keyed.
+template <template <class, bool> class K, class C, class A>
+inline int launch_line_form(rt::Stream& st, bool unit, const A& a, size_t nthreads) {
+    return unit ? rt::launch<K<C, true>>(st, a, nthreads) : rt::launch<K<C, false>>(st, a, nthreads);
+}
+template <class C>
+inline int launch_pair_fused(rt::Stream& st, bool unit, const PairArgs<C>& a) {
+    return launch_line_form<PairDist, C>(st, unit, a, pair6_threads(a.n));
+}
+template <class C>
+inline int launch_pair_miller_split(rt::Stream& st, bool unit, const PairArgs<C>& a) {
+    return launch_line_form<PairMillerHalf, C>(st, unit, a, pair6_split_threads(a.n));
+}
+template <class C>
+inline int launch_pair_final(rt::Stream& st, const PairArgs<C>& a) {
+    return rt::launch<PairFinalDist<C>>(st, a, pair6_threads(a.n));
+}
 #endif
 
 // one pairing product check as stages on the job's main (aux = 0) or second stream.  Split: the two Miller loops of an
@@ -1412,20 +1432,13 @@ void add_pairing_stages(J* j, PairArgs<C>* pargs, int aux, const char* nm_miller
     j->stages.push_back({nm_miller, [j, pargs, aux]() { return rt::launch<PairMiller<C>>(aux ? j->stream_aux() : j->stream(), *pargs, pargs->n * 2); }, aux, 0});
     j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinal<C>>(aux ? j->stream_aux() : j->stream(), *pargs, pargs->n); }, aux, 0});
 #else
-    pargs->single = 0;      // always (stages.hpp PairArgs)
     if (split == PairSplit::Always || (split == PairSplit::ByJobForm && j->latency_form)) {
         // the two Miller loops of every item on separate wavefronts, then product + final exponentiation (stages.hpp)
-        j->stages.push_back({nm_miller, [j, pargs, aux]() { 
-            rt::Stream& st = aux ? j->stream_aux() : j->stream();
-            const size_t nt = ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 128;
-            return j->ctx->dev_lines_unit ? rt::launch<PairMillerHalf<C, true>>(st, *pargs, nt) : rt::launch<PairMillerHalf<C, false>>(st, *pargs, nt); }, aux, 0});
-        j->stages.push_back({nm_final, [j, pargs, aux]() { return rt::launch<PairFinalDist<C>>(aux ? j->stream_aux() : j->stream(), *pargs, ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64); }, aux, 0});
+        j->stages.push_back({nm_miller, [j, pargs, aux]() { return launch_pair_miller_split<C>(aux ? j->stream_aux() : j->stream(), j->ctx->dev_lines_unit, *pargs); }, aux, 0});
+        j->stages.push_back({nm_final, [j, pargs, aux]() { return launch_pair_final<C>(aux ? j->stream_aux() : j->stream(), *pargs); }, aux, 0});
         return;
     }
-    j->stages.push_back({nm_dist, [j, pargs, aux]() { 
-        rt::Stream& st = aux ? j->stream_aux() : j->stream();
-        const size_t nt = ((pargs->n + GRP_PER_WAVE - 1) / GRP_PER_WAVE) * 64;
-        return j->ctx->dev_lines_unit ? rt::launch<PairDist<C, true>>(st, *pargs, nt) : rt::launch<PairDist<C, false>>(st, *pargs, nt); }, aux, 0});
+    j->stages.push_back({nm_dist, [j, pargs, aux]() { return launch_pair_fused<C>(aux ? j->stream_aux() : j->stream(), j->ctx->dev_lines_unit, *pargs); }, aux, 0});
 #endif
 }
 

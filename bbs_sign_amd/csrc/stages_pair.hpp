@@ -16,8 +16,7 @@ struct PairArgs {
     const int8_t* gate_arr;   // item i is processed iff gate_arr[i] == gate
     int gate;
     int8_t* out;              // result 1 / 0 per item (may alias the status array)
-    uint32_t* fmiller;        // [2][12N][n]
-    int single;               // always 0 (the one-value form was retired): fmiller holds one value per pair (PairMillerHalf)
+    uint32_t* fmiller;        // one-lane stages: [2][12N][n] (f12_store); six-lane kernels: fmiller_slot
     // batch verification: this launch is the per-item FALLBACK behind the combined checks -- if all n_checks of them passed
     // (batch_ok[k] == 1), every gated item's product is 1 (error 2^-128) and the lane only writes that; null otherwise
     const int8_t* batch_ok;
@@ -66,6 +65,20 @@ BBS_HD Fp12<C> f12_load(const uint32_t* base, size_t n, size_t i) {
     return f12_from_array<C>(e);
 }
 
+// the one-lane Miller loop of ONE pair (a pair whose point or table is the identity contributes 1)
+template <class C>
+BBS_HD Fp12<C> miller_one_pair(const LineTable<C>& tab, const G1Aff<C>& P, const MillerSchedule& sched) {
+    Fp12<C> f = f12_one<C>();
+    if (g1a_is_inf<C>(P) | (tab.q_is_identity != 0)) return f;
+    int li = 0;
+    for (int k = 0; k < sched.n_ops; k++) {
+        if (sched.op[k] == 0) f = f12_sqr<C>(f);
+        else f = f12_mul_line<C>(f, tab.e[li++], P, tab.unit != 0);
+    }
+    if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
+    return f;
+}
+
 // lane per (pair, item)
 template <class C>
 struct PairMiller {
@@ -78,19 +91,8 @@ struct PairMiller {
         if (pair_batch_passed<C>(a)) return;
         G1Aff<C> P = pair_load_point<C>(a, pair == 0 ? a.pa : a.pb, i);
         if (pair == 1 && a.negate_b) P = g1a_neg<C>(P);
-        const LineTable<C>* tab = pair == 0 ? &a.cc->tab_pk : &a.cc->tab_bp2;
-        Fp12<C> f = f12_one<C>();
-        const bool skip = g1a_is_inf<C>(P) | (tab->q_is_identity != 0);
-        if (!skip) {
-            int li = 0;
-            const int nops = a.cc->sched.n_ops;
-            for (int k = 0; k < nops; k++) {
-                if (a.cc->sched.op[k] == 0) f = f12_sqr<C>(f);
-                else f = f12_mul_line<C>(f, tab->e[li++], P, tab->unit != 0);
-            }
-            if constexpr (C::K::X_NEG) f = f12_conj<C>(f);
-        }
-        f12_store<C>(a.fmiller + (size_t)pair * 12 * N * n, n, i, f);
+        const LineTable<C>& tab = pair == 0 ? a.cc->tab_pk : a.cc->tab_bp2;
+        f12_store<C>(a.fmiller + (size_t)pair * 12 * N * n, n, i, miller_one_pair<C>(tab, P, a.cc->sched));
     }
 };
 
@@ -128,28 +130,59 @@ struct PairPrep {
 // Thread index: wave = t / 64 ; group = (t % 64) / 6 ; item = wave * 10 + group.
 // UNIT: the form of BOTH line tables (pairing.hpp "Unit form"), picked by the host per job.
 // =============================================================================================
+// The product of one item on its six lanes: e(Pa, W) * e(Pb, BP2) == 1, W's lines in *tw.  Both bodies of PairDistKeyed call it
+// with a key-set entry's table (keyed.hpp); PairDist below is the same body with tw = &cc->tab_pk, written out for its registers.
+// Every lane of the group returns the boolean.
+template <class C, bool UNIT>
+__device__ __forceinline__ bool pair6_product_is_one(const Lane6& L, const CtxConsts<C>* cc, const LineTable<C>* tw, const G1Aff<C>& Pa,
+                                                     const G1Aff<C>& Pb) {
+    const bool skipA = g1a_is_inf<C>(Pa) | (tw->q_is_identity != 0);
+    const bool skipB = g1a_is_inf<C>(Pb) | (cc->tab_bp2.q_is_identity != 0);
+    Fp2<C> f = d_one<C>(L);
+    if (!(skipA & skipB)) {
+        // the Miller accumulator is its own variable, never handed by reference to a non-inlined function: that
+        // would make it a memory object and put a scratch store / load of it around every step of the loop
+        Fp2<C> m = d_one<C>(L);
+        int li = 0;
+        const int nops = cc->sched.n_ops;
+        for (int k = 0; k < nops; k++) {
+            if (cc->sched.op[k] == 0) {
+                m = d_sqr<C>(L, m);
+            } else {
+                if (!skipA) m = d_mul_line<C, UNIT>(L, m, tw->e[li], Pa);
+                if (!skipB) m = d_mul_line<C, UNIT>(L, m, cc->tab_bp2.e[li], Pb);
+                li++;
+            }
+        }
+        if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
+        const Fp2<C> mf = m;
+        f = d_final_exp<C>(L, mf, &cc->frob[0][0][0][0]);
+    }
+    return d_is_one<C>(L, f);
+}
+
 template <class C, bool UNIT>
 struct PairDist {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
         const int lane = (int)(t & 63);
-        const int grp = lane / GRP;
-        if (grp >= GRP_PER_WAVE) return;
-        const size_t i = (t >> 6) * GRP_PER_WAVE + grp;
+        const int grp = pair6_group(lane);
+        if (grp < 0) return;
+        const size_t i = pair6_item(t >> 6, grp);
         if (i >= a.n) return;
         if (a.gate_arr[i] != a.gate) return;
-        Lane6 L{grp * GRP, lane - grp * GRP};
+        const Lane6 L = pair6_lanes(lane, grp);
         if (pair_batch_passed<C>(a)) { if (L.m == 0) a.out[i] = 1; return; }
         G1Aff<C> Pa = pair_load_point<C>(a, a.pa, i);
         G1Aff<C> Pb = pair_load_point<C>(a, a.pb, i);
         if (a.negate_b) Pb = g1a_neg<C>(Pb);
+        // pair6_product_is_one's body with W = cc->tab_pk, written out: no form of the call leaves the registers of this kernel
+        // and of PairDistKeyed both as they are (profiles/pair_body_ab.log, section 2).  A change to either body goes into both.
         const CtxConsts<C>* cc = a.cc;
         const bool skipA = g1a_is_inf<C>(Pa) | (cc->tab_pk.q_is_identity != 0);
         const bool skipB = g1a_is_inf<C>(Pb) | (cc->tab_bp2.q_is_identity != 0);
         Fp2<C> f = d_one<C>(L);
         if (!(skipA & skipB)) {
-            // the Miller accumulator is its own variable, never handed by reference to a non-inlined function: that
-            // would make it a memory object and put a scratch store / load of it around every step of the loop
             Fp2<C> m = d_one<C>(L);
             int li = 0;
             const int nops = cc->sched.n_ops;
@@ -171,6 +204,29 @@ struct PairDist {
     }
 };
 
+// The Miller values between PairMillerHalf and PairFinalDist: fmiller is [pair][lane m][2N][n], lane m = w-basis coefficient m =
+// the tower's Fp2 number (m & 1) * 3 + (m >> 1); limb j of c0 at row j, of c1 at row N + j (coalesced over the items' lanes m)
+template <class C>
+BBS_HD size_t fmiller_slot(size_t n, int pair, int m, int row, size_t i) {
+    return (((size_t)pair * GRP + m) * 2 * C::FpP::N + row) * n + i;
+}
+template <class C>
+BBS_HD void fmiller_store(uint32_t* fm, size_t n, int pair, int m, size_t i, const Fp2<C>& g) {
+    constexpr int N = C::FpP::N;
+    uint32_t* o = fm + fmiller_slot<C>(n, pair, m, 0, i);
+#pragma unroll
+    for (int j = 0; j < N; j++) { o[(size_t)j * n] = g.c0.v[j]; o[(size_t)(N + j) * n] = g.c1.v[j]; }
+}
+template <class C>
+BBS_HD Fp2<C> fmiller_load(const uint32_t* fm, size_t n, int pair, int m, size_t i) {
+    constexpr int N = C::FpP::N;
+    const uint32_t* p = fm + fmiller_slot<C>(n, pair, m, 0, i);
+    Fp2<C> g;
+#pragma unroll
+    for (int j = 0; j < N; j++) { g.c0.v[j] = p[(size_t)j * n]; g.c1.v[j] = p[(size_t)(N + j) * n]; }
+    return g;
+}
+
 // ---- latency form (round 3): the two Miller loops of an item on SEPARATE six-lane groups ------------------------------
 // PairDist runs both pairs of an item on one group (63 shared squarings + 2 x 68 line products) and then the final
 // exponentiation: 410 wavefronts of ~4.9 ms for a 4096-item batch on a chip of 1024 SIMDs.  When a batch has the chip to
@@ -183,17 +239,16 @@ template <class C, bool UNIT>
 struct PairMillerHalf {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
-        constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
-        const int grp = lane / GRP;
-        if (grp >= GRP_PER_WAVE) return;
+        const int grp = pair6_group(lane);
+        if (grp < 0) return;
         const size_t wave = t >> 6;
         const int pair = (int)(wave & 1);
-        const size_t i = (wave >> 1) * GRP_PER_WAVE + grp;
+        const size_t i = pair6_item(wave >> 1, grp);
         if (i >= a.n) return;
         if (a.gate_arr[i] != a.gate) return;
         if (pair_batch_passed<C>(a)) return;                   // PairFinalDist writes the verdict
-        Lane6 L{grp * GRP, lane - grp * GRP};
+        const Lane6 L = pair6_lanes(lane, grp);
         G1Aff<C> P = pair_load_point<C>(a, pair ? a.pb : a.pa, i);
         if (pair && a.negate_b) P = g1a_neg<C>(P);
         const CtxConsts<C>* cc = a.cc;
@@ -209,6 +264,9 @@ struct PairMillerHalf {
             }
             if constexpr (C::K::X_NEG) m = d_conj<C>(L, m);
         }
+        // fmiller_store, written out: through the helper this kernel takes more registers and, on BN254, loses its second
+        // wavefront per SIMD (profiles/pair_body_ab.log, section 2)
+        constexpr int N = C::FpP::N;
         uint32_t* o = a.fmiller + ((size_t)pair * GRP + L.m) * 2 * N * a.n + i;
 #pragma unroll
         for (int j = 0; j < N; j++) { o[(size_t)j * a.n] = m.c0.v[j]; o[(size_t)(N + j) * a.n] = m.c1.v[j]; }
@@ -218,29 +276,16 @@ template <class C>
 struct PairFinalDist {
     static constexpr int WAVES_PER_EU = PAIR_WAVES;
     static __device__ void run(const PairArgs<C>& a, size_t t) {
-        constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
-        const int grp = lane / GRP;
-        if (grp >= GRP_PER_WAVE) return;
-        const size_t i = (t >> 6) * GRP_PER_WAVE + grp;
+        const int grp = pair6_group(lane);
+        if (grp < 0) return;
+        const size_t i = pair6_item(t >> 6, grp);
         if (i >= a.n) return;
         if (a.gate_arr[i] != a.gate) return;
-        Lane6 L{grp * GRP, lane - grp * GRP};
+        const Lane6 L = pair6_lanes(lane, grp);
         if (pair_batch_passed<C>(a)) { if (L.m == 0) a.out[i] = 1; return; }
-        Fp2<C> g0;
-        const uint32_t* p0 = a.fmiller + (size_t)L.m * 2 * N * a.n + i;
-#pragma unroll
-        for (int j = 0; j < N; j++) { g0.c0.v[j] = p0[(size_t)j * a.n]; g0.c1.v[j] = p0[(size_t)(N + j) * a.n]; }
-        Fp2<C> mf = g0;
-        if (!a.single) {                                        // (uniform over the launch)
-            Fp2<C> g1;
-            const uint32_t* p1 = a.fmiller + ((size_t)GRP + L.m) * 2 * N * a.n + i;
-#pragma unroll
-            for (int j = 0; j < N; j++) { g1.c0.v[j] = p1[(size_t)j * a.n]; g1.c1.v[j] = p1[(size_t)(N + j) * a.n]; }
-            mf = d_mul<C>(L, g0, g1);
-        }
-        const Fp2<C> mfc = mf;
-        const Fp2<C> f = d_final_exp<C>(L, mfc, &a.cc->frob[0][0][0][0]);
+        const Fp2<C> mf = d_mul<C>(L, fmiller_load<C>(a.fmiller, a.n, 0, L.m, i), fmiller_load<C>(a.fmiller, a.n, 1, L.m, i));
+        const Fp2<C> f = d_final_exp<C>(L, mf, &a.cc->frob[0][0][0][0]);
         const bool one = d_is_one<C>(L, f);
         if (L.m == 0) a.out[i] = one ? 1 : 0;
     }

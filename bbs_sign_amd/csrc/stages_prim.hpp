@@ -177,12 +177,12 @@ struct SelfTestDist {
     static __device__ void run(const SelfTestArgs<C>& a, size_t t) {
         constexpr int N = C::FpP::N;
         const int lane = (int)(t & 63);
-        const int grp = lane / GRP;
+        const int grp = lane / GRP;                 // (pair6_group, written out for this kernel's registers: profiles/pair_body_ab.log)
         if (grp >= GRP_PER_WAVE) return;
-        const size_t i = (t >> 6) * GRP_PER_WAVE + grp;
+        const size_t i = pair6_item(t >> 6, grp);
         if (i >= a.n) return;
         if (!a.active[i]) return;
-        Lane6 L{grp * GRP, lane - grp * GRP};
+        const Lane6 L = pair6_lanes(lane, grp);
         // w-basis coefficient m of a tower-ordered array: g_m = (e[2k], e[2k+1]) with k = (m & 1) * 3 + (m >> 1)
         const int k = (L.m & 1) * 3 + (L.m >> 1);
         uint32_t* xd = a.out_dist + i * 12 * N;
