@@ -72,6 +72,7 @@ SIGNATURES = {
     # keyed batch verification: the switch, the report of a job, the segmented sums alone
     "bbs_ctx_set_keyed_batch_verification": (ci, [vp, ci, c_u8p, sz]),
     "bbs_job_bv_report": (ci, [vp, c_u32p, c_u32p, c_u32p]),
+    "bbs_job_bv_verdicts": (ci, [vp, c_i8p, sz, ctypes.POINTER(sz)]),
     "bbs_selftest_segmented_sums": (ci, [vp, sz, c_u8p, c_u8p, sz, c_u64p, c_u64p, c_u8p]),
     "bbs_selftest_glv_split": (ci, [ci, c_u8p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "bbs_selftest_lin_pm": (ci, [ci, ci, c_u8p, c_u8p, c_u8p]),

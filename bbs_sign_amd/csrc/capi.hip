@@ -641,6 +641,18 @@ int bbs_job_bv_report(bbs_job* job, uint32_t* groups, uint32_t* groups_passed, u
     *groups = *groups_passed = *items_in_groups = 0;
     return job->bv_report ? job->bv_report(groups, groups_passed, items_in_groups) : BBS_OK;
 }
+int bbs_job_bv_verdicts(bbs_job* job, int8_t* verdicts, size_t cap, size_t* n_out) {
+    if (!job || !n_out) return BBS_E_ARG;
+    *n_out = 0;
+    if (!verdicts) return BBS_E_ARG;
+    if (!job->bv_verdicts) return BBS_OK;
+    std::vector<int8_t> v;
+    if (const int rc = job->bv_verdicts(v)) return rc;
+    *n_out = v.size();
+    if (cap < v.size()) return BBS_E_ARG;
+    std::memcpy(verdicts, v.data(), v.size());
+    return BBS_OK;
+}
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int cap, int* n_stages) {
     if (!job || reps < 1) return BBS_E_ARG;
     if (job->use()) return BBS_E_HIP;

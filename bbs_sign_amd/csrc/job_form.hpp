@@ -306,10 +306,15 @@ int add_keyed_bv_stages(J* j, Ctx<C>* ctx, PairedJobForm<C>* jf, size_t n, const
     add_keyed_pairing_stages<C>(j, jf, &bv->vpa, 0, &bv->vpair, "keyed_rlc_pairing", "keyed_rlc_pair_final_exp");
     j->stages.push_back({"keyed_bv_decide", [j, bv]() { return rt::launch<KeyedBvDecide>(j->stream(), bv->dec, j->n); }});
     // bbs_job_bv_report: groups formed, groups whose 16 checks all passed (the verdicts read back on request), grouped items
-    j->bv_report = [j, bv](uint32_t* groups, uint32_t* passed, uint32_t* items) {
-        std::vector<int8_t> v((size_t)16 * bv->G);
+    // bbs_job_bv_verdicts: the same flags as they are, entry g * 16 + w
+    j->bv_verdicts = [j, bv](std::vector<int8_t>& v) {
+        v.assign((size_t)16 * bv->G, 0);
         if (j->use() || rt::sync(j->stream())) return (int)BBS_E_HIP;
-        if (rt::d2h(v.data(), bv->verdicts, v.size(), j->stream())) return (int)BBS_E_HIP;
+        return rt::d2h(v.data(), bv->verdicts, v.size(), j->stream()) ? (int)BBS_E_HIP : (int)BBS_OK;
+    };
+    j->bv_report = [j, bv](uint32_t* groups, uint32_t* passed, uint32_t* items) {
+        std::vector<int8_t> v;
+        if (const int rc = j->bv_verdicts(v)) return rc;
         uint32_t ok = 0;
         for (uint32_t g = 0; g < bv->G; g++) {
             bool all = true;

@@ -1062,8 +1062,11 @@ struct bbs_job {
     virtual void set_result_targets(uint8_t*, uint8_t*, uint64_t*) {}
     virtual int set_octet_form() { return BBS_E_ARG; }    // sign / proof_gen: results leave as octet strings (before run)
     virtual size_t device_bytes() const { return 0; }     // device memory this job holds (allocation size classes)
-    // bbs_job_bv_report: set by a keyed job that formed groups (job_form.hpp add_keyed_bv_stages); no groups: zeros
+    // bbs_job_bv_report: set by a job with combined checks -- a keyed job that formed groups (job_form.hpp add_keyed_bv_stages)
+    // or a single-key batch-verification job (add_batch_combination: one group of all n items); neither: zeros
     std::function<int(uint32_t*, uint32_t*, uint32_t*)> bv_report;
+    // bbs_job_bv_verdicts: the raw verdict flags of the last run, read back on request (set where bv_report is): 16 per group
+    std::function<int(std::vector<int8_t>&)> bv_verdicts;
     virtual int fetch_signatures(uint8_t*) { return BBS_E_ARG; }
     virtual int fetch_proofs(uint8_t*, uint8_t*, uint64_t*) { return BBS_E_ARG; }
     // One pass over the stages.  ev != nullptr: one event before the first stage, then a (start, stop) pair around
@@ -1501,6 +1504,21 @@ int add_batch_combination(J* j, BvState<C>* bv, Ctx<C>* ctx, size_t n, const Ctx
         j->stages.push_back({"pip_tile_sums", [bv, strm]() { return rt::launch<PipTileSums<C>>(strm(), bv->tsum, (size_t)bv->tsum.M * bv->tsum.NW); }, aux, 0});
 #endif
     add_pairing_stages<C>(j, &bv->pa_sum, aux, "rlc_pair_miller", "rlc_pair_final_exp", "rlc_pairing_6lane", PairSplit::Always);
+    // bbs_job_bv_verdicts / bbs_job_bv_report: the 16 results as the decision reads them (the second stream has been joined by
+    // the time the job is waited for); the report counts the whole job as one group
+    j->bv_verdicts = [j, flags](std::vector<int8_t>& v) {
+        v.assign(NW, 0);
+        if (j->use() || rt::sync(j->stream())) return (int)BBS_E_HIP;
+        return rt::d2h(v.data(), flags + NW, v.size(), j->stream()) ? (int)BBS_E_HIP : (int)BBS_OK;
+    };
+    j->bv_report = [j](uint32_t* groups, uint32_t* passed, uint32_t* items) {
+        std::vector<int8_t> v;
+        if (const int rc = j->bv_verdicts(v)) return rc;
+        bool all = true;
+        for (const int8_t f : v) all &= f == 1;
+        *groups = 1; *passed = all ? 1u : 0u; *items = (uint32_t)j->n;
+        return (int)BBS_OK;
+    };
     return BBS_OK;
 }
 template <class C, class J>

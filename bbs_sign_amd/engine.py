@@ -1288,11 +1288,26 @@ class Job:
         return self.eng._dec_proofs(pf, cm, cmo, st, self.n), st
 
     def bv_report(self):
-        """bbs_job_bv_report, after wait(): (groups formed, groups whose 16 combined checks all passed, items in groups) of a
-        keyed job under Engine.set_keyed_batch_verification; zeros for a job without groups."""
+        """bbs_job_bv_report, after wait(): (groups formed, groups whose 16 combined checks all passed, items in groups).
+        A keyed job under Engine.set_keyed_batch_verification: one group per key that reached the threshold.  A single-key job
+        under set_batch_verification: the whole job as one group, (1, 1 iff all 16 verdicts are 1, n).  Zeros for a job
+        without a combination."""
         g, p, it = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
         Engine._chk(self.eng.lib.bbs_job_bv_report(self.h, ctypes.byref(g), ctypes.byref(p), ctypes.byref(it)), "bbs_job_bv_report")
         return g.value, p.value, it.value
+
+    def bv_verdicts(self) -> np.ndarray:
+        """bbs_job_bv_verdicts, after wait(): the raw verdict flags of the last run's combined checks (1 = passed) -- 16 for a
+        single-key batch-verification job, 16 * groups for a keyed one (entry g * 16 + w), none for a job without a
+        combination."""
+        cnt = ctypes.c_size_t(0)
+        out = np.zeros(16, dtype=np.int8)
+        rc = self.eng.lib.bbs_job_bv_verdicts(self.h, out.ctypes.data_as(_lib.c_i8p), out.size, ctypes.byref(cnt))
+        if rc == -100 and cnt.value > out.size:          # BBS_E_ARG with the count set: a keyed job with more than one group
+            out = np.zeros(cnt.value, dtype=np.int8)
+            rc = self.eng.lib.bbs_job_bv_verdicts(self.h, out.ctypes.data_as(_lib.c_i8p), out.size, ctypes.byref(cnt))
+        Engine._chk(rc, "bbs_job_bv_verdicts")
+        return out[:cnt.value]
 
     def stage_names(self):
         """bbs_job_stage_name of every stage of the job, in launch order."""

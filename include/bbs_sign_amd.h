@@ -755,12 +755,21 @@ void bbs_job_free(bbs_job* job);
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int kernel_cap,
                       int* n_stages_out);
 const char* bbs_job_stage_name(const bbs_job* job, int stage);
-/* Keyed batch verification (bbs_ctx_set_keyed_batch_verification), after bbs_job_wait: the groups the job formed, the groups whose
- * 16 combined checks all passed in the last run (the verdict flags are read back from the device by this call), and the items
- * that belong to a group.  Zeros for a job without groups.  It tells the combined path from the per-item one; the stages of the
- * combined path are keyed_rlc_prep, keyed_pip_windows, keyed_pip_group_sums, keyed_rlc_pairing and keyed_bv_decide
- * (bbs_job_stage_name).  BBS_E_ARG for a NULL argument. */
+/* Batch verification, after bbs_job_wait: the groups the job formed, the groups whose 16 combined checks all passed in the last
+ * run (the verdict flags are read back from the device by this call), and the items that belong to a group.  It tells the
+ * combined path from the per-item one.
+ *  - keyed (bbs_ctx_set_keyed_batch_verification): one group per issuer key that reached the threshold; the stages of the
+ *    combined path are keyed_rlc_prep, keyed_pip_windows, keyed_pip_group_sums, keyed_rlc_pairing and keyed_bv_decide
+ *    (bbs_job_stage_name).
+ *  - single-key (bbs_ctx_set_batch_verification; verify and proof_verify, both job forms, mixed lengths included): the whole
+ *    job is one group, (1, 1 iff all 16 verdicts are 1, n).  Items decided before the pairing step are counted in n but add
+ *    nothing to the combination.
+ * Zeros for a job without a combination.  BBS_E_ARG for a NULL argument.
+ * bbs_job_bv_verdicts: the raw verdict flags behind that report, 1 = the combined check passed: 16 for a single-key job (one
+ * per 8-bit window of the coefficients), 16 * groups for a keyed one (entry g * 16 + w).  *n_out = their count, 0 for a job
+ * without a combination.  BBS_E_ARG for a NULL argument, and for cap < count (*n_out is still set, nothing is written). */
 int bbs_job_bv_report(bbs_job* job, uint32_t* groups, uint32_t* groups_passed, uint32_t* items_in_groups);
+int bbs_job_bv_verdicts(bbs_job* job, int8_t* verdicts, size_t cap, size_t* n_out);
 /* Throughput form: `njobs` device-resident batches in flight, step k runs on jobs[k % njobs] (every
  * job owns a HIP stream pair, so independent batches overlap on the GPU).  total_ms = first event to
  * the latest last-stage event; kernel_ms[s] = sum over all steps of stage s's own duration. */

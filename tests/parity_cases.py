@@ -591,6 +591,14 @@ def check_pippenger_tiles(curve, lib_path=None, n=9000, seed=27):
     eng.close()
 
 
+def bv_observed(job):
+    """A submitted batch-verification job, waited for and freed -> (statuses, the 16 verdict flags, bbs_job_bv_report)."""
+    job.wait()
+    out = [int(s) for s in job.result], [int(v) for v in job.bv_verdicts()], job.bv_report()
+    job.free()
+    return out
+
+
 def check_batch_verification(curve, lib_path=None, n=9, L=4, seed=5, window_bits=None):
     """Opt-in batch verification (one combined pairing check, per-item fallback) returns the same statuses as the
     default per-item mode and the oracle: all-valid batch; items that fail before the pairing (they are left out of
@@ -618,6 +626,8 @@ def check_batch_verification(curve, lib_path=None, n=9, L=4, seed=5, window_bits
     dm = [[msgs[i][j] for j in disclosed[i]] for i in range(n)]
     # 1. all valid
     assert list(batch.core_proof_verify_batch(proofs, dm, disclosed, headers, phs)) == [1] * n
+    # ... decided by the 16 combined checks themselves, not by a fallback behind a check that failed
+    assert bv_observed(batch.core_proof_verify_submit(proofs, dm, disclosed, headers, phs)) == ([1] * n, [1] * 16, (1, 1, n))
     # 2. failures before the pairing only: the combined check passes for the rest
     bad = [to_engine_proof(p_) for p_ in proofs]
     bad[1].e_cap = (bad[1].e_cap + 1) % c.r
@@ -639,10 +649,13 @@ def check_batch_verification(curve, lib_path=None, n=9, L=4, seed=5, window_bits
     want = list(exact.core_proof_verify_batch(fp, dm, disclosed, headers, phs))
     assert want == [1, 1, 0, 0, 1, 1, 1, 0, 1][:n], want
     assert list(batch.core_proof_verify_batch(fp, dm, disclosed, headers, phs)) == want
+    st, verdicts, report = bv_observed(batch.core_proof_verify_submit(fp, dm, disclosed, headers, phs))
+    assert st == want and verdicts != [1] * 16 and report == (1, 0, n), (st, verdicts, report)
     op = bbs.Proof(fp[2].a_bar, fp[2].b_bar, fp[2].d, fp[2].e_cap, fp[2].r1_cap, fp[2].r3_cap, fp[2].commitments, fp[2].challenge)
     assert bbs.core_proof_verify(suite, pk, op, gens, headers[2], phs[2], dm[2], disclosed[2], api_id) is False
     # 3b. core_verify in the same mode: all valid, then forged A / identity A / wrong message / wrong header
     assert list(batch.core_verify_batch(sigs, msgs, headers)) == [1] * n
+    assert bv_observed(batch.core_verify_submit(sigs, msgs, headers)) == ([1] * n, [1] * 16, (1, 1, n))
     vs = [Signature(s_.a, s_.e) for s_ in sigs]
     vm = [list(m) for m in msgs]
     vh = list(headers)
@@ -654,6 +667,8 @@ def check_batch_verification(curve, lib_path=None, n=9, L=4, seed=5, window_bits
     want_v = list(exact.core_verify_batch(vs, vm, vh))
     assert want_v == [0, 1, 1, 0, 1, 0, 0, 1, 0][:n], want_v
     assert list(batch.core_verify_batch(vs, vm, vh)) == want_v
+    st, verdicts, report = bv_observed(batch.core_verify_submit(vs, vm, vh))
+    assert st == want_v and verdicts != [1] * 16 and report == (1, 0, n), (st, verdicts, report)
     # 4. a resident job can be run again and a context can go back to the per-item mode
     job = batch.core_proof_verify_upload(fp, dm, disclosed, headers, phs)
     for _ in range(2):
@@ -878,13 +893,17 @@ def check_bv_tiles(curve, lib_path=None, n=16384, L=8, R=2, window_bits=None, jo
     eng.set_batch_verification(True)
     st = eng.core_proof_verify_batch(proofs, dm, disclosed)                  # combined checks pass: nobody falls back
     assert [int(x) for x in st] == [0 if i in pre else 1 for i in range(n)]
+    # ... as the verdict flags say (the items of `pre` fail at the challenge with their points untouched: whether the job's
+    # form has them in the combination or not, their pairing products are 1)
+    assert bv_observed(eng.core_proof_verify_submit(proofs, dm, disclosed)) == ([0 if i in pre else 1 for i in range(n)], [1] * 16, (1, 1, n))
     for run in plant_runs:
         cur = list(proofs)
         for k in run:
             cur[k] = forged[k]
         want = [0 if (i in pre or i in run) else 1 for i in range(n)]
         eng.set_batch_verification(True)
-        st_b = [int(x) for x in eng.core_proof_verify_batch(cur, dm, disclosed)]
+        st_b, verdicts, report = bv_observed(eng.core_proof_verify_submit(cur, dm, disclosed))
+        assert verdicts != [1] * 16 and report == (1, 0, n), (curve, run, verdicts, report)
         eng.set_batch_verification(False)
         st_e = [int(x) for x in eng.core_proof_verify_batch(cur, dm, disclosed)]
         assert st_e == want, (curve, run, "per-item mode")
@@ -895,8 +914,10 @@ def check_bv_tiles(curve, lib_path=None, n=16384, L=8, R=2, window_bits=None, jo
     for i in vbad:
         vs[i] = Signature(c.g1_add(sigs[i].a, c.g1), sigs[i].e)
     eng.set_batch_verification(True)
-    st = eng.core_verify_batch(vs, msgs)
-    assert [int(x) for x in st] == [0 if i in vbad else 1 for i in range(n)]
+    assert bv_observed(eng.core_verify_submit(sigs, msgs)) == ([1] * n, [1] * 16, (1, 1, n))
+    st, verdicts, report = bv_observed(eng.core_verify_submit(vs, msgs))
+    assert st == [0 if i in vbad else 1 for i in range(n)]
+    assert verdicts != [1] * 16 and report == (1, 0, n), (curve, verdicts, report)
     assert tiles > 1
     eng.close()
 

@@ -303,3 +303,45 @@ def test_pool_misuse_is_refused(twin):
     assert [int(x) for x in got] == [1] * n
     pool.close()
     eng.close()
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
+def test_bv_verdicts_arguments(twin, curve):
+    """bbs_job_bv_verdicts: NULL job / buffer / count are BBS_E_ARG; a buffer below the count is BBS_E_ARG with the count
+    still reported and nothing written; a job without a combination reports 0 verdicts whatever the buffer."""
+    suite = bbs.SUITES[curve]
+    L, n = 2, 3
+    eng = pc.make_engine(curve, pc.gens_for(suite, L + 1), suite.api_id, twin, sk=7)
+    lib = eng.lib
+    msgs = [[i + 1, i + 2] for i in range(n)]
+    sigs, st = eng.core_sign_batch(msgs)
+    assert list(st) == [1] * n
+    buf = np.full(20, 0x5A, dtype=np.int8)
+    p8, nul8 = buf.ctypes.data_as(_lib.c_i8p), ctypes.cast(None, _lib.c_i8p)
+    cnt = ctypes.c_size_t(99)
+    plain = eng.core_verify_submit(sigs, msgs)
+    plain.wait()
+    assert lib.bbs_job_bv_verdicts(None, p8, 20, ctypes.byref(cnt)) == E_ARG
+    assert lib.bbs_job_bv_verdicts(plain.h, p8, 20, None) == E_ARG
+    assert lib.bbs_job_bv_verdicts(plain.h, nul8, 20, ctypes.byref(cnt)) == E_ARG
+    cnt.value = 99
+    assert lib.bbs_job_bv_verdicts(plain.h, p8, 0, ctypes.byref(cnt)) == 0 and cnt.value == 0      # no combination: nothing to hold
+    assert plain.bv_verdicts().size == 0 and plain.bv_report() == (0, 0, 0)
+    plain.free()
+    eng.set_batch_verification(True, bytes(range(32)))
+    job = eng.core_verify_submit(sigs, msgs)
+    job.wait()
+    assert list(job.result) == [1] * n
+    for cap in (0, 15):
+        cnt.value = 99
+        assert lib.bbs_job_bv_verdicts(job.h, p8, cap, ctypes.byref(cnt)) == E_ARG and cnt.value == 16, cap
+    assert (buf == 0x5A).all()
+    assert lib.bbs_job_bv_verdicts(job.h, nul8, 16, ctypes.byref(cnt)) == E_ARG
+    assert lib.bbs_job_bv_verdicts(job.h, p8, 16, None) == E_ARG
+    assert lib.bbs_job_bv_verdicts(job.h, p8, 16, ctypes.byref(cnt)) == 0 and cnt.value == 16
+    assert list(buf[:16]) == [1] * 16 and (buf[16:] == 0x5A).all()
+    assert list(job.bv_verdicts()) == [1] * 16 and job.bv_report() == (1, 1, n)
+    g = ctypes.c_uint32(0)
+    assert lib.bbs_job_bv_report(job.h, None, ctypes.byref(g), ctypes.byref(g)) == E_ARG
+    job.free()
+    eng.close()
