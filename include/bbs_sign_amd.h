@@ -337,6 +337,10 @@ int bbs_ctx_get_public_key_compressed(bbs_ctx* ctx, uint8_t* out, size_t cap, si
  * checks and unpacking run on the device -- and returns a device-resident job; `bbs_job_run` enqueues the
  * kernels on the job's streams (asynchronous); `bbs_job_wait` blocks; `bbs_job_fetch_*` copies results back.
  * The one-shot `*_batch` functions do all of it; `*_submit` is the asynchronous one-shot form.
+ * Order of the per-item codes in every record form (core_proof_verify, core_verify, core_sign, core_proof_gen): the
+ * reference's own errors and panics first, in the reference's order (proof_verify: -3, -6, -1, -23, -22; verify and sign:
+ * -1, -23; proof_gen: -2, -3, -1, -4, -23); then BBS_ST_NONCANONICAL for ANY coordinate >= p or scalar >= r of the item,
+ * wherever it stands (record, commitments, messages, disclosed messages, random scalars); then BBS_ST_NOT_ON_CURVE.
  * ------------------------------------------------------------------------------------------ */
 
 /* core_proof_verify (src/proof_verify.rs:64-116 with proof_verify_init :119-188).
@@ -378,7 +382,9 @@ int bbs_core_proof_verify_submit(bbs_ctx* ctx, size_t n, const uint8_t* proofs_f
  * bbs_proof_from_octets followed by bbs_core_proof_verify_batch would give: BBS_ST_INVALID_ENCODING (shape, identity
  * point), BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE (also: outside the subgroup) before the reference's own checks.  The
  * disclosed messages are scalars, as for bbs_core_proof_verify_batch.  Because every point has been subgroup-checked, the
- * variable-base terms use the GLV split (BLS12-381) without bbs_ctx_set_points_in_subgroup. */
+ * variable-base terms use the GLV split (BLS12-381) without bbs_ctx_set_points_in_subgroup.
+ * Order: the codes of bbs_proof_from_octets in its order (below: the shape, the first failing point, the proof's scalars);
+ * then the reference's -3, -6, -1, -23, -22; then BBS_ST_NONCANONICAL for a disclosed message >= r. */
 int bbs_proof_verify_octets_submit(bbs_ctx* ctx, size_t n, const uint8_t* proof_octets, const uint64_t* oct_off,
                                    const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
                                    const uint64_t* disclosed_idx, const uint64_t* didx_off,
@@ -423,7 +429,8 @@ int bbs_core_verify_submit(bbs_ctx* ctx, size_t n, const uint8_t* signatures,
 /* verify from the wire: n signature octet strings of fp_bytes + 32 octets each, compress(A) || I2OSP(e, 32) (the byte
  * string of src/tests/test_vector.rs:188-191), decompressed, subgroup- and range-checked on the device in front of
  * core_verify.  status[i] = what bbs_signature_from_octets gives when it fails (malformed / not on the curve or in the
- * subgroup / identity / e = 0 or >= r), else what core_verify gives.  _submit as bbs_core_verify_submit. */
+ * subgroup / identity / e = 0 or >= r, in the order given at bbs_signature_from_octets), else what core_verify gives.
+ * _submit as bbs_core_verify_submit. */
 int bbs_verify_octets_submit(bbs_ctx* ctx, size_t n, const uint8_t* signature_octets,
                              const uint8_t* messages, const uint64_t* msg_off,
                              const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out);
@@ -455,7 +462,8 @@ int bbs_verify_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* signature_octet
  * entries device to device and frees the old array with its last holder.
  * ------------------------------------------------------------------------------------------ */
 /* n_keys issuer public keys (affine records as bbs_ctx_set_public_key; is_identity may be NULL = none).  key_status[k] (may
- * be NULL): 1, or BBS_ST_NOT_ON_CURVE for a key bbs_ctx_set_public_key would refuse (not on the twist / not of order r).
+ * be NULL): 1, or BBS_ST_NOT_ON_CURVE for a key bbs_ctx_set_public_key would refuse (not on the twist / not of order r; a
+ * record with a coordinate >= p counts as not on the twist: a record has no code of its own for it).
  * Replaces the context's previous key set (a new empty set, then an append); n_keys = 0 clears it.  Independent of
  * bbs_ctx_set_public_key.  Needs the generators (BBS_E_STATE); bbs_ctx_set_generators clears the key set.  A set is immutable
  * once built and every keyed job holds the set it was created with: replacing it or appending to it while jobs are in flight
@@ -807,7 +815,8 @@ int bbs_g1_msm_batch(bbs_ctx* ctx, size_t n, const uint8_t* fixed_scalars, size_
  * that is not canonical / not on the curve (it then contributes nothing). */
 int bbs_g1_msm_pippenger(bbs_ctx* ctx, size_t n, const uint8_t* points_affine, const uint8_t* scalars,
                          uint8_t* out_affine, int* out_is_identity, int8_t* status);
-/* status[i] = ( e(Pa[i], pk) * e(Pb[i], BP2) == 1 ) */
+/* status[i] = ( e(Pa[i], pk) * e(Pb[i], BP2) == 1 ), or BBS_ST_NONCANONICAL for a coordinate >= p, or, looked at second,
+ * BBS_ST_NOT_ON_CURVE; bbs_g1_msm_batch decides its scalars and points in the same order. */
 int bbs_pairing_product2_is_one_batch(bbs_ctx* ctx, size_t n, const uint8_t* pa_affine,
                                       const uint8_t* pb_affine, int8_t* status);
 
@@ -963,6 +972,12 @@ int bbs_sk_to_pk_batch(bbs_ctx* ctx, size_t n, const uint8_t* sk32, uint8_t* pk_
  * identity point / zero e where the BBS draft does.  Return 0 or a BBS_ST_* code.
  * (The reference derives ark-serialize's CanonicalSerialize/Deserialize for these types --
  * src/sign.rs:18, src/proof_gen.rs:29, src/key_gen.rs:12 -- without ever exercising them.)
+ * Order of the codes.  A point: BBS_ST_NONCANONICAL (a missing compression flag; an identity encoding with a value bit or
+ * the sign flag set; x >= p after the flag bits are cleared) before BBS_ST_NOT_ON_CURVE (no root; outside the subgroup).
+ * A signature: A's code; BBS_ST_INVALID_ENCODING for A = identity; BBS_ST_NONCANONICAL for e >= r; BBS_ST_INVALID_ENCODING
+ * for e = 0.  A proof: BBS_ST_INVALID_ENCODING for the shape; then the FIRST of Abar, Bbar, D that fails decides, with its
+ * code or, for the identity, BBS_ST_INVALID_ENCODING; then BBS_ST_NONCANONICAL for any of e^, r1^, r3^, m^_j, c >= r.  The
+ * batched forms (`*_from_octets_batch`, bbs_*verify_octets_*, bbs_*_wire_*) decide in the same order.
  * ------------------------------------------------------------------------------------------ */
 int bbs_signature_to_octets(int curve, const uint8_t* sig_record, uint8_t* out /* fp_bytes + 32 */);
 int bbs_signature_from_octets(int curve, const uint8_t* octets, uint8_t* sig_record_out);
