@@ -211,7 +211,11 @@ static int selftest_fp4sqr(int hi, const uint8_t* a, const uint8_t* b, uint8_t* 
     if (!fe_from_le_bytes<P>(a, A.c0) || !fe_from_le_bytes<P>(a + FPB, A.c1) || !fe_from_le_bytes<P>(b, B.c0) ||
         !fe_from_le_bytes<P>(b + FPB, B.c1)) return BBS_E_ARG;
     Fp2<C> r;
-    if constexpr (C::K::XI_C0 == 1) r = (hi & 2) ? fp4_sqr_part2<C>((hi & 1) != 0, A, B) : fp4_sqr_part<C>((hi & 1) != 0, A, B);
+    // hi bits: 1 = the high half, 2 = the two-pass arm, 4 = the xi form of the high half (xi = 1 + u, one-pass arm only)
+    if (hi & 4) {
+        if (C::K::XI_C0 != 1 || (hi & 3) != 1) return BBS_E_ARG;
+    }
+    if constexpr (C::K::XI_C0 == 1) r = (hi & 2) ? fp4_sqr_part2<C>((hi & 1) != 0, A, B) : fp4_sqr_part<C>((hi & 1) != 0, A, B, (hi & 4) != 0);
     else r = fp4_sqr_part<C>((hi & 1) != 0, A, B);
     fe_to_le_bytes<P>(r.c0, out);
     fe_to_le_bytes<P>(r.c1, out + FPB);

@@ -206,7 +206,9 @@ __device__ __forceinline__ Fp2<C> d_cyclo_sqr(const Lane6& L, const Fp2<C>& g) {
     Fp2<C> px = d_coef<C>(L, g, partner);
     Fp2<C> sq;                                              // lane m<3: X2[0] of pair m ; m>=3: X2[1] of pair m-3
     if constexpr (C::K::XI_C0 == 1) {                       // BLS12-381; BN254 (xi = 9 + u, 10 limbs): measured no faster, keeps the form below
-        sq = fp4_sqr_part<C>(hi, g, px);                    // tower.hpp: four column products, one reduction pair
+        // tower.hpp: four column products, one combine for both lanes, one reduction pair.  Lane 5's only reader is lane 1,
+        // which wants xi C2[1]: lane 5 runs the high row on xi A and publishes the product with xi.
+        sq = fp4_sqr_part<C>(hi, g, px, L.m == 5);
     } else {
         Fp2<C> u = f2_sqr<C>(g);                            // x0^2 on the low lane, x1^2 on the high lane
         Fp2<C> v = f2_sqr<C>(f2_add<C>(g, px));             // (x0 + x1)^2 on both
@@ -224,7 +226,7 @@ __device__ __forceinline__ Fp2<C> d_cyclo_sqr(const Lane6& L, const Fp2<C>& g) {
     // pull pattern: 0<-0, 3<-3, 1<-5, 4<-2, 2<-1, 5<-4
     const int src = (L.m == 0) ? 0 : (L.m == 3) ? 3 : (L.m == 1) ? 5 : (L.m == 4) ? 2 : (L.m == 2) ? 1 : 4;
     Fp2<C> t = d_coef<C>(L, sq, src);
-    t = f2_sel<C>(L.m == 1, f2_mul_xi<C>(t), t);
+    if constexpr (C::K::XI_C0 != 1) t = f2_sel<C>(L.m == 1, f2_mul_xi<C>(t), t);    // BLS12-381: lane 5 published xi C2[1]
     // odd lanes: 3 t + 2 g ; even lanes: 3 t - 2 g
     return f2_lin_pm<C, 3, 2>(t, g, (L.m & 1) != 0);
 }

@@ -228,6 +228,21 @@ BBS_HD Fp2<C> f2acc_finish_hi(F2AccHi<C>& acc, const F2AccMid<C>& st) {
 // limb-column products and one reduction pair, the same instruction stream for both halves (operands selected by
 // `hi`; the two lanes of a pair in pairing_dist.hpp run it side by side):
 //   low  half (A = x0, B = x1):  x0^2 + xi x1^2 ;  high half (A = x1, B = x0):  2 x0 x1
+//
+// xi = 1 + u (BLS12-381), dA = A0 - A1, dB = B0 - B1 reduced, sA = A0 + A1, sB = B0 + B1 lazy -- the UNIFORM form:
+//   slot      low                 high                xi form of high (A0 := dA, A1 := sA, i.e. xi A for A)
+//   X1        sA dA               (2 A0) B0           (2 dA) B0
+//   X2        (2 A0) A1           (2 A0) B1           (2 dA) B1
+//   X3        sB dB               A1 dB               sA dB
+//   X4        (2 B0) B1           A1 sB               sA sB
+//   re = X1 + K p^2 + X3 - X4 ;  im = X2 + X3 + X4        for every row: no select in the column loop
+//   high: re = 2 A0 B0 + A1 (B0 - B1) - A1 (B0 + B1) = 2 (A0 B0 - A1 B1),  im = 2 A0 B1 + 2 A1 B0.
+// The xi form (XIH) returns xi * 2 x0 x1: the lane whose only reader wants the product with xi publishes it (lane 5 of
+// pairing_dist.hpp d_cyclo_sqr).  K p^2 is X1's initial value; X3 is accumulated once and starts both sums.
+// Weights (units of a product of two normal elements, tools/gen_params.py fp4_sqr_rows asserts every row against WP2X):
+//   low re +4 -2, im 6 ;  high re +3 -2, im 5 ;  xi form re +4 -4, im 8 (no lift on im: 8 maxcol + reduction < 2^64).
+//
+// xi = 9 + u (BN254) -- the form measured no faster than two squarings, kept host-tested:
 //   slot      low                            high
 //   X1        (A0 + A1)(A0 - A1)             2 A0 B0
 //   X2        2 A0 A1                        2 A1 B1
@@ -235,44 +250,71 @@ BBS_HD Fp2<C> f2acc_finish_hi(F2AccHi<C>& acc, const F2AccMid<C>& st) {
 //   X4        2 B0 B1                        2 A1 B0
 //   re = X1 + K p^2 + (low ? c X3 - X4 : -X2) ;  im = X3 + (low ? c X4 + X2 : X4)
 // 4 N^2 + 2 N^2 multiply-accumulates instead of two fused Fp2 squares (8 N^2) plus their linear chains.
-// Column bounds: differences are taken reduced (normal limbs); for c = 9 (BN254) the sums as well, so that
-// c X3 and c X4 stay below 2^63.5 (N = 10).  Host-testable: bbs_selftest_fp4sqr.
+// Column bounds: differences are taken reduced (normal limbs); for c = 9 the sums as well, so that
+// c X3 and c X4 stay below 2^63.5 (N = 10).  Host-testable: bbs_selftest_fp4sqr (hi | 4: the xi form).
 template <class C>
-BBS_HD Fp2<C> fp4_sqr_part(bool hi, const Fp2<C>& A, const Fp2<C>& B) {
+BBS_HD Fp2<C> fp4_sqr_part(bool hi, const Fp2<C>& A, const Fp2<C>& B, bool xih = false) {
     using P = typename C::FpP;
     constexpr int N = P::N;
     constexpr uint32_t XC = C::K::XI_C0;
     const Fp<C> dA = fe_sub<P>(A.c0, A.c1), dB = fe_sub<P>(B.c0, B.c1);
-    Fp<C> sA, sB;
-    if constexpr (XC == 1) { sA = fe_add_nr<P>(A.c0, A.c1); sB = fe_add_nr<P>(B.c0, B.c1); }
-    else { sA = fe_add<P>(A.c0, A.c1); sB = fe_add<P>(B.c0, B.c1); }
-    uint32_t l1[N], r1[N], l2[N], r2[N], l3[N], r3[N], l4[N], r4[N];
+    if constexpr (XC == 1) {
+        const Fp<C> sA = fe_add_nr<P>(A.c0, A.c1), sB = fe_add_nr<P>(B.c0, B.c1);
+        uint32_t l1[N], r1[N], l2[N], r2[N], l3[N], r3[N], l4[N], r4[N];
 #pragma unroll
-    for (int i = 0; i < N; i++) {
-        const uint32_t a0 = A.c0.v[i], a1 = A.c1.v[i], b0 = B.c0.v[i], b1 = B.c1.v[i];
-        l1[i] = hi ? (a0 << 1) : sA.v[i];    r1[i] = hi ? b0 : dA.v[i];
-        l2[i] = hi ? (a1 << 1) : (a0 << 1);  r2[i] = hi ? b1 : a1;
-        l3[i] = hi ? (a0 << 1) : sB.v[i];    r3[i] = hi ? b1 : dB.v[i];
-        l4[i] = hi ? (a1 << 1) : (b0 << 1);  r4[i] = hi ? b0 : b1;
-    }
-    uint64_t x1[2 * N - 1], x2[2 * N - 1], x3[2 * N - 1], x4[2 * N - 1];
-    r28::cols_zero<P>(x1); r28::cols_zero<P>(x2); r28::cols_zero<P>(x3); r28::cols_zero<P>(x4);
-    r28::cols_mac<P>(x1, l1, r1);
-    r28::cols_mac<P>(x2, l2, r2);
-    r28::cols_mac<P>(x3, l3, r3);
-    r28::cols_mac<P>(x4, l4, r4);
+        for (int i = 0; i < N; i++) {
+            const uint32_t a0 = A.c0.v[i], a1 = A.c1.v[i], b0 = B.c0.v[i], b1 = B.c1.v[i];
+            const uint32_t e0 = xih ? dA.v[i] : a0, e1 = xih ? sA.v[i] : a1;      // xi A in place of A (high rows only)
+            l2[i] = e0 << 1;                     r2[i] = hi ? b1 : a1;
+            l1[i] = hi ? l2[i] : sA.v[i];        r1[i] = hi ? b0 : dA.v[i];
+            l3[i] = hi ? e1 : sB.v[i];           r3[i] = dB.v[i];
+            l4[i] = hi ? e1 : (b0 << 1);         r4[i] = hi ? sB.v[i] : b1;
+        }
+        uint64_t re[2 * N - 1], im[2 * N - 1], x4[2 * N - 1];
+        r28::cols_zero<P>(im);
+        r28::cols_mac<P>(im, l3, r3);                                              // X3, once
 #pragma unroll
-    for (int c = 0; c < 2 * N - 1; c++) {
-        const uint64_t cx3 = XC * x3[c], cx4 = XC * x4[c];
-        const uint64_t re = x1[c] + P::WP2X[c] + (hi ? (0 - x2[c]) : (cx3 - x4[c]));
-        const uint64_t im = x3[c] + (hi ? x4[c] : (cx4 + x2[c]));
-        x1[c] = re;
-        x2[c] = im;
+        for (int c = 0; c < 2 * N - 1; c++) re[c] = im[c] + P::WP2X[c];
+        r28::cols_mac<P>(re, l1, r1);
+        r28::cols_mac<P>(im, l2, r2);
+        r28::cols_zero<P>(x4);
+        r28::cols_mac<P>(x4, l4, r4);
+#pragma unroll
+        for (int c = 0; c < 2 * N - 1; c++) { re[c] -= x4[c]; im[c] += x4[c]; }
+        Fp2<C> r;
+        r28::cols_reduce<P>(r.c0.v, re);
+        r28::cols_reduce<P>(r.c1.v, im);
+        return r;
+    } else {
+        const Fp<C> sA = fe_add<P>(A.c0, A.c1), sB = fe_add<P>(B.c0, B.c1);
+        uint32_t l1[N], r1[N], l2[N], r2[N], l3[N], r3[N], l4[N], r4[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const uint32_t a0 = A.c0.v[i], a1 = A.c1.v[i], b0 = B.c0.v[i], b1 = B.c1.v[i];
+            l1[i] = hi ? (a0 << 1) : sA.v[i];    r1[i] = hi ? b0 : dA.v[i];
+            l2[i] = hi ? (a1 << 1) : (a0 << 1);  r2[i] = hi ? b1 : a1;
+            l3[i] = hi ? (a0 << 1) : sB.v[i];    r3[i] = hi ? b1 : dB.v[i];
+            l4[i] = hi ? (a1 << 1) : (b0 << 1);  r4[i] = hi ? b0 : b1;
+        }
+        uint64_t x1[2 * N - 1], x2[2 * N - 1], x3[2 * N - 1], x4[2 * N - 1];
+        r28::cols_zero<P>(x1); r28::cols_zero<P>(x2); r28::cols_zero<P>(x3); r28::cols_zero<P>(x4);
+        r28::cols_mac<P>(x1, l1, r1);
+        r28::cols_mac<P>(x2, l2, r2);
+        r28::cols_mac<P>(x3, l3, r3);
+        r28::cols_mac<P>(x4, l4, r4);
+#pragma unroll
+        for (int c = 0; c < 2 * N - 1; c++) {
+            const uint64_t cx3 = XC * x3[c], cx4 = XC * x4[c];
+            const uint64_t re = x1[c] + P::WP2X[c] + (hi ? (0 - x2[c]) : (cx3 - x4[c]));
+            const uint64_t im = x3[c] + (hi ? x4[c] : (cx4 + x2[c]));
+            x1[c] = re;
+            x2[c] = im;
+        }
+        Fp2<C> r;
+        r28::cols_reduce<P>(r.c0.v, x1);
+        r28::cols_reduce<P>(r.c1.v, x2);
+        return r;
     }
-    Fp2<C> r;
-    r28::cols_reduce<P>(r.c0.v, x1);
-    r28::cols_reduce<P>(r.c1.v, x2);
-    return r;
 }
 
 // fp4_sqr_part with the four limb-column products accumulated in two passes (columns 0 .. N-1, then N .. 2N-2): 4 x N

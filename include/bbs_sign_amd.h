@@ -1082,7 +1082,8 @@ int bbs_selftest_glv_split(int curve, const uint8_t* k32, uint8_t* k1_16, uint8_
 int bbs_selftest_mul3(int curve, int glv, const uint8_t* points, const uint8_t* scalars, uint8_t* out_affine);
 /* Host arithmetic self-test (no GPU): one half of an Fp4 square as the pairing kernel computes it (four limb-column
  * products, one reduction pair): hi = 0: a^2 + xi b^2, hi = 1: 2 a b, for a, b in Fp2 (c0 || c1, canonical LE);
- * hi | 2 (BLS12-381): the same through the two-pass column accumulators. */
+ * hi | 2 (BLS12-381): the same through the two-pass column accumulators; hi = 1 | 4 (BLS12-381): xi * 2 a b, the
+ * form the high lane of the pair (g2, g5) publishes (any other use of bit 4 is BBS_E_ARG). */
 int bbs_selftest_fp4sqr(int curve, int hi, const uint8_t* a, const uint8_t* b, uint8_t* out);
 int bbs_selftest_f2dot(int curve, size_t n_terms, const uint8_t* a, const uint8_t* b, const uint8_t* weights,
                        uint8_t* out);

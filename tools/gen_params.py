@@ -36,8 +36,38 @@ def raw_arr(name, ws):
     return "    static constexpr uint32_t %s[%d] = {%s};\n" % (name, len(ws), body)
 
 
-def field28_struct(name, mod, n, nc, bound_mult):
-    """Base field in radix 2^28 (carry-free multiply-accumulate columns, see field.hpp)."""
+def fp4_sqr_rows(name, mod, n, bound_mult, amax, wp2x, k6):
+    """Column and value bounds of the uniform Fp4 half-square (tower.hpp fp4_sqr_part, xi = 1 + u): every row of its
+    table combines as re = X1 + K p^2 + X3 - X4, im = X2 + X3 + X4.  An operand is normal (a value or a reduced
+    difference: limbs <= amax, value < BOUND p), lazy (a limb-wise sum of two normal ones) or doubled (a normal one
+    shifted left by one); the last two have limbs <= 2 amax and values < 2 BOUND p."""
+    ncol = 2 * n - 1
+    norm = (list(amax), bound_mult * mod)
+    wide = ([2 * a for a in amax], 2 * bound_mult * mod)            # lazy sum or doubled operand
+    rows = {
+        #            X1            X2            X3            X4
+        "low":     ((wide, norm), (wide, norm), (wide, norm), (wide, norm)),     # sA dA, (2 A0) A1, sB dB, (2 B0) B1
+        "high":    ((wide, norm), (wide, norm), (norm, norm), (norm, wide)),     # (2 A0) B0, (2 A0) B1, A1 dB, A1 sB
+        "high xi": ((wide, norm), (wide, norm), (wide, norm), (wide, wide)),     # (2 dA) B0, (2 dA) B1, sA dB, sA sB
+    }
+    slack = n * (1 << 56) + (1 << 40)                               # what the reduction adds to a column, and its carry
+    for row, prods in rows.items():
+        for (l, _), (r, _) in prods:
+            assert all(x < (1 << 30) for x in l) and all(x < (1 << 29) for x in r), (name, row)      # r28::cols_mac operands
+        col = [[sum(l[0][i] * r[0][k - i] for i in range(n) if 0 <= k - i < n) for k in range(ncol)] for l, r in prods]
+        val = [l[1] * r[1] for l, r in prods]
+        for k in range(ncol):
+            assert col[3][k] <= wp2x[k], (name, row, k, "subtracted column above the lift")
+            assert col[0][k] + col[2][k] + wp2x[k] + slack < (1 << 64), (name, row, k, "re column")
+            assert col[1][k] + col[2][k] + col[3][k] + slack < (1 << 64), (name, row, k, "im column")
+        # (value) / R + p < 2p
+        assert val[0] + val[2] + k6 * mod * mod < (mod << (28 * n)), (name, row, "re value")
+        assert val[1] + val[2] + val[3] < (mod << (28 * n)), (name, row, "im value")
+
+
+def field28_struct(name, mod, n, nc, bound_mult, fp4_uniform=False):
+    """Base field in radix 2^28 (carry-free multiply-accumulate columns, see field.hpp).  fp4_uniform: the field of a
+    curve with xi = 1 + u, whose cyclotomic square runs the uniform four-product form (fp4_sqr_rows)."""
     R = 1 << (28 * n)
     inv = (-pow(mod, -1, 1 << 28)) % (1 << 28)
     E = mod.bit_length()
@@ -112,6 +142,8 @@ def field28_struct(name, mod, n, nc, bound_mult):
             adj6 = cand
             break
     assert adj6 is not None, name
+    if fp4_uniform:
+        fp4_sqr_rows(name, mod, n, bound_mult, amax, adj6, K6)
     s += "    // K p^2 (K = %d) lifted for column sums of total weight <= 6, see r28::cols_* / F2Acc\n" % K6
     s += "    static constexpr uint64_t WP2X[%d] = {%s};\n" % (2 * n - 1, ", ".join("0x%016xull" % v for v in adj6))
     # BOUND * p with 2^28 borrowed into every lower limb: a - b + SUBM is non-negative limb by limb
@@ -498,7 +530,7 @@ def main():
              8255268479661695615178834896135584953541182794935974658059743263102507888551)
 
     s = "// GENERATED by tools/gen_params.py -- do not edit.\n#pragma once\n#include <cstdint>\n\nnamespace bbs {\n\n"
-    s += field28_struct("BlsFpParams", bls_p, 14, 12, 2)
+    s += field28_struct("BlsFpParams", bls_p, 14, 12, 2, fp4_uniform=True)
     s += field_struct("BlsFrParams", bls_r, 8)
     s += field28_struct("BnFpParams", bn_p, 10, 8, 3)
     s += field_struct("BnFrParams", bn_r, 8)
