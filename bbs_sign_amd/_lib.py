@@ -127,6 +127,22 @@ SIGNATURES = {
     "bbs_core_verify_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
     "bbs_verify_wire_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_verify_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    # verification under a job-local key set: the keyed forms with n_keys, pk_octets in front of key_index
+    "bbs_core_proof_verify_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,
+                                                    c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_proof_verify_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p,
+                                                   c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_proof_verify_wire_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p,
+                                                    c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_proof_verify_wire_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u64p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p,
+                                                   c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_core_verify_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_verify_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_verify_wire_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_verify_wire_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_job_key_statuses": (ci, [vp, c_i8p, sz, ctypes.POINTER(sz)]),
+    "bbs_selftest_key_len_rows": (ci, [vp, sz, c_u8p, ci, c_u8p, c_i8p]),
+    "bbs_selftest_hash_ctx_bytes": (sz, []),
     # keyed proof_gen: as the un-keyed forms, key_index after n
     "bbs_core_proof_gen_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
                                              c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),

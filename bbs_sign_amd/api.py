@@ -362,6 +362,7 @@ class _IssuerEngine:
         self.L = L
         self.index: Dict[object, int] = {}
         self.sk_index: Dict[int, int] = {}          # sign_many_issuers: secret key -> its index in the signing set
+        self.octets: Dict[object, bytes] = {}       # register_keys=False: key -> its compressed string (key_octets)
         self.eng = Engine(curve, device=device, lib_path=lib_path, window_bits=4 if lib_path is not None else None)
         self.eng.set_generators(create_generators(curve, L + 1, lib_path), api_id(curve))
         self.eng.set_keyed_mixed_lengths(True)
@@ -383,6 +384,23 @@ class _IssuerEngine:
             first, _ = self.eng.add_public_keys(new)
             for k, pk in enumerate(new):
                 self.index[self.name(pk)] = first + k
+
+    def key_octets(self, pk_obj) -> bytes:
+        """The compressed string of a key for the job-local key sets (``register_keys=False``), remembered per key: what
+        public_key_to_octets writes, if it decodes to the same key again; otherwise (coordinates that cannot be written, a point
+        that is not on the twist: its string would name ANOTHER key) a string every decoder refuses, so that the items of such
+        a key get BBS_ST_UNKNOWN_KEY as they do when the key is registered.  The engine's key set is not touched."""
+        name = self.name(pk_obj.pk)
+        o = self.octets.get(name)
+        if o is None:
+            try:
+                o = public_key_to_octets(pk_obj)
+                if self.name(octets_to_public_key(pk_obj.curve, o, pk_obj.lib_path, pk_obj.device).pk) != name:
+                    raise BbsError(-41)
+            except BbsError:
+                o = b"\xff" * (2 * self.eng.fpb)
+            self.octets[name] = o
+        return o
 
     def keys_in_order(self):
         by_index = sorted(self.index.items(), key=lambda kv: kv[1])
@@ -446,8 +464,11 @@ def sign_many_issuers(items: Sequence[tuple]) -> list:
     return out
 
 
-def _many_issuers(items, count, to_octets, run, batch_verification=False):
+def _many_issuers(items, count, to_octets, run, batch_verification=False, register_keys=True, run_own=None):
     """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms.
+    register_keys=False: the keys are NOT registered on the cached engine -- the call deduplicates the keys of its items, writes
+    them as octets and goes through the ``*_with_keys_*`` wire form (``run_own``): the job prepares them on the device and
+    releases them, ``index`` and the engine's key set stay as they were.
     batch_verification: bbs_ctx_set_keyed_batch_verification on the cached engine for this call -- True: the library's default
     threshold; an integer >= 1: that many items per key -- with a fresh seed from the operating system, and off again
     afterwards.  Off is the state the cache keeps its engines in (nothing else holds them), so that is the prior state.  Calls
@@ -462,9 +483,20 @@ def _many_issuers(items, count, to_octets, run, batch_verification=False):
         groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
     for (curve, device, lib_path), idx in groups.items():
         its = [items[i] for i in idx]
-        ie = _issuer_engine(curve, device, lib_path, max(count(it) for it in its), [it[0].pk for it in its])
-        call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path),
-                             lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
+        ie = _issuer_engine(curve, device, lib_path, max(count(it) for it in its), [it[0].pk for it in its] if register_keys else [])
+        if register_keys:
+            call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path),
+                                 lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
+        else:
+            def own(octs, kept):
+                local: Dict[object, int] = {}
+                key_octets = []
+                for it in kept:
+                    if ie.name(it[0].pk) not in local:
+                        local[ie.name(it[0].pk)] = len(key_octets)
+                        key_octets.append(ie.key_octets(it[0]))
+                return run_own(ie.eng, key_octets, [local[ie.name(it[0].pk)] for it in kept], octs, kept)
+            call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path), own, at=1)
         if batch_verification:
             with _bv_lock:
                 ie.eng.set_keyed_batch_verification(True, None, min_items)
@@ -479,7 +511,7 @@ def _many_issuers(items, count, to_octets, run, batch_verification=False):
     return out
 
 
-def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False) -> list:
+def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True) -> list:
     """PublicKey.verify for many items ``(pk, signature, header, messages)`` of ANY issuers and ANY message counts, in ONE
     device call per (curve, device, lib_path): one cached engine with bbs_ctx_set_keyed_mixed_lengths on, whose L is the
     largest count seen and whose key set grows by appending (a key is registered once).  Entry i is the boolean
@@ -489,19 +521,27 @@ def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False
     fails with a BbsRuntimeError from bbs_ctx_set_public_key.
     ``batch_verification=True`` switches bbs_ctx_set_keyed_batch_verification on for this call: the items of an issuer that
     has enough of them in the list (the library's default threshold; an integer >= 1 instead of True: that many) are checked by
-    16 combined pairing products; the entries are the same."""
+    16 combined pairing products; the entries are the same.
+    ``register_keys=False`` is for a verifier that does not know its issuers in advance: the keys of THIS list travel with the
+    job (bbs_verify_wire_with_keys_batch), are prepared on the device by the job and released with it; the cached engine's key
+    set does not grow.  The entries are the same.  Worth it for lists that bring many keys that will not be seen again; a
+    handful of recurring issuers is served better by the default, which prepares a key once."""
     return _many_issuers(items, lambda it: len(it[3]), signature_to_octets,
                          lambda eng, kidx, octs, its: eng.verify_wire_keyed_batch(kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]),
-                         batch_verification)
+                         batch_verification, register_keys,
+                         lambda eng, keys, kidx, octs, its: eng.verify_wire_with_keys_batch(keys, kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]))
 
 
-def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False) -> list:
+def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True) -> list:
     """proof_verify for many items ``(pk, proof, header, ph, disclosed_messages, disclosed_indexes)`` of any issuers and any
-    message counts (commitments + disclosed indexes each), as verify_many_issuers (``batch_verification`` included)."""
+    message counts (commitments + disclosed indexes each), as verify_many_issuers (``batch_verification`` and ``register_keys``
+    included)."""
     return _many_issuers(items, lambda it: len(it[1].commitments) + len(it[5]), proof_to_octets,
                          lambda eng, kidx, octs, its: eng.proof_verify_wire_keyed_batch(
                              kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]),
-                         batch_verification)
+                         batch_verification, register_keys,
+                         lambda eng, keys, kidx, octs, its: eng.proof_verify_wire_with_keys_batch(
+                             keys, kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]))
 
 
 def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) -> list:

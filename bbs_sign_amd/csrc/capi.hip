@@ -337,18 +337,25 @@ static int empty_raw_batch(const uint64_t*& msg_byte_off, const uint64_t* msg_it
     return BBS_OK;
 }
 // Each single-key export and its keyed twin (keyed.hpp: the context's key set instead of its one public key, item i under
-// key key_index[i]) are one function; the single-key export passes no key_index.
+// key key_index[i]) are one function; the single-key export passes no key_index.  The bbs_*_with_keys_* exports are the keyed
+// function with the key set of the call (job_form.hpp JobKeys) in `wk`.
+struct WithKeys { size_t n_keys; const uint8_t* pk_octets; };
+template <class In>
+static In with_keys(In in, const WithKeys* wk) {
+    if (wk) { in.job_keys = true; in.n_keys = wk->n_keys; in.pk_octets = wk->pk_octets; }
+    return in;
+}
 template <bool KEYED>
 static int core_proof_verify_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proofs_fixed,
                                     const uint8_t* commitments, const uint64_t* commit_off, const uint8_t* disclosed_msgs,
                                     const uint64_t* dmsg_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
                                     const uint8_t* headers, const uint64_t* hdr_off, const uint8_t* ph, const uint64_t* ph_off,
-                                    int8_t* status, bbs_job** job_out) {
+                                    int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
     if (!ctx || !status || !job_out) return BBS_E_ARG;
-    return verify_submit<KEYED>(ctx, n, PvIn{.proofs_fixed = proofs_fixed, .commitments = commitments, .commit_off = commit_off,
+    return verify_submit<KEYED>(ctx, n, with_keys(PvIn{.proofs_fixed = proofs_fixed, .commitments = commitments, .commit_off = commit_off,
                                              .disclosed_msgs = disclosed_msgs, .dmsg_off = dmsg_off, .disclosed_idx = disclosed_idx,
                                              .didx_off = didx_off, .headers = headers, .hdr_off = hdr_off, .ph = ph, .ph_off = ph_off,
-                                             .key_index = key_index}, status, job_out);
+                                             .key_index = key_index}, wk), status, job_out);
 }
 // the public proof_verify of the reference for a fixed number of messages, in one call: proof octets AND the disclosed
 // messages as raw bytes (msg_to_scalars on the device in front of the ingest stage)
@@ -356,31 +363,31 @@ template <bool KEYED>
 static int proof_verify_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* proof_octets, const uint64_t* oct_off,
                                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                                     const uint64_t* disclosed_idx, const uint64_t* didx_off, const uint8_t* headers, const uint64_t* hdr_off,
-                                    const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out) {
+                                    const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
     if (!ctx || !status || !job_out || (n && (!oct_off || !msg_item_off))) return BBS_E_ARG;
     if (int rc = empty_raw_batch(msg_byte_off, msg_item_off, n)) return rc;
-    return verify_submit<KEYED>(ctx, n, PvIn{.dmsg_off = msg_item_off, .disclosed_idx = disclosed_idx, .didx_off = didx_off,
+    return verify_submit<KEYED>(ctx, n, with_keys(PvIn{.dmsg_off = msg_item_off, .disclosed_idx = disclosed_idx, .didx_off = didx_off,
                                              .headers = headers, .hdr_off = hdr_off, .ph = ph, .ph_off = ph_off,
                                              .proof_octets = proof_octets, .oct_off = oct_off, .msg_bytes = msg_bytes,
-                                             .msg_byte_off = msg_byte_off, .key_index = key_index}, status, job_out);
+                                             .msg_byte_off = msg_byte_off, .key_index = key_index}, wk), status, job_out);
 }
 template <bool KEYED>
 static int core_verify_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures, const uint8_t* messages,
-                              const uint64_t* msg_off, const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out) {
+                              const uint64_t* msg_off, const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
     if (!ctx || !status || !job_out) return BBS_E_ARG;
-    return verify_submit<KEYED>(ctx, n, VfIn{.signatures = signatures, .messages = messages, .msg_off = msg_off, .headers = headers,
-                                             .hdr_off = hdr_off, .key_index = key_index}, status, job_out);
+    return verify_submit<KEYED>(ctx, n, with_keys(VfIn{.signatures = signatures, .messages = messages, .msg_off = msg_off, .headers = headers,
+                                             .hdr_off = hdr_off, .key_index = key_index}, wk), status, job_out);
 }
 // the reference's PUBLIC verify for a context's number of messages, in one call: signature octet strings and raw messages
 // in (msg_to_scalars on the device)
 template <bool KEYED>
 static int verify_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets, const uint8_t* msg_bytes,
                               const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* headers, const uint64_t* hdr_off,
-                              int8_t* status, bbs_job** job_out) {
+                              int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
     if (!ctx || !status || !job_out || (n && (!signature_octets || !msg_item_off))) return BBS_E_ARG;
     if (int rc = empty_raw_batch(msg_byte_off, msg_item_off, n)) return rc;
-    return verify_submit<KEYED>(ctx, n, VfIn{.msg_off = msg_item_off, .headers = headers, .hdr_off = hdr_off, .signature_octets = signature_octets,
-                                             .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off, .key_index = key_index}, status, job_out);
+    return verify_submit<KEYED>(ctx, n, with_keys(VfIn{.msg_off = msg_item_off, .headers = headers, .hdr_off = hdr_off, .signature_octets = signature_octets,
+                                             .msg_bytes = msg_bytes, .msg_byte_off = msg_byte_off, .key_index = key_index}, wk), status, job_out);
 }
 
 // the reference's PUBLIC proof_gen (src/proof_gen.rs:78-113) in one call: signature octets and raw messages in, proof octets out
@@ -657,6 +664,17 @@ int bbs_job_bv_verdicts(bbs_job* job, int8_t* verdicts, size_t cap, size_t* n_ou
     std::memcpy(verdicts, v.data(), v.size());
     return BBS_OK;
 }
+int bbs_job_key_statuses(bbs_job* job, int8_t* out, size_t cap, size_t* n_out) {
+    if (!job || !n_out) return BBS_E_ARG;
+    *n_out = 0;
+    if (!job->key_statuses) return BBS_E_STATE;       // the job has no key set of its own
+    std::vector<int8_t> v;
+    if (const int rc = job->key_statuses(v)) return rc;
+    *n_out = v.size();
+    if (cap < v.size() || (!out && !v.empty())) return BBS_E_ARG;
+    if (!v.empty()) std::memcpy(out, v.data(), v.size());
+    return BBS_OK;
+}
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int cap, int* n_stages) {
     if (!job || reps < 1) return BBS_E_ARG;
     if (job->use()) return BBS_E_HIP;
@@ -853,6 +871,58 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
                                 const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h, const uint64_t* ho, int8_t* status) {
     bbs_job* job = nullptr;
     return wait_and_free(bbs_verify_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
+}
+// verification under a job-local key set (job_form.hpp JobKeys): the keyed exports with the key set of the call in front of key_index
+int bbs_core_proof_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* pf,
+                                           const uint8_t* cm, const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di,
+                                           const uint64_t* dio, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                           int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return core_proof_verify_submit<true>(ctx, n, key_index, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, status, job_out, &wk);
+}
+int bbs_core_proof_verify_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* pf,
+                                          const uint8_t* cm, const uint64_t* cmo, const uint8_t* dm, const uint64_t* dmo, const uint64_t* di,
+                                          const uint64_t* dio, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                          int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_proof_verify_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, pf, cm, cmo, dm, dmo, di, dio, h, ho, ph, pho, status, &job), job);
+}
+int bbs_proof_verify_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* oct,
+                                           const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                           const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio, const uint8_t* h,
+                                           const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return proof_verify_wire_submit<true>(ctx, n, key_index, oct, oct_off, msg_bytes, msg_byte_off, msg_item_off, di, dio, h, ho, ph, pho, status, job_out, &wk);
+}
+int bbs_proof_verify_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* oct,
+                                          const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                          const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio, const uint8_t* h,
+                                          const uint64_t* ho, const uint8_t* ph, const uint64_t* pho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_proof_verify_wire_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, oct, oct_off, msg_bytes, msg_byte_off, msg_item_off, di, dio,
+                                                                h, ho, ph, pho, status, &job), job);
+}
+int bbs_core_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sigs,
+                                     const uint8_t* m, const uint64_t* mo, const uint8_t* h, const uint64_t* ho, int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return core_verify_submit<true>(ctx, n, key_index, sigs, m, mo, h, ho, status, job_out, &wk);
+}
+int bbs_core_verify_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sigs,
+                                    const uint8_t* m, const uint64_t* mo, const uint8_t* h, const uint64_t* ho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_verify_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, sigs, m, mo, h, ho, status, &job), job);
+}
+int bbs_verify_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sig_octets,
+                                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h,
+                                     const uint64_t* ho, int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return verify_wire_submit<true>(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, job_out, &wk);
+}
+int bbs_verify_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sig_octets,
+                                    const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint8_t* h,
+                                    const uint64_t* ho, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_verify_wire_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, h, ho, status, &job), job);
 }
 // the signing key set of keyed sign (runtime.hpp SignSet; registration: op_kg.hpp add_secret_keys)
 int bbs_ctx_set_secret_keys(bbs_ctx* ctx, size_t n_keys, const uint8_t* sk32, int8_t* key_status, uint8_t* pk_affine_out, int8_t* is_identity_out) {
@@ -1296,6 +1366,11 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
     if (pk_octets) { pk_affine = nullptr; is_identity = nullptr; }
     return with_curve(ctx, [&](auto* c) { return selftest_key_entries(c, n, pk_affine, is_identity, pk_octets, path, entries_out, status_out, pk_affine_out); });
 }
+int bbs_selftest_key_len_rows(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int path, uint8_t* rows_out, int8_t* status_out) {
+    if (!ctx || (path != 0 && path != 1) || (n && (!pk_octets || !rows_out || !status_out))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return selftest_key_len_rows(c, n, pk_octets, path, rows_out, status_out); });
+}
+size_t bbs_selftest_hash_ctx_bytes(void) { return sizeof(HashCtx); }
 size_t bbs_selftest_key_entry_bytes(int curve) {
     return curve == BBS_CURVE_BLS12_381 ? sizeof(KeyEntry<BlsCurve>) : curve == BBS_CURVE_BN254 ? sizeof(KeyEntry<BnCurve>) : 0;
 }

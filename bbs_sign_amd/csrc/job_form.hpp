@@ -30,13 +30,44 @@ struct KeyedBv {
     KeyedBvDecideArgs dec{};
     int8_t* verdicts = nullptr;              // [16 G], cleared before every run: a check that never ran reads as failed
 };
+// A job-local key set (bbs_*_with_keys_*): the distinct keys of ONE job arrive as compressed octets with the call, travel in the
+// job's staging image and are prepared on the device by the job itself -- KeyBuild (stages_key.hpp), and KeyLenBuild where the job
+// is of mixed counts -- on its main stream in front of its ingest kernel, into arrays the job owns and releases.  The context's
+// key set is neither read nor changed.  The keys are prepared with the upload, once, as the ingest kernel runs once: a job
+// that is run again (bbs_job_run) finds its entries, its key statuses and its ingest statuses as the first run did.
+// What the host cannot know when it plans such a job is which keys are accepted: keyed_order gives every index < n_keys its slot,
+// JobKeyGate decides on the device.  op_key.hpp has the launches (the kernels live in the key units only).
+template <class C>
+struct JobKeys {
+    bool on = false;
+    size_t n_keys = 0;
+    const uint8_t* pk_octets = nullptr;      // the caller's array (read by keyed_order only)
+    size_t oct_at = 0;                       // place of the strings in the staging words, in words
+    const uint32_t* d_oct = nullptr;         // the strings on the device
+    KeyEntry<C>* entries = nullptr;          // [n_keys]
+    int8_t* status = nullptr;                // [n_keys] KeyBuild's codes: 1, BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE
+    HashCtx* rows = nullptr;                 // [n_keys][L + 1], jobs of mixed counts only
+    std::vector<uint32_t> grp_key;           // keyed batch verification: key of group g (bbs_job_bv_report leaves refused keys out)
+    std::vector<uint32_t> grp_items;
+};
 // verify / proof_verify: plus the keyed pairing order
 template <class C>
 struct PairedJobForm : JobForm<C> {
     PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
     bool unit = false;                       // line form of the key set the job holds (KeySet::unit)
     KeyedBv<C> bv{};                         // keyed batch verification, where the context's switch was on at upload
+    JobKeys<C> jk{};                         // the job's own keys (bbs_*_with_keys_*); off: the context's key set
 };
+// op_key.hpp (instantiated in tu_key_*.hip).  prepare: allocates status (and rows, stride = L + 1; 0: none) through `alloc`
+// (device bytes owned by the job, null = no memory), clears the entries and launches KeyBuild (and KeyLenBuild) on st.
+// gate: JobKeyGate behind the ingest kernel.
+template <class C> int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uint32_t stride, const std::function<void*(size_t)>& alloc,
+                                        std::shared_ptr<const void>& blob_held);
+template <class C> int job_keys_gate(rt::Stream& st, const JobKeys<C>& jk, bool unit, size_t n, const uint32_t* kidx, int8_t* status0);
+extern template int job_keys_prepare<BlsCurve>(Ctx<BlsCurve>*, rt::Stream&, JobKeys<BlsCurve>&, bool, uint32_t, const std::function<void*(size_t)>&, std::shared_ptr<const void>&);
+extern template int job_keys_prepare<BnCurve>(Ctx<BnCurve>*, rt::Stream&, JobKeys<BnCurve>&, bool, uint32_t, const std::function<void*(size_t)>&, std::shared_ptr<const void>&);
+extern template int job_keys_gate<BlsCurve>(rt::Stream&, const JobKeys<BlsCurve>&, bool, size_t, const uint32_t*, int8_t*);
+extern template int job_keys_gate<BnCurve>(rt::Stream&, const JobKeys<BnCurve>&, bool, size_t, const uint32_t*, int8_t*);
 
 // The form of an upload and its state checks.  The context's switches are read HERE, once: the checks, the stages and the
 // data of the job all go by this one look, whatever a setter does meanwhile.  What differs per operation: the key set a keyed
@@ -44,8 +75,9 @@ struct PairedJobForm : JobForm<C> {
 // the single key (pk_set, sign: sk_set).
 enum class FormOp { Verify, ProofGen, Sign };          // Verify: verify and proof_verify
 template <bool KEYED, class C>
-int decide_form(const Ctx<C>* ctx, FormOp op, size_t n, const uint32_t* key_index, Form& form) {
-    const bool have_key_set = op == FormOp::Sign ? ctx->sign_keys != nullptr : ctx->keys != nullptr;
+int decide_form(const Ctx<C>* ctx, FormOp op, size_t n, const uint32_t* key_index, Form& form, bool job_keys = false) {
+    // (job_keys: the job brings its own key set -- the context's is not looked at and need not exist)
+    const bool have_key_set = job_keys || (op == FormOp::Sign ? ctx->sign_keys != nullptr : ctx->keys != nullptr);
     const bool single_mixed = op == FormOp::Verify ? ctx->mixed_lengths : ctx->mixed_lengths_gen;
     const bool have_single_key = op == FormOp::Sign ? ctx->sk_set : ctx->pk_set;
     if constexpr (KEYED) {
@@ -152,16 +184,19 @@ void keyed_bv_plan(size_t n, const std::vector<uint32_t>& cnt, size_t min_items,
     bv.at = words.size();
     words.insert(words.end(), pw.begin(), pw.end());
 }
+// A job-local key set (jf.jk.on): the set is the job's own, every index < n_keys counts as accepted here (JobKeyGate decides on
+// the device), and the key strings follow the plan in `words`.
 template <class C, class J>
 void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJobForm<C>& jf, std::vector<uint32_t>& words) {
-    const auto ks = ctx->keys;
+    JobKeys<C>& jk = jf.jk;
+    const auto ks = jk.on ? nullptr : ctx->keys;
     j->key_set = ks;
-    const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
+    const size_t nk = jk.on ? jk.n_keys : (ks ? ks->n : 0);     // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
     std::vector<uint32_t> cnt(nk, 0);
     words.assign(n, 0);
     for (size_t i = 0; i < n; i++) {
         const uint32_t k = key_index[i];
-        const bool ok = k < nk && ks->status[k] == 1;
+        const bool ok = k < nk && (jk.on || ks->status[k] == 1);
         words[i] = ok ? k : KEY_NONE;
         if (ok) cnt[k]++;
     }
@@ -169,11 +204,21 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJ
     size_t nu = 0, ns = 0;
     keyed_slots(words.data(), n, cnt, order, nu, ns);
     words.insert(words.end(), order.begin(), order.end());
-    jf.src.keys = ks ? ks->d.template as<KeyEntry<C>>() : nullptr;
+    jf.src.keys = jk.on ? jk.entries : (ks ? ks->d.template as<KeyEntry<C>>() : nullptr);
     jf.pair.keys = jf.src.keys; jf.pair.n_uni = nu; jf.pair.n_slots = ns;
     jf.unit = ks ? ks->unit : ctx->lines_unit();
     if (ctx->keyed_bv) keyed_bv_plan<C>(n, cnt, ctx->keyed_bv_min, jf.bv, words);
+    if (!jk.on) return;
+    if (jf.bv.G)                               // (the groups in key order, as keyed_bv_plan numbers them)
+        for (size_t k = 0; k < nk; k++)
+            if (cnt[k] && cnt[k] >= ctx->keyed_bv_min) { jk.grp_key.push_back((uint32_t)k); jk.grp_items.push_back(cnt[k]); }
+    jk.oct_at = words.size();
+    words.resize(jk.oct_at + jk.n_keys * (2 * C::FpP::NC));
+    if (jk.n_keys) std::memcpy(words.data() + jk.oct_at, jk.pk_octets, jk.n_keys * 2 * Ctx<C>::FPB);
 }
+// the device half of a job-local key set, behind the staging image: d = the words' place on the device
+template <class C>
+void job_keys_bind(JobKeys<C>& jk, const uint32_t* d) { jk.d_oct = d + jk.oct_at; }
 // the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
 template <class C, class J>
 void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, JobForm<C>& jf, std::vector<uint32_t>& words) {
@@ -206,6 +251,35 @@ int keyed_sign_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, J
     jf.src.sks = ss ? ss->d.template as<uint32_t>() : nullptr;
     return BBS_OK;
 }
+// A job-local key set, first half (in front of keyed_order): the checks of the call and the entries' array, which the plan points at.
+// on = the upload came through a bbs_*_with_keys_* export.
+template <class C, class J>
+int job_keys_begin(J* j, bool on, size_t n_keys, const uint8_t* pk_octets, JobKeys<C>& jk) {
+    jk.on = on;
+    if (!on) return BBS_OK;
+    if ((n_keys && !pk_octets) || n_keys > 0xFFFFFFF0ull) return BBS_E_ARG;
+    jk.n_keys = n_keys; jk.pk_octets = pk_octets;
+    int rc = BBS_OK;
+    jk.entries = j->template scratch<KeyEntry<C>>(std::max<size_t>(n_keys, 1), rc);
+    return rc;
+}
+// second half, behind form_bind and in front of the ingest kernel: KeyBuild (and KeyLenBuild) on the job's main stream, the
+// job's own prefixes per (key, length) bound, bbs_job_key_statuses answered from the device array on request
+template <class C, class J>
+int job_keys_launch(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
+    JobKeys<C>* jk = &jf.jk;
+    if (!jk->on) return BBS_OK;
+    const uint32_t stride = jf.form == Form::KeyedMixed ? (uint32_t)ctx->L + 1 : 0;
+    auto alloc = [j](size_t b) -> void* { int rc = BBS_OK; return j->template scratch<uint8_t>(std::max<size_t>(b, 1), rc); };
+    if (const int rc = job_keys_prepare<C>(ctx, j->stream(), *jk, jf.unit, stride, alloc, j->key_blob)) return rc;
+    if (stride) jf.src.pref = jk->rows;
+    j->key_statuses = [j, jk](std::vector<int8_t>& v) {
+        v.assign(jk->n_keys, 0);
+        if (j->use() || rt::sync(j->stream())) return (int)BBS_E_HIP;
+        return (jk->n_keys && rt::d2h(v.data(), jk->status, v.size(), j->stream())) ? (int)BBS_E_HIP : (int)BBS_OK;
+    };
+    return BBS_OK;
+}
 // the device half: d = the words' place in the device copy of the staging image
 template <class C>
 void keyed_bind(JobForm<C>& jf, const uint32_t* d) { jf.src.kidx = d; }
@@ -213,6 +287,7 @@ template <class C>
 void keyed_bind(PairedJobForm<C>& jf, size_t n, const uint32_t* d) {
     jf.src.kidx = d;
     jf.pair.kidx = d; jf.pair.slot_item = d + n; jf.pair.wave_key = d + n + jf.pair.n_slots;
+    if (jf.jk.on) job_keys_bind<C>(jf.jk, d);
     KeyedBv<C>& bv = jf.bv;
     if (!bv.G) return;
     const uint32_t* b = d + bv.at;
@@ -228,6 +303,12 @@ void keyed_bind(PairedJobForm<C>& jf, size_t n, const uint32_t* d) {
 template <class J>
 int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
     return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
+}
+// the same place in a verify / proof_verify job: the context's key set, or the job's own (JobKeyGate: the device decides)
+template <class C, class J>
+int paired_keyed_gate(J* j, size_t n, const PairedJobForm<C>& jf, int8_t* status0) {
+    if (jf.jk.on) return job_keys_gate<C>(j->stream(), jf.jk, jf.unit, n, jf.src.kidx, status0);
+    return keyed_gate(j, n, jf.src.kidx, status0);
 }
 #if !defined(BBS_HOST_TWIN)
 // the keyed fused kernel over the slots of the pairing order (runtime.hpp launch_line_form)
@@ -324,6 +405,25 @@ int add_keyed_bv_stages(J* j, Ctx<C>* ctx, PairedJobForm<C>* jf, size_t n, const
         *groups = bv->G; *passed = ok; *items = bv->items;
         return (int)BBS_OK;
     };
+    // a job-local key set: the groups of the keys KeyBuild refused (all their items gated, their checks over nothing) are left
+    // out, so that the report is the one of a keyed job over the registered set, where such a key forms no group
+    if (jf->jk.on) {
+        const JobKeys<C>* jk = &jf->jk;
+        j->bv_report = [j, bv, jk](uint32_t* groups, uint32_t* passed, uint32_t* items) {
+            std::vector<int8_t> v, ks;
+            if (const int rc = j->bv_verdicts(v)) return rc;
+            if (const int rc = j->key_statuses(ks)) return rc;
+            uint32_t G = 0, ok = 0, it = 0;
+            for (uint32_t g = 0; g < bv->G; g++) {
+                if (ks[jk->grp_key[g]] != 1) continue;
+                bool all = true;
+                for (int w = 0; w < 16; w++) all &= v[(size_t)g * 16 + w] == 1;
+                G++; ok += all ? 1u : 0u; it += jk->grp_items[g];
+            }
+            *groups = G; *passed = ok; *items = it;
+            return (int)BBS_OK;
+        };
+    }
     return BBS_OK;
 }
 

@@ -1,9 +1,28 @@
 // Host orchestration of key registration (template over the curve); instantiated by tu_key_*.hip.  runtime.hpp Ctx has the
 // contract of add_keys, stages_key.hpp the device stage.
 #pragma once
-#include "runtime.hpp"
+#include "job_form.hpp"
 #include "host_codec.hpp"
 #include "stages_key.hpp"
+
+// What a launch of KeyBuild takes that depends on the curve and the line form alone: the twist constant, the stand-in point, the
+// Frobenius constants, the Miller loop count; n_steps = the steps of the walk (the workspace is sized by it).
+template <class C>
+int key_build_consts(KeyBuildArgs<C>& a, bool want_unit, size_t& n_steps) {
+    const std::vector<int> bits = miller_bits<C>();
+    n_steps = bits.size() + (C::ID == 1 ? 2 : 0);
+    for (int b : bits) n_steps += b ? 1 : 0;
+    if (bits.size() > (size_t)KEY_MAX_BITS || n_steps > (size_t)MAX_LINES) return BBS_E_STATE;
+    a.b2 = g2_b<C>();
+    const G2Aff<C> gen = g2_generator<C>();
+    a.gen_x = gen.x; a.gen_y = gen.y;
+    a.frob_x = f2_from_consts<C>(C::K::FROB[0][2][0], C::K::FROB[0][2][1]);
+    a.frob_y = f2_from_consts<C>(C::K::FROB[0][3][0], C::K::FROB[0][3][1]);
+    a.want_unit = want_unit ? 1 : 0;
+    a.n_bits = (int)bits.size();
+    for (size_t k = 0; k < bits.size(); k++) a.bits[k] = (uint8_t)bits[k];
+    return BBS_OK;
+}
 
 // One key by the host functions (host_g2.hpp, host_codec.hpp): the reference the device stage is compared with, and the path
 // of every registration call (runtime.hpp KEY_BUILD_ON_DEVICE).  e is filled completely (zero behind the lines); the status is the stage's.  The line
@@ -85,17 +104,15 @@ int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const in
     }
     const size_t in_bytes = n * (oct ? 2 : 4) * FPB;
     DevBuf d_in, d_inf, d_st, d_rec, d_io, d_ws, d_blob;
-    const std::vector<int> bits = miller_bits<C>();
-    size_t n_steps = bits.size() + (C::ID == 1 ? 2 : 0);
-    for (int b : bits) n_steps += b ? 1 : 0;
-    if (bits.size() > (size_t)KEY_MAX_BITS || n_steps > (size_t)MAX_LINES) return BBS_E_STATE;
+    KeyBuildArgs<C> a{};
+    size_t n_steps = 0;
+    if (const int rc = key_build_consts<C>(a, lines_unit(), n_steps)) return rc;
     if (d_in.alloc(in_bytes) || d_st.alloc(n) || d_blob.alloc(blob.size()) || d_ws.alloc(key_build_ws_words<C>(n_steps) * n * 4)) return BBS_E_NOMEM;
     if (oct ? (d_rec.alloc(n * 4 * FPB) || d_io.alloc(n)) : (is_inf && d_inf.alloc(n))) return BBS_E_NOMEM;
     auto fail = [&](int rc) { (void)rt::sync(stream); return rc; };      // the buffers must not go back while the stream uses them
     if (rt::h2d_async(d_in.p, oct ? oct : rec, in_bytes, stream) || rt::h2d_async(d_blob.p, blob.data(), blob.size(), stream)) return fail(BBS_E_HIP);
     if (d_inf.p && rt::h2d_async(d_inf.p, is_inf, n, stream)) return fail(BBS_E_HIP);
     if (rt::dmemset(d_out, 0, n * sizeof(KeyEntry<C>), stream)) return fail(BBS_E_HIP);
-    KeyBuildArgs<C> a{};
     a.n = n;
     a.rec = oct ? nullptr : d_in.as<uint32_t>();
     a.is_inf = d_inf.as<int8_t>();
@@ -108,14 +125,6 @@ int Ctx<C>::key_build(KeyEntry<C>* d_out, size_t n, const uint8_t* rec, const in
     a.hash0 = d_blob.as<HashCtx>();
     a.suffix = d_blob.as<uint8_t>() + sizeof(HashCtx);
     a.suffix_len = (uint32_t)(blob.size() - sizeof(HashCtx));
-    a.b2 = g2_b<C>();
-    const G2Aff<C> gen = g2_generator<C>();
-    a.gen_x = gen.x; a.gen_y = gen.y;
-    a.frob_x = f2_from_consts<C>(C::K::FROB[0][2][0], C::K::FROB[0][2][1]);
-    a.frob_y = f2_from_consts<C>(C::K::FROB[0][3][0], C::K::FROB[0][3][1]);
-    a.want_unit = lines_unit() ? 1 : 0;
-    a.n_bits = (int)bits.size();
-    for (size_t k = 0; k < bits.size(); k++) a.bits[k] = (uint8_t)bits[k];
     if (rt::launch<KeyBuild<C>>(stream, a, n)) return fail(BBS_E_HIP);
     if (rt::d2h_async(status, d_st.p, n, stream)) return fail(BBS_E_HIP);
     if (oct && rec_out && rt::d2h_async(rec_out, d_rec.p, n * 4 * FPB, stream)) return fail(BBS_E_HIP);
@@ -297,4 +306,90 @@ int selftest_key_entries(Ctx<C>* ctx, size_t n, const uint8_t* rec, const int8_t
     if (const int rc = ctx->key_build(d.as<KeyEntry<C>>(), n, rec, is_inf, oct, true, status_out, oct ? rec_out : nullptr, nullptr)) return rc;
     if (rt::d2h(entries_out, d.p, n * sizeof(KeyEntry<C>), ctx->stream) || rt::sync(ctx->stream)) return BBS_E_HIP;
     return BBS_OK;
+}
+
+// ---- job-local key sets (job_form.hpp JobKeys) ------------------------------------------------------------------------------
+// The keys of one job on the job's stream st, asynchronously: the entries cleared (KeyBuild wants them zeroed), KeyBuild in its
+// octet form over the strings in the job's staging image, and -- stride != 0: a job of mixed counts -- KeyLenBuild into the job's
+// own rows.  Nothing is copied back; nothing waits.  Every buffer comes from the job (alloc) and lives as long as it does.
+template <class C>
+int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uint32_t stride, const std::function<void*(size_t)>& alloc,
+                     std::shared_ptr<const void>& blob_held) {
+    const size_t nk = jk.n_keys;
+    std::shared_ptr<const typename Ctx<C>::KeyBlob> kb;
+    if (const int rc = ctx->sync_key_blob(kb)) return rc;
+    blob_held = kb;
+    KeyBuildArgs<C> a{};
+    size_t n_steps = 0;
+    if (const int rc = key_build_consts<C>(a, unit, n_steps)) return rc;
+    jk.status = static_cast<int8_t*>(alloc(nk));
+    uint32_t* ws = static_cast<uint32_t*>(alloc(key_build_ws_words<C>(n_steps) * nk * 4));
+    if (stride) jk.rows = static_cast<HashCtx*>(alloc(nk * stride * sizeof(HashCtx)));
+    if (!jk.status || !ws || (stride && !jk.rows)) return BBS_E_NOMEM;
+    if (!nk) return BBS_OK;
+    if (rt::dmemset(jk.entries, 0, nk * sizeof(KeyEntry<C>), st)) return BBS_E_HIP;
+    a.n = nk;
+    a.oct = jk.d_oct;
+    a.out = jk.entries;
+    a.status = jk.status;
+    a.ws = ws;
+    a.hash0 = kb->hash0();
+    a.suffix = kb->suffix();
+    a.suffix_len = (uint32_t)kb->suffix_len();
+    if (rt::launch<KeyBuild<C>>(st, a, nk)) return BBS_E_HIP;
+    if (!stride) return BBS_OK;
+    KeyLenBuildArgs<C> la{};
+    la.n_keys = nk; la.stride = stride; la.oct = jk.d_oct; la.key_status = jk.status;
+    la.cg = kb->cg(); la.api_id = kb->api(); la.api_len = (uint32_t)kb->api_len;
+    la.hash0 = kb->hash0(); la.out = jk.rows;
+    return rt::launch<KeyLenBuild<C>>(st, la, nk * stride) ? BBS_E_HIP : BBS_OK;
+}
+template <class C>
+int job_keys_gate(rt::Stream& st, const JobKeys<C>& jk, bool unit, size_t n, const uint32_t* kidx, int8_t* status0) {
+    JobKeyGateArgs<C> g{n, kidx, jk.entries, jk.status, unit ? 1 : 0, status0};
+    return rt::launch<JobKeyGate<C>>(st, g, n) ? BBS_E_HIP : BBS_OK;
+}
+
+// bbs_selftest_key_len_rows: the prefixes per (key, length) of n keys given as octets, [n][L + 1] HashCtx, by path 0 = the host
+// functions registration uses (host_key_entry's decisions, domain_midstate per length) or path 1 = the stages a job with a
+// job-local key set runs (job_keys_prepare: KeyBuild, KeyLenBuild); the context's key set is not touched
+template <class C>
+int selftest_key_len_rows(Ctx<C>* ctx, size_t n, const uint8_t* oct, int path, uint8_t* rows_out, int8_t* status_out) {
+    constexpr size_t FPB = Ctx<C>::FPB;
+    if (!ctx->gens_set) return BBS_E_STATE;
+    if (ctx->use()) return BBS_E_HIP;
+    const size_t S = (size_t)ctx->L + 1;
+    if (!n) return BBS_OK;
+    if (path == 0) {
+        const std::vector<uint8_t> cg = ctx->compressed_gens();
+        std::vector<HashCtx> rows(n * S, ctx->key_hash0());
+        KeyEntry<C> e;
+        for (size_t k = 0; k < n; k++) {
+            G2Aff<C> q{};
+            q.inf = true; q.x = f2_zero<C>(); q.y = f2_zero<C>();
+            status_out[k] = ctx->host_key_entry(nullptr, false, oct + k * 2 * FPB, e, nullptr, nullptr, &q);
+            if (status_out[k] != 1) continue;
+            for (size_t l = 0; l < S; l++) ctx->domain_midstate(q, rows[k * S + l], (int)l, cg.data());
+        }
+        std::memcpy(rows_out, rows.data(), rows.size() * sizeof(HashCtx));
+        return BBS_OK;
+    }
+    std::vector<std::unique_ptr<DevBuf>> bufs;
+    auto alloc = [&](size_t b) -> void* {
+        bufs.emplace_back(new DevBuf());
+        return bufs.back()->alloc(std::max<size_t>(b, 1)) ? nullptr : bufs.back()->p;
+    };
+    JobKeys<C> jk;
+    jk.on = true; jk.n_keys = n;
+    jk.entries = static_cast<KeyEntry<C>*>(alloc(n * sizeof(KeyEntry<C>)));
+    uint32_t* d_oct = static_cast<uint32_t*>(alloc(n * 2 * FPB));
+    if (!jk.entries || !d_oct) return BBS_E_NOMEM;
+    jk.d_oct = d_oct;
+    std::shared_ptr<const void> held;
+    int rc = rt::h2d(d_oct, oct, n * 2 * FPB, ctx->stream) ? BBS_E_HIP : BBS_OK;
+    if (!rc) rc = job_keys_prepare<C>(ctx, ctx->stream, jk, ctx->lines_unit(), (uint32_t)S, alloc, held);
+    if (!rc && (rt::sync(ctx->stream) || rt::d2h(rows_out, jk.rows, n * S * sizeof(HashCtx), ctx->stream) ||
+                rt::d2h(status_out, jk.status, n, ctx->stream))) rc = BBS_E_HIP;
+    (void)rt::sync(ctx->stream);                  // (the buffers go back with the locals, behind the synchronisation)
+    return rc;
 }

@@ -64,6 +64,7 @@ int Ctx<C>::set_generators(const uint8_t* g, size_t count, const uint8_t* aid, s
     keys.reset();                    // the key set's domain midstates were built from the previous generators
     key_lens.reset();                // (and its prefixes per length)
     sign_keys.reset();               // (and the secret halves: they are indexed like the key set)
+    key_blob.reset();                // (and what job-local key sets are hashed from; jobs in flight keep theirs)
     win_bits = wb;
     hc.L = L; hc.n_bases = nb; hc.win_bits = win_bits; hc.n_windows = W;
     for (int j = 0; j < 8; j++) hc.fix_bias[j] = 0;

@@ -42,7 +42,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     constexpr int NC = C::FpP::NC;      // canonical 32-bit words
     constexpr int FPB = 4 * NC;
     Form form;
-    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form)) return rcf;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form, KEYED && in.job_keys)) return rcf;
     if (!out || (n && (!in.dmsg_off || !in.didx_off))) return BBS_E_ARG;
     if (n && !wire && (!in.proofs_fixed || !in.commit_off)) return BBS_E_ARG;
     if (n && wire && !in.proof_octets) return BBS_E_ARG;
@@ -54,7 +54,10 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     job->jf.form = form;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    if constexpr (KEYED) {
+        if (const int rck = job_keys_begin<C>(job.get(), in.job_keys, in.n_keys, in.pk_octets, job->jf.jk)) return rck;
+        keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    }
     // ---- the batch as one staging image in page-locked memory, one asynchronous copy; everything else (the
     // reference's checks, range checks, unpacking, the SoA transposition) happens on the device: stage PvIngest
     // first ragged section: the commitments (core form) or the proof octet strings (wire form)
@@ -109,6 +112,9 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     if (rc) return rc;
     job->zero_on_reset.push_back({pair_ok, nn});          // a pairing lane that never ran reads as "product != 1"
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if constexpr (KEYED) {
+        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf))) return rc;
+    }
     if (!wire) {
         PvIngestArgs<C>& ia = job->ingest;
         ia.n = n; ia.L = L; ia.dst_too_long = ctx->dst_too_long ? 1 : 0;
@@ -141,7 +147,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
         if ((rc = launch_ingest<PvOctIngest<C>, PvOctIngestMixed<C>>(job.get(), job->jf, oa, n))) return rc;
     }
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, job->d_status0.template as<int8_t>()))) return rc;
+        if ((rc = paired_keyed_gate<C>(job.get(), n, job->jf, job->d_status0.template as<int8_t>()))) return rc;
     }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.pts; pa.pb = a.pts + (size_t)2 * NC * n; pa.negate_b = 1;

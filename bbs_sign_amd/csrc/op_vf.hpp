@@ -26,7 +26,7 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
     Form form;
-    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form)) return rcf;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::Verify, n, in.key_index, form, KEYED && in.job_keys)) return rcf;
     if (!out || (n && ((!in.signatures && !in.signature_octets) || !in.msg_off))) return BBS_E_ARG;
     if (ctx->use()) return BBS_E_HIP;
     const int L = ctx->L;
@@ -38,7 +38,10 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     job->jf.form = form;
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    if constexpr (KEYED) {
+        if (const int rck = job_keys_begin<C>(job.get(), in.job_keys, in.n_keys, in.pk_octets, job->jf.jk)) return rck;
+        keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    }
     // the batch as one staging image, one asynchronous copy; checks, range checks and the SoA transposition on the
     // device (stage VfIngest), as for proof_verify
     const bool raw = in.msg_byte_off != nullptr;
@@ -92,9 +95,12 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     ia.sig_a = sig_a; ia.sig_e = sig_e; ia.msgs = smsgs; ia.hdr_off = offs; ia.hdr_len = offs + nn;
     ia.status0 = job->d_status0.template as<int8_t>();
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if constexpr (KEYED) {
+        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf))) return rc;
+    }
     if ((rc = launch_ingest<VfIngest<C>, VfIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, ia.status0))) return rc;
+        if ((rc = paired_keyed_gate<C>(job.get(), n, job->jf, ia.status0))) return rc;
     }
     PairArgs<C>& pa = job->pa;
     pa.n = n; pa.cc = a.cc; pa.pa = a.aff; pa.pb = a.aff + (size_t)2 * N * n; pa.negate_b = 0;

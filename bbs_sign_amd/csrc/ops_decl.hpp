@@ -24,6 +24,10 @@ struct PvIn {
     const uint8_t* msg_bytes = nullptr;
     const uint64_t* msg_byte_off = nullptr;
     const uint32_t* key_index = nullptr;        // KEYED only: item i is verified under key key_index[i] of the context's key set
+    // KEYED only, bbs_*_with_keys_*: the key set is THIS call's -- n_keys compressed strings, prepared by the job (job_form.hpp JobKeys)
+    bool job_keys = false;
+    size_t n_keys = 0;
+    const uint8_t* pk_octets = nullptr;
 };
 struct VfIn {
     const uint8_t* signatures = nullptr;        // n records A || e
@@ -38,6 +42,9 @@ struct VfIn {
     const uint8_t* msg_bytes = nullptr;
     const uint64_t* msg_byte_off = nullptr;
     const uint32_t* key_index = nullptr;        // KEYED only, as PvIn
+    bool job_keys = false;                      // KEYED only, as PvIn
+    size_t n_keys = 0;
+    const uint8_t* pk_octets = nullptr;
 };
 struct SgIn {
     const uint8_t* messages = nullptr;
@@ -145,3 +152,6 @@ extern template int key_gen_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_
 extern template int sk_to_pk_batch<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*, int8_t*);
 extern template int key_gen_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint8_t*, size_t, uint8_t*, uint8_t*, uint8_t*, int8_t*);
 extern template int sk_to_pk_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*, int8_t*);
+template <class C> int selftest_key_len_rows(Ctx<C>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
+extern template int selftest_key_len_rows<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
+extern template int selftest_key_len_rows<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);

@@ -665,6 +665,40 @@ struct Ctx : bbs_ctx {
     };
     std::shared_ptr<const KeyLenSet> key_lens;
     size_t key_lens_bytes() const { const auto kl = key_lens; return keyed_mixed_lengths && kl ? kl->of->n * kl->stride * sizeof(HashCtx) : 0; }
+    // Job-local key sets (bbs_*_with_keys_*, op_key.hpp job_keys_prepare): what KeyBuild and KeyLenBuild read beside the keys,
+    // the same for every key and every job of the context: key_hash0() || I2OSP(L, 8) || compressed_gens() || api_id.  Uploaded
+    // when the first such job is created, dropped by set_generators; a job holds a reference.  Never built where the exports
+    // are not used.
+    struct KeyBlob {
+        DevBuf d;
+        size_t api_len = 0, gens_bytes = 0;
+        const HashCtx* hash0() const { return d.as<HashCtx>(); }
+        const uint8_t* suffix() const { return d.as<uint8_t>() + sizeof(HashCtx); }       // I2OSP(L, 8) || gens || api_id
+        size_t suffix_len() const { return 8 + gens_bytes + api_len; }
+        const uint8_t* cg() const { return suffix() + 8; }
+        const uint8_t* api() const { return cg() + gens_bytes; }
+    };
+    std::shared_ptr<const KeyBlob> key_blob;
+    int sync_key_blob(std::shared_ptr<const KeyBlob>& out) {
+        std::lock_guard<std::mutex> g(mu);
+        if (!gens_set) return BBS_E_STATE;
+        if (!key_blob) {
+            std::vector<uint8_t> blob(sizeof(HashCtx));
+            const HashCtx h0 = key_hash0();
+            std::memcpy(blob.data(), &h0, sizeof(h0));
+            for (int k = 7; k >= 0; k--) blob.push_back((uint8_t)((uint64_t)L >> (8 * k)));
+            const std::vector<uint8_t> cg = compressed_gens();
+            blob.insert(blob.end(), cg.begin(), cg.end());
+            blob.insert(blob.end(), api_id.begin(), api_id.end());
+            std::shared_ptr<KeyBlob> kb(new KeyBlob());
+            kb->api_len = api_id.size(); kb->gens_bytes = cg.size();
+            if (kb->d.alloc(blob.size())) return BBS_E_NOMEM;
+            if (rt::h2d(kb->d.p, blob.data(), blob.size(), stream) || rt::sync(stream)) return BBS_E_HIP;
+            key_blob = std::move(kb);
+        }
+        out = key_blob;
+        return BBS_OK;
+    }
     // mixed message counts (bbs_ctx_set_mixed_lengths): off by default.  On: the single-key verify / proof_verify jobs created
     // from now on accept item i with its own count l_i <= L; the only data of a context that depend on the count are the domain
     // prefixes, one HashCtx per length 0 .. L (prefix l = the first l + 1 generators: create_generators is prefix-consistent).
@@ -1067,6 +1101,8 @@ struct bbs_job {
     std::function<int(uint32_t*, uint32_t*, uint32_t*)> bv_report;
     // bbs_job_bv_verdicts: the raw verdict flags of the last run, read back on request (set where bv_report is): 16 per group
     std::function<int(std::vector<int8_t>&)> bv_verdicts;
+    // bbs_job_key_statuses: set by a job with a job-local key set (job_form.hpp JobKeys): KeyBuild's code per key, read back on request
+    std::function<int(std::vector<int8_t>&)> key_statuses;
     virtual int fetch_signatures(uint8_t*) { return BBS_E_ARG; }
     virtual int fetch_proofs(uint8_t*, uint8_t*, uint64_t*) { return BBS_E_ARG; }
     // One pass over the stages.  ev != nullptr: one event before the first stage, then a (start, stop) pair around
@@ -1149,6 +1185,7 @@ struct JobBase : bbs_job {
     std::shared_ptr<const void> key_set;     // keyed jobs: the context's key set at upload (released after the streams synchronised)
     std::shared_ptr<const void> len_set;     // mixed-length jobs: the context's per-length domain prefixes at upload (likewise)
     std::shared_ptr<const void> key_len_set; // keyed jobs of mixed counts: the prefixes per (key, length) at upload (likewise)
+    std::shared_ptr<const void> key_blob;    // jobs with a job-local key set: what their keys were hashed with (likewise)
     std::shared_ptr<const void> sign_key_set;// keyed sign jobs: the context's signing set at upload (likewise; the last holder clears it)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};

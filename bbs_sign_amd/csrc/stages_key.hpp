@@ -373,4 +373,101 @@ struct KeyBuild {
 
 #undef BBS_KB_HD
 
+// ---- job-local key sets (bbs_*_with_keys_*; job_form.hpp JobKeys) ------------------------------------------------------------
+// The keys of ONE job, prepared by KeyBuild (octet form) on the job's main stream in front of its ingest kernel.  The host
+// planned the job without knowing which keys come out accepted: every index < n_keys has its slot in the pairing order and in
+// the groups of keyed batch verification.  This gate, behind KeyBuild and the ingest kernel and in front of everything that
+// reads an entry, decides the items whose key the job does not have -- an index >= n_keys (KEY_NONE, set by the host), a key
+// KeyBuild refused, and an accepted key (not the identity) whose table came out in another form than the job's: unit == 0 in a
+// unit-form job, a walk that met c = 0.  No key of order r is known to reach that; the job fails closed there
+// (BBS_ST_UNKNOWN_KEY), registration -- which moves the whole context to the (c, nl) form -- serves such a key.
+// A decided item keeps its slot; the pairing kernels and the combination leave it out by its status, as every decided item.
+template <class C>
+struct JobKeyGateArgs {
+    size_t n;
+    const uint32_t* kidx;        // [n] key of item i, KEY_NONE: index >= n_keys
+    const KeyEntry<C>* keys;     // [n_keys] as KeyBuild left them
+    const int8_t* key_status;    // [n_keys] KeyBuild's codes
+    int unit;                    // line form of the job
+    int8_t* status0;
+};
+template <class C>
+struct JobKeyGate {
+    static __host__ __device__ void run(const JobKeyGateArgs<C>& a, size_t i) {
+        const uint32_t k = a.kidx[i];
+        bool ok = k != KEY_NONE;
+        if (ok) ok = a.key_status[k] == 1;
+        if (ok) {
+            const LineTable<C>& t = a.keys[k].tab;
+            ok = t.q_is_identity != 0 || (t.unit != 0) == (a.unit != 0);
+        }
+        if (!ok) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
+    }
+};
+
+// The prefixes per (key, length) of a job-local key set under bbs_ctx_set_keyed_mixed_lengths: what Ctx::build_key_lens hashes
+// on host threads, one lane per (key, l), 0 <= l < stride = L + 1, into the job's own rows.  For an accepted key compress(pk) is
+// the input string itself (decoding is canonical, the identity included), so the lane hashes bytes only:
+//     Z_pad || octets || I2OSP(l, 8) || compress(Q1, H_1 .. H_l) || api_id
+// and keeps midstate, total, tail and tail length as step 5 of KeyBuild does.  Rows of a refused key stay at hash0.
+// Lanes of one wavefront hash different lengths.  The message is read as a function of the word index and the compression
+// function is inlined in the one loop over blocks: no out-of-line helper is reached by part of a wavefront.
+// Everything in front of api_id is whole words (FPB, 8 and 64 are multiples of 4).
+template <class C>
+struct KeyLenBuildArgs {
+    size_t n_keys;
+    uint32_t stride;             // L + 1
+    const uint32_t* oct;         // [n_keys][2 NC] words of the compressed strings, as KeyBuild reads them
+    const int8_t* key_status;    // [n_keys] KeyBuild's codes
+    const uint8_t* cg;           // compress(Q1) || compress(H_1) || .. || compress(H_L), 4-byte aligned
+    const uint8_t* api_id;
+    uint32_t api_len;
+    const HashCtx* hash0;
+    HashCtx* out;                // [n_keys][stride]
+};
+template <class C>
+struct KeyLenBuild {
+    static __host__ __device__ void run(const KeyLenBuildArgs<C>& a, size_t t) {
+        constexpr uint32_t NC = C::FpP::NC;
+        const size_t k = t / a.stride;
+        const uint32_t l = (uint32_t)(t - k * a.stride);
+        HashCtx& o = a.out[t];
+        o = *a.hash0;
+        if (a.key_status[k] != 1) return;
+        const uint32_t* ow = a.oct + k * 2 * NC;
+        const uint32_t* gw = reinterpret_cast<const uint32_t*>(a.cg);
+        // word j of the message (big-endian), zero behind its end
+        const uint32_t w_key = 16, w_len = w_key + 2 * NC, w_gen = w_len + 2, w_api = w_gen + (l + 1) * NC;
+        const uint32_t total = 4 * w_api + a.api_len;
+        auto word = [&](uint32_t j) -> uint32_t {
+            if (j < w_key) return 0u;
+            if (j < w_len) return kb_bswap(ow[j - w_key]);
+            if (j < w_gen) return j == w_len ? 0u : l;
+            if (j < w_api) return kb_bswap(gw[j - w_gen]);
+            uint32_t v = 0;
+            for (uint32_t b = 0; b < 4; b++) {
+                const uint32_t at = 4 * (j - w_api) + b;
+                v = (v << 8) | (at < a.api_len ? (uint32_t)a.api_id[at] : 0u);
+            }
+            return v;
+        };
+        uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+        const uint32_t n_blocks = total / 64;
+#pragma unroll 1
+        for (uint32_t b = 0; b < n_blocks; b++) {
+            uint32_t w[16];
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++) w[i] = word(16 * b + i);
+            sha256_compress_body(h, w);
+        }
+        for (int i = 0; i < 8; i++) o.dom_mid[i] = h[i];
+        o.dom_mid_total = (uint64_t)n_blocks * 64;
+        o.dom_tail_len = total - n_blocks * 64;
+        for (uint32_t i = 0; i < 16; i++) {                              // (words behind the end are zero, as the entry is)
+            const uint32_t v = word(16 * n_blocks + i);
+            for (uint32_t b = 0; b < 4; b++) o.dom_tail[4 * i + b] = (uint8_t)(v >> ((3 - b) * 8));
+        }
+    }
+};
+
 }  // namespace bbs

@@ -305,22 +305,34 @@ class Engine:
     # ---- the one call of every verify-family export: statuses out, nothing else.  `args` in C parameter order, `key_index`
     # for the keyed exports, `fixup(st)` applied to the delivered statuses.  A successful call writes every entry: the
     # -128 the buffer starts with never shows, and an entry nobody wrote cannot read as a verdict (fail closed).
-    def _status_call(self, fn, n, args, key_index, tail=()):
+    # `key_octets` (the ``*_with_keys_*`` exports): the key set of THIS call, compressed strings, in front of key_index.
+    def _status_call(self, fn, n, args, key_index, tail=(), key_octets=None):
         st = np.full(max(n, 1), -128, dtype=np.int8)
         key = () if key_index is None else self._key_index(key_index, n)
-        self._chk(getattr(self.lib, fn)(self.h, n, *key[1:], *args, st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+        own = ()
+        if key_octets is not None:
+            ko = self._key_octets(key_octets)
+            own = (len(key_octets), _u8(ko))
+        self._chk(getattr(self.lib, fn)(self.h, n, *own, *key[1:], *args, st.ctypes.data_as(_lib.c_i8p), *tail), fn)
         return st
 
-    def _status_batch(self, fn, n, args, key_index=None, fixup=None) -> np.ndarray:
-        st = self._status_call(fn, n, args, key_index)
+    def _key_octets(self, key_octets):
+        ob = 2 * self.fpb
+        for k, o in enumerate(key_octets):
+            if len(o) != ob:
+                raise ValueError("key %d: %d octets, a compressed public key has %d" % (k, len(o), ob))
+        return _bytes_arr(b"".join(bytes(o) for o in key_octets) or b"\0")
+
+    def _status_batch(self, fn, n, args, key_index=None, fixup=None, key_octets=None) -> np.ndarray:
+        st = self._status_call(fn, n, args, key_index, key_octets=key_octets)
         if fixup:
             fixup(st)
         return st[:n]
 
-    def _status_submit(self, fn, n, args, key_index=None, fixup=None) -> "Job":
+    def _status_submit(self, fn, n, args, key_index=None, fixup=None, key_octets=None) -> "Job":
         """Everything enqueued, nothing waited for; ``job.wait()`` then ``job.result``."""
         j = ctypes.c_void_p()
-        st = self._status_call(fn, n, args, key_index, (ctypes.byref(j),))
+        st = self._status_call(fn, n, args, key_index, (ctypes.byref(j),), key_octets=key_octets)
         job = Job(self, j, n)
         job.result = st[:n]
         job._fixup = (lambda: fixup(st)) if fixup else None
@@ -389,6 +401,55 @@ class Engine:
     def verify_wire_keyed_batch(self, key_index, sig_octets, messages_raw, headers=None) -> np.ndarray:
         n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
         return self._status_batch("bbs_verify_wire_keyed_batch", n, args, key_index, fix)
+
+    # Verification under a job-local key set (bbs_*_with_keys_*): ``key_octets`` = the distinct keys of THIS call as compressed
+    # strings (public_key_to_octets), ``key_index[i]`` names one of them.  The job prepares the keys on the device and releases
+    # them; the engine's key set is neither read nor changed.  Statuses as the keyed twin's on an engine whose key set was
+    # registered from the same strings (-44: index out of range, or a key registration would refuse); Job.key_statuses() says
+    # which keys were refused.  A key given twice is two keys: deduplicate before the call (api.verify_many_issuers does).
+    def core_proof_verify_with_keys_submit(self, key_octets, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> "Job":
+        n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
+        return self._status_submit("bbs_core_proof_verify_with_keys_submit", n, args, key_index, key_octets=key_octets)
+
+    def core_proof_verify_with_keys_batch(self, key_octets, key_index, proofs, disclosed_msgs, disclosed_idx, headers=None, phs=None) -> np.ndarray:
+        n, keep, args = self._pv_inputs(proofs, disclosed_msgs, disclosed_idx, headers, phs)
+        return self._status_batch("bbs_core_proof_verify_with_keys_batch", n, args, key_index, key_octets=key_octets)
+
+    def proof_verify_wire_with_keys_submit(self, key_octets, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> "Job":
+        n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
+        return self._status_submit("bbs_proof_verify_wire_with_keys_submit", n, args, key_index, key_octets=key_octets)
+
+    def proof_verify_wire_with_keys_batch(self, key_octets, key_index, octets, disclosed_raw, disclosed_idx, headers=None, phs=None) -> np.ndarray:
+        n, keep, args = self._wire_inputs(octets, disclosed_raw, disclosed_idx, headers, phs)
+        return self._status_batch("bbs_proof_verify_wire_with_keys_batch", n, args, key_index, key_octets=key_octets)
+
+    def core_verify_with_keys_submit(self, key_octets, key_index, signatures, messages, headers=None) -> "Job":
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        return self._status_submit("bbs_core_verify_with_keys_submit", n, args, key_index, key_octets=key_octets)
+
+    def core_verify_with_keys_batch(self, key_octets, key_index, signatures, messages, headers=None) -> np.ndarray:
+        n, keep, args = self._vf_core_args(signatures, messages, headers)
+        return self._status_batch("bbs_core_verify_with_keys_batch", n, args, key_index, key_octets=key_octets)
+
+    def verify_wire_with_keys_submit(self, key_octets, key_index, sig_octets, messages_raw, headers=None) -> "Job":
+        n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
+        return self._status_submit("bbs_verify_wire_with_keys_submit", n, args, key_index, fix, key_octets=key_octets)
+
+    def verify_wire_with_keys_batch(self, key_octets, key_index, sig_octets, messages_raw, headers=None) -> np.ndarray:
+        n, keep, args, fix = self._vf_wire_args(sig_octets, messages_raw, headers)
+        return self._status_batch("bbs_verify_wire_with_keys_batch", n, args, key_index, fix, key_octets=key_octets)
+
+    def selftest_key_len_rows(self, key_octets, path: int):
+        """bbs_selftest_key_len_rows -> (rows, statuses): rows[k][l] = the bytes of the prefix of key k and length l."""
+        n = len(key_octets)
+        hb = int(self.lib.bbs_selftest_hash_ctx_bytes())
+        S = self.L + 1
+        ko = self._key_octets(key_octets)
+        rows = np.zeros(max(n * S * hb, 1), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        self._chk(self.lib.bbs_selftest_key_len_rows(self.h, n, _u8(ko), path, _u8(rows), st.ctypes.data_as(_lib.c_i8p)), "bbs_selftest_key_len_rows")
+        b = rows.tobytes()
+        return [[b[(k * S + l) * hb:(k * S + l + 1) * hb] for l in range(S)] for k in range(n)], st[:n]
 
     def set_secret_key(self, sk: int):
         buf = _bytes_arr(self._fr(sk))
@@ -1295,6 +1356,19 @@ class Job:
         g, p, it = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
         Engine._chk(self.eng.lib.bbs_job_bv_report(self.h, ctypes.byref(g), ctypes.byref(p), ctypes.byref(it)), "bbs_job_bv_report")
         return g.value, p.value, it.value
+
+    def key_statuses(self) -> np.ndarray:
+        """bbs_job_key_statuses, after wait(): the code of every key of a job-local key set (``*_with_keys_*``) in the order the
+        keys were given -- 1 accepted, -40 not a canonical string, -41 not on the twist or not of order r.  BBS_E_STATE for a
+        job that has no key set of its own."""
+        cnt = ctypes.c_size_t(0)
+        out = np.zeros(64, dtype=np.int8)
+        rc = self.eng.lib.bbs_job_key_statuses(self.h, out.ctypes.data_as(_lib.c_i8p), out.size, ctypes.byref(cnt))
+        if rc == -100 and cnt.value > out.size:          # BBS_E_ARG with the count set: more keys than the first buffer holds
+            out = np.zeros(cnt.value, dtype=np.int8)
+            rc = self.eng.lib.bbs_job_key_statuses(self.h, out.ctypes.data_as(_lib.c_i8p), out.size, ctypes.byref(cnt))
+        Engine._chk(rc, "bbs_job_key_statuses")
+        return out[:cnt.value]
 
     def bv_verdicts(self) -> np.ndarray:
         """bbs_job_bv_verdicts, after wait(): the raw verdict flags of the last run's combined checks (1 = passed) -- 16 for a

@@ -528,6 +528,88 @@ int bbs_verify_wire_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_ind
 int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signature_octets,
                                 const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                                 const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+/* ------------------------------------------------------------------------------------------
+ * Verification under keys that ARRIVE WITH THE JOB: per-job key sets.  The keyed exports above serve a closed set of issuers
+ * whose keys were registered beforehand.  These eight serve a verifier that learns the issuer key next to the proof: the call
+ * passes the DISTINCT keys of the job as compressed octets (n_keys strings of 2 * fp_bytes bytes, the format
+ * bbs_ctx_add_public_keys_octets takes) and key_index[i] names a key OF THIS CALL.  The job prepares its keys on the device as its
+ * own first work -- one lane per key decodes the string, tests the twist and [r]Q, walks the Miller-loop line table and hashes
+ * the domain midstate (and, with bbs_ctx_set_keyed_mixed_lengths on, one lane per (key, length) hashes the prefixes) -- on its
+ * main stream in front of its ingest kernel, asynchronously like everything else of a job, into arrays it owns (counted by
+ * bbs_job_device_bytes: per key the entry, 22 848 bytes of workspace on BLS12-381, a status byte, and (L + 1) prefixes of
+ * 368 bytes in jobs of mixed counts) and releases with the job.  The context's key set is neither read nor changed; a context
+ * without a public key or a key set serves these calls.  The key bytes are copied into the job's staging image by the call: the
+ * caller's array is free when _submit returns.  The library does NOT deduplicate: a key given twice is prepared twice and is
+ * two keys.  The keys are prepared with the upload, as the ingest kernel runs with the upload: bbs_job_run on the same job
+ * runs the stages again over the same prepared keys.
+ * Arguments: those of the keyed twin with n_keys and pk_octets in front of key_index.
+ * STATUS RULE: the status array is, bit for bit, what the keyed twin returns on a context with the same generators, api_id and
+ * switches whose key set was built by bbs_ctx_add_public_keys_octets(pk_octets), given the same key_index and items.  So an
+ * index >= n_keys is BBS_ST_UNKNOWN_KEY, a key registration would refuse (BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE) makes its
+ * items BBS_ST_UNKNOWN_KEY, the identity encoding is an accepted key, and everything else is decided as under that key alone.
+ * Which keys were accepted is decided on the device: the host plans the job (pairing order, groups of keyed batch verification)
+ * with every index < n_keys, and a gate behind the key stage decides the items of a refused key; they keep their slots and are
+ * left out by status as every decided item is.
+ * FAIL-CLOSED CASE: a key whose line walk meets a line through the twist's origin (c = 0) has no unit form.  Registration moves
+ * the whole context to the (c, nl) form for such a key; a job cannot.  On a context in the unit form (the default) the items of
+ * such a key get BBS_ST_UNKNOWN_KEY although bbs_job_key_statuses says 1 for it.  No key of order r is known to reach this;
+ * register such a key (bbs_ctx_add_public_keys*) to use it.
+ * BBS_E_ARG: NULL pk_octets with n_keys > 0, NULL key_index with n > 0, n_keys > 0xFFFFFFF0, a NULL status.  BBS_E_STATE: no
+ * generators; bbs_ctx_set_mixed_lengths on without bbs_ctx_set_keyed_mixed_lengths (as the keyed twins).
+ * Composition: both job forms, bbs_ctx_set_points_in_subgroup, both line forms, bbs_ctx_set_keyed_mixed_lengths (per-item
+ * counts), bbs_ctx_set_keyed_batch_verification (groups form by the job's own key indexes; bbs_job_bv_report counts the groups of
+ * accepted keys, bbs_job_bv_verdicts returns 16 flags for every group the host planned, refused keys included).
+ * bbs_ctx_set_batch_verification is not looked at.
+ * bbs_job_key_statuses: after bbs_job_wait, the per-key codes (1, BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE) in the order of
+ * pk_octets, copied from the device on request (nothing is added to a run); *n_out = n_keys; BBS_E_ARG where cap < n_keys;
+ * BBS_E_STATE for a job without a key set of its own.
+ * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys; a
+ * cache of prepared keys across jobs; preparing a handful of keys on the host instead (one call of the key stage costs one walk
+ * however few keys it brings); running the key stage beside the MSM stages on a side stream; a faster subgroup test by the
+ * curve endomorphism; registration through the device stage. */
+int bbs_core_proof_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                           const uint32_t* key_index, const uint8_t* proofs_fixed,
+                                           const uint8_t* commitments, const uint64_t* commit_off,
+                                           const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
+                                           const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                           const uint8_t* headers, const uint64_t* hdr_off,
+                                           const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out);
+int bbs_core_proof_verify_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                          const uint32_t* key_index, const uint8_t* proofs_fixed,
+                                          const uint8_t* commitments, const uint64_t* commit_off,
+                                          const uint8_t* disclosed_msgs, const uint64_t* dmsg_off,
+                                          const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                          const uint8_t* headers, const uint64_t* hdr_off,
+                                          const uint8_t* ph, const uint64_t* ph_off, int8_t* status);
+int bbs_proof_verify_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                           const uint32_t* key_index, const uint8_t* proof_octets,
+                                           const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                           const uint64_t* msg_item_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                           const uint8_t* headers, const uint64_t* hdr_off,
+                                           const uint8_t* ph, const uint64_t* ph_off, int8_t* status, bbs_job** job_out);
+int bbs_proof_verify_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                          const uint32_t* key_index, const uint8_t* proof_octets,
+                                          const uint64_t* oct_off, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
+                                          const uint64_t* msg_item_off, const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                          const uint8_t* headers, const uint64_t* hdr_off,
+                                          const uint8_t* ph, const uint64_t* ph_off, int8_t* status);
+int bbs_core_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                     const uint32_t* key_index, const uint8_t* signatures,
+                                     const uint8_t* messages, const uint64_t* msg_off,
+                                     const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out);
+int bbs_core_verify_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                    const uint32_t* key_index, const uint8_t* signatures,
+                                    const uint8_t* messages, const uint64_t* msg_off,
+                                    const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+int bbs_verify_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                     const uint32_t* key_index, const uint8_t* signature_octets,
+                                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                     const uint8_t* headers, const uint64_t* hdr_off, int8_t* status, bbs_job** job_out);
+int bbs_verify_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                    const uint32_t* key_index, const uint8_t* signature_octets,
+                                    const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                    const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
+int bbs_job_key_statuses(bbs_job* job, int8_t* out, size_t cap, size_t* n_out);
 /* Keyed forms of bbs_core_proof_gen_* and bbs_proof_gen_wire_*: ONE context derives proofs from signatures of MANY issuers.
  * The reference takes the public key per call (src/proof_gen.rs:78-113) and uses it in calculate_domain alone -- no pairing,
  * no W -- so a keyed item reads its key's domain midstate from the key set the keyed verify entry points use, and everything
@@ -1015,6 +1097,12 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
                              const uint8_t* pk_octets, int path, uint8_t* entries_out, int8_t* status_out,
                              uint8_t* pk_affine_out);
 size_t bbs_selftest_key_entry_bytes(int curve);
+/* The prefixes per (key, length) of n keys given as octets (bbs_ctx_set_keyed_mixed_lengths), by two implementations; the caller
+ * compares the outputs.  path 0: the host functions registration uses; path 1: the device stages a job with a job-local key
+ * set runs (the key stage, then one lane per (key, length)).  rows_out: n x (L + 1) x bbs_selftest_hash_ctx_bytes() bytes, rows of
+ * a refused key as every row starts out; status_out: n.  Needs the generators; does not touch the context's key set. */
+int bbs_selftest_key_len_rows(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int path, uint8_t* rows_out, int8_t* status_out);
+size_t bbs_selftest_hash_ctx_bytes(void);
 /* Keyed batch verification self-test: the segmented bucket kernel and the group sums alone (stages keyed_pip_windows and
  * keyed_pip_group_sums).  n affine G1 points (2 * fp_bytes each, canonical LE, zeros = the identity) given in group order,
  * digits[w * n + i] = the 8-bit coefficient of point i in window w (16 windows), and n_groups groups, group g = the points
