@@ -143,6 +143,11 @@ SIGNATURES = {
     "bbs_job_key_statuses": (ci, [vp, c_i8p, sz, ctypes.POINTER(sz)]),
     "bbs_selftest_key_len_rows": (ci, [vp, sz, c_u8p, ci, c_u8p, c_i8p]),
     "bbs_selftest_hash_ctx_bytes": (sz, []),
+    # the job-local key cache of the with_keys exports
+    "bbs_ctx_set_job_key_cache": (ci, [vp, sz]),
+    "bbs_ctx_job_key_cache_report": (ci, [vp, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz), c_u64p, c_u64p, c_u64p, c_u64p, ctypes.POINTER(sz)]),
+    "bbs_job_key_cache_report": (ci, [vp, c_u32p, c_u32p, ctypes.POINTER(ci)]),
+    "bbs_selftest_job_key_cache_entries": (ci, [vp, sz, c_u8p, c_u8p, c_i8p, c_u8p]),
     # keyed proof_gen: as the un-keyed forms, key_index after n
     "bbs_core_proof_gen_keyed_submit": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
                                              c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),

@@ -464,11 +464,12 @@ def sign_many_issuers(items: Sequence[tuple]) -> list:
     return out
 
 
-def _many_issuers(items, count, to_octets, run, batch_verification=False, register_keys=True, run_own=None):
+def _many_issuers(items, count, to_octets, run, batch_verification=False, register_keys=True, run_own=None, key_cache=0):
     """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms.
     register_keys=False: the keys are NOT registered on the cached engine -- the call deduplicates the keys of its items, writes
     them as octets and goes through the ``*_with_keys_*`` wire form (``run_own``): the job prepares them on the device and
-    releases them, ``index`` and the engine's key set stay as they were.
+    releases them, ``index`` and the engine's key set stay as they were.  key_cache (with register_keys=False only): the capacity
+    of the cached engine's job-local key cache (Engine.set_job_key_cache), set when it differs from what the engine has.
     batch_verification: bbs_ctx_set_keyed_batch_verification on the cached engine for this call -- True: the library's default
     threshold; an integer >= 1: that many items per key -- with a fresh seed from the operating system, and off again
     afterwards.  Off is the state the cache keeps its engines in (nothing else holds them), so that is the prior state.  Calls
@@ -488,6 +489,9 @@ def _many_issuers(items, count, to_octets, run, batch_verification=False, regist
             call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path),
                                  lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
         else:
+            if ie.eng.job_key_cache_report()["capacity"] != int(key_cache):
+                ie.eng.set_job_key_cache(int(key_cache))
+
             def own(octs, kept):
                 local: Dict[object, int] = {}
                 key_octets = []
@@ -511,7 +515,7 @@ def _many_issuers(items, count, to_octets, run, batch_verification=False, regist
     return out
 
 
-def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True) -> list:
+def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True, key_cache: int = 0) -> list:
     """PublicKey.verify for many items ``(pk, signature, header, messages)`` of ANY issuers and ANY message counts, in ONE
     device call per (curve, device, lib_path): one cached engine with bbs_ctx_set_keyed_mixed_lengths on, whose L is the
     largest count seen and whose key set grows by appending (a key is registered once).  Entry i is the boolean
@@ -525,23 +529,27 @@ def verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False
     ``register_keys=False`` is for a verifier that does not know its issuers in advance: the keys of THIS list travel with the
     job (bbs_verify_wire_with_keys_batch), are prepared on the device by the job and released with it; the cached engine's key
     set does not grow.  The entries are the same.  Worth it for lists that bring many keys that will not be seen again; a
-    handful of recurring issuers is served better by the default, which prepares a key once."""
+    handful of recurring issuers is served better by the default, which prepares a key once -- or by ``key_cache=N`` (with
+    ``register_keys=False`` only): the cached engine keeps the prepared keys of these calls in N slots on the device
+    (Engine.set_job_key_cache) and a later call prepares only the keys no slot holds.  The entries are the same."""
     return _many_issuers(items, lambda it: len(it[3]), signature_to_octets,
                          lambda eng, kidx, octs, its: eng.verify_wire_keyed_batch(kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]),
                          batch_verification, register_keys,
-                         lambda eng, keys, kidx, octs, its: eng.verify_wire_with_keys_batch(keys, kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]))
+                         lambda eng, keys, kidx, octs, its: eng.verify_wire_with_keys_batch(keys, kidx, octs, [list(it[3]) for it in its], [it[2] for it in its]),
+                         key_cache)
 
 
-def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True) -> list:
+def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool = False, register_keys: bool = True, key_cache: int = 0) -> list:
     """proof_verify for many items ``(pk, proof, header, ph, disclosed_messages, disclosed_indexes)`` of any issuers and any
-    message counts (commitments + disclosed indexes each), as verify_many_issuers (``batch_verification`` and ``register_keys``
-    included)."""
+    message counts (commitments + disclosed indexes each), as verify_many_issuers (``batch_verification``, ``register_keys`` and
+    ``key_cache`` included)."""
     return _many_issuers(items, lambda it: len(it[1].commitments) + len(it[5]), proof_to_octets,
                          lambda eng, kidx, octs, its: eng.proof_verify_wire_keyed_batch(
                              kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]),
                          batch_verification, register_keys,
                          lambda eng, keys, kidx, octs, its: eng.proof_verify_wire_with_keys_batch(
-                             keys, kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]))
+                             keys, kidx, octs, [list(it[4]) for it in its], [list(it[5]) for it in its], [it[2] for it in its], [it[3] for it in its]),
+                         key_cache)
 
 
 def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) -> list:

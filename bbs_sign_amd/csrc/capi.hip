@@ -675,6 +675,29 @@ int bbs_job_key_statuses(bbs_job* job, int8_t* out, size_t cap, size_t* n_out) {
     if (!v.empty()) std::memcpy(out, v.data(), v.size());
     return BBS_OK;
 }
+// the job-local key cache (runtime.hpp Ctx::KeyCacheGen, key_cache.hpp)
+int bbs_ctx_set_job_key_cache(bbs_ctx* ctx, size_t capacity_keys) {
+    if (!ctx) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return c->set_job_key_cache(capacity_keys); });
+}
+int bbs_ctx_job_key_cache_report(bbs_ctx* ctx, size_t* capacity, size_t* resident, size_t* pinned, uint64_t* hits, uint64_t* misses,
+                                 uint64_t* evictions, uint64_t* bypassed_jobs, size_t* device_bytes) {
+    if (!ctx) return BBS_E_ARG;
+    with_curve(ctx, [&](auto* c) { c->job_key_cache_report(capacity, resident, pinned, hits, misses, evictions, bypassed_jobs, device_bytes); });
+    return BBS_OK;
+}
+int bbs_job_key_cache_report(bbs_job* job, uint32_t* hits, uint32_t* misses, int* bypassed) {
+    if (!job) return BBS_E_ARG;
+    if (!job->has_job_keys) return BBS_E_STATE;       // the job did not come through a bbs_*_with_keys_* export
+    if (hits) *hits = job->key_cache_hits;
+    if (misses) *misses = job->key_cache_misses;
+    if (bypassed) *bypassed = job->key_cache_bypassed ? 1 : 0;
+    return BBS_OK;
+}
+int bbs_selftest_job_key_cache_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, uint8_t* entries_out, int8_t* status_out, uint8_t* rows_out) {
+    if (!ctx || (n && (!pk_octets || !entries_out || !status_out))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return selftest_job_key_cache_entries(c, n, pk_octets, entries_out, status_out, rows_out); });
+}
 int bbs_job_run_timed(bbs_job* job, int reps, float* total_ms, float* kernel_ms, int cap, int* n_stages) {
     if (!job || reps < 1) return BBS_E_ARG;
     if (job->use()) return BBS_E_HIP;

@@ -49,6 +49,34 @@ struct JobKeys {
     HashCtx* rows = nullptr;                 // [n_keys][L + 1], jobs of mixed counts only
     std::vector<uint32_t> grp_key;           // keyed batch verification: key of group g (bbs_job_bv_report leaves refused keys out)
     std::vector<uint32_t> grp_items;
+    // The job-local key cache (bbs_ctx_set_job_key_cache; runtime.hpp Ctx::KeyCacheGen, key_cache.hpp).  cache == null: the job is
+    // not cached (switch off, or bypassed) and everything above is what it says.  Otherwise THE CACHE IS THE JOB'S KEY SET: the job
+    // reads keys, key statuses and rows from the cache's arrays by SLOT.  The host plans in the job's own key numbering (counts,
+    // pairing order, groups: those of the keyed twin) and then translates key -> slot in the places of the staging words that
+    // hold a key id: kidx, the wave keys, the virtual items' kidx and wave keys (keyed_order).  entries / status / rows above
+    // then hold the job's MISSES only, [n_build()], prepared as ever and copied into their slots by KeyCachePublish.
+    // Both pointers are owned by JobBase::key_cache_pin, which outlives the job's streams.
+    typename Ctx<C>::KeyCacheGen* cache = nullptr;
+    KeyCachePlan* plan = nullptr;
+    size_t slot_at = 0;                      // place of the misses' slots in the staging words
+    const uint32_t* d_slot_of = nullptr;     // [n_build()] on the device
+    std::vector<std::shared_ptr<typename Ctx<C>::KeyCacheEvent>> wait_events;     // of hit slots still being published (another job's stream)
+    size_t n_build() const { return cache ? plan->miss_key.size() : n_keys; }
+    const KeyEntry<C>* use_entries() const { return cache ? cache->entries.template as<KeyEntry<C>>() : entries; }
+    const int8_t* use_status() const { return cache ? cache->status.template as<int8_t>() : status; }
+    const HashCtx* use_rows() const { return cache ? cache->rows.template as<HashCtx>() : rows; }
+};
+// what a cached job holds of the cache from its upload until it is freed (a job may be run again): the generation and its pins
+template <class C>
+struct KeyCachePin {
+    Ctx<C>* ctx = nullptr;
+    std::shared_ptr<typename Ctx<C>::KeyCacheGen> gen;
+    KeyCachePlan plan;
+    ~KeyCachePin() {                         // (an upload that failed before its entries were on their way gives its slots back)
+        if (!gen || !plan.planned) return;
+        std::lock_guard<std::mutex> g(ctx->mu);
+        gen->book.release(plan);
+    }
 };
 // verify / proof_verify: plus the keyed pairing order
 template <class C>
@@ -204,7 +232,7 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJ
     size_t nu = 0, ns = 0;
     keyed_slots(words.data(), n, cnt, order, nu, ns);
     words.insert(words.end(), order.begin(), order.end());
-    jf.src.keys = jk.on ? jk.entries : (ks ? ks->d.template as<KeyEntry<C>>() : nullptr);
+    jf.src.keys = jk.on ? jk.use_entries() : (ks ? ks->d.template as<KeyEntry<C>>() : nullptr);
     jf.pair.keys = jf.src.keys; jf.pair.n_uni = nu; jf.pair.n_slots = ns;
     jf.unit = ks ? ks->unit : ctx->lines_unit();
     if (ctx->keyed_bv) keyed_bv_plan<C>(n, cnt, ctx->keyed_bv_min, jf.bv, words);
@@ -213,12 +241,36 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJ
         for (size_t k = 0; k < nk; k++)
             if (cnt[k] && cnt[k] >= ctx->keyed_bv_min) { jk.grp_key.push_back((uint32_t)k); jk.grp_items.push_back(cnt[k]); }
     jk.oct_at = words.size();
-    words.resize(jk.oct_at + jk.n_keys * (2 * C::FpP::NC));
-    if (jk.n_keys) std::memcpy(words.data() + jk.oct_at, jk.pk_octets, jk.n_keys * 2 * Ctx<C>::FPB);
+    if (!jk.cache) {
+        words.resize(jk.oct_at + jk.n_keys * (2 * C::FpP::NC));
+        if (jk.n_keys) std::memcpy(words.data() + jk.oct_at, jk.pk_octets, jk.n_keys * 2 * Ctx<C>::FPB);
+        return;
+    }
+    // a cached job: everything above was planned in the job's numbering; now key -> slot wherever the words hold a key id,
+    // and behind the plan only the strings of the misses, then their slots
+    const KeyCachePlan& p = *jk.plan;
+    auto to_slots = [&p](uint32_t* w, size_t count) {
+        for (size_t i = 0; i < count; i++) if (w[i] != KEY_NONE) w[i] = p.slot_of[w[i]];
+    };
+    to_slots(words.data(), n);                                                       // kidx
+    to_slots(words.data() + n + ns, nu / KEY_SLOTS_PER_WAVE);                        // the wave keys
+    if (jf.bv.G) {
+        uint32_t* b = words.data() + jf.bv.at;
+        to_slots(b + jf.bv.o_vkidx, (size_t)16 * jf.bv.G);                           // the virtual items' kidx
+        to_slots(b + jf.bv.o_vslots + jf.bv.v_slots, jf.bv.v_uni / KEY_SLOTS_PER_WAVE);      // and their wave keys
+    }
+    constexpr size_t KW = 2 * C::FpP::NC;
+    const size_t m = p.miss_key.size();
+    jk.slot_at = jk.oct_at + m * KW;
+    words.resize(jk.slot_at + m);
+    for (size_t t = 0; t < m; t++) {
+        std::memcpy(words.data() + jk.oct_at + t * KW, jk.pk_octets + (size_t)p.miss_key[t] * 2 * Ctx<C>::FPB, 2 * Ctx<C>::FPB);
+        words[jk.slot_at + t] = p.miss_slot[t];
+    }
 }
 // the device half of a job-local key set, behind the staging image: d = the words' place on the device
 template <class C>
-void job_keys_bind(JobKeys<C>& jk, const uint32_t* d) { jk.d_oct = d + jk.oct_at; }
+void job_keys_bind(JobKeys<C>& jk, const uint32_t* d) { jk.d_oct = d + jk.oct_at; jk.d_slot_of = d + jk.slot_at; }
 // the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
 template <class C, class J>
 void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, JobForm<C>& jf, std::vector<uint32_t>& words) {
@@ -253,14 +305,51 @@ int keyed_sign_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, J
 }
 // A job-local key set, first half (in front of keyed_order): the checks of the call and the entries' array, which the plan points at.
 // on = the upload came through a bbs_*_with_keys_* export.
+// With the job-local key cache on, the look at the cache happens here as well (jf.form has been decided): the generation of the
+// job's form, the plan of its keys -- hits pinned, slots claimed for the misses, or the job bypassed -- and the events of hit
+// slots another job is still publishing.  The job's own arrays then hold its misses only.
 template <class C, class J>
-int job_keys_begin(J* j, bool on, size_t n_keys, const uint8_t* pk_octets, JobKeys<C>& jk) {
+int job_keys_cache_plan(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
+    JobKeys<C>& jk = jf.jk;
+    {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        if (!ctx->job_key_cache_cap) return BBS_OK;
+    }
+    std::shared_ptr<const typename Ctx<C>::KeyBlob> kb;
+    if (const int rc = ctx->sync_key_blob(kb)) return rc;
+    const uint32_t stride = jf.form == Form::KeyedMixed ? (uint32_t)ctx->L + 1 : 0;
+    auto pin = std::make_shared<KeyCachePin<C>>();      // (declared in front of the lock: its destructor takes it)
+    pin->ctx = ctx;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (!ctx->job_key_cache_cap) return BBS_OK;
+    if (const int rc = ctx->job_key_cache_gen(kb, ctx->lines_unit(), stride, pin->gen)) return rc;
+    if (!pin->gen->book.plan(jk.pk_octets, jk.n_keys, pin->plan, ctx->job_key_cache_counters)) {
+        ctx->job_key_cache_counters.bypassed_jobs++;
+        j->key_cache_bypassed = true;
+        return BBS_OK;
+    }
+    for (const uint32_t s : pin->plan.hit_slots) {
+        auto& e = pin->gen->slot_event[s];
+        if (!e) continue;
+        if (rt::event_done(e->ev)) { e.reset(); continue; }
+        if (std::find(jk.wait_events.begin(), jk.wait_events.end(), e) == jk.wait_events.end()) jk.wait_events.push_back(e);
+    }
+    jk.cache = pin->gen.get(); jk.plan = &pin->plan;
+    j->key_cache_hits = pin->plan.hits; j->key_cache_misses = pin->plan.misses;
+    j->key_cache_pin = pin;
+    return BBS_OK;
+}
+template <class C, class J>
+int job_keys_begin(J* j, Ctx<C>* ctx, bool on, size_t n_keys, const uint8_t* pk_octets, PairedJobForm<C>& jf) {
+    JobKeys<C>& jk = jf.jk;
     jk.on = on;
     if (!on) return BBS_OK;
     if ((n_keys && !pk_octets) || n_keys > 0xFFFFFFF0ull) return BBS_E_ARG;
     jk.n_keys = n_keys; jk.pk_octets = pk_octets;
+    j->has_job_keys = true;
+    if (const int rc = job_keys_cache_plan<C>(j, ctx, jf)) return rc;
     int rc = BBS_OK;
-    jk.entries = j->template scratch<KeyEntry<C>>(std::max<size_t>(n_keys, 1), rc);
+    jk.entries = j->template scratch<KeyEntry<C>>(std::max<size_t>(jk.n_build(), 1), rc);
     return rc;
 }
 // second half, behind form_bind and in front of the ingest kernel: KeyBuild (and KeyLenBuild) on the job's main stream, the
@@ -270,13 +359,22 @@ int job_keys_launch(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
     JobKeys<C>* jk = &jf.jk;
     if (!jk->on) return BBS_OK;
     const uint32_t stride = jf.form == Form::KeyedMixed ? (uint32_t)ctx->L + 1 : 0;
+    if (jk->cache && (jk->cache->unit != jf.unit || jk->cache->stride != stride)) return BBS_E_STATE;      // (a form switched between the two looks: fail closed)
     auto alloc = [j](size_t b) -> void* { int rc = BBS_OK; return j->template scratch<uint8_t>(std::max<size_t>(b, 1), rc); };
     if (const int rc = job_keys_prepare<C>(ctx, j->stream(), *jk, jf.unit, stride, alloc, j->key_blob)) return rc;
-    if (stride) jf.src.pref = jk->rows;
+    if (stride) jf.src.pref = jk->use_rows();
     j->key_statuses = [j, jk](std::vector<int8_t>& v) {
         v.assign(jk->n_keys, 0);
         if (j->use() || rt::sync(j->stream())) return (int)BBS_E_HIP;
-        return (jk->n_keys && rt::d2h(v.data(), jk->status, v.size(), j->stream())) ? (int)BBS_E_HIP : (int)BBS_OK;
+        if (!jk->n_keys) return (int)BBS_OK;
+        if (!jk->cache) return rt::d2h(v.data(), jk->status, v.size(), j->stream()) ? (int)BBS_E_HIP : (int)BBS_OK;
+        // a cached job: the codes of its slots, in the job's key order (one copy of the span of slots it names)
+        const std::vector<uint32_t>& slot_of = jk->plan->slot_of;
+        const auto mm = std::minmax_element(slot_of.begin(), slot_of.end());
+        std::vector<int8_t> span((size_t)*mm.second - *mm.first + 1);
+        if (rt::d2h(span.data(), jk->use_status() + *mm.first, span.size(), j->stream())) return (int)BBS_E_HIP;
+        for (size_t k = 0; k < v.size(); k++) v[k] = span[slot_of[k] - *mm.first];
+        return (int)BBS_OK;
     };
     return BBS_OK;
 }
@@ -307,8 +405,12 @@ int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
 // the same place in a verify / proof_verify job: the context's key set, or the job's own (JobKeyGate: the device decides)
 template <class C, class J>
 int paired_keyed_gate(J* j, size_t n, const PairedJobForm<C>& jf, int8_t* status0) {
-    if (jf.jk.on) return job_keys_gate<C>(j->stream(), jf.jk, jf.unit, n, jf.src.kidx, status0);
-    return keyed_gate(j, n, jf.src.kidx, status0);
+    if (!jf.jk.on) return keyed_gate(j, n, jf.src.kidx, status0);
+    // a cached job that hit a slot another job is still publishing: its main stream waits on the device, here, in front of the
+    // first kernel that reads an entry (the host never waits)
+    for (const auto& e : jf.jk.wait_events)
+        if (rt::stream_wait(j->stream(), e->ev)) return BBS_E_HIP;
+    return job_keys_gate<C>(j->stream(), jf.jk, jf.unit, n, jf.src.kidx, status0);
 }
 #if !defined(BBS_HOST_TWIN)
 // the keyed fused kernel over the slots of the pairing order (runtime.hpp launch_line_form)

@@ -312,12 +312,15 @@ int selftest_key_entries(Ctx<C>* ctx, size_t n, const uint8_t* rec, const int8_t
 // The keys of one job on the job's stream st, asynchronously: the entries cleared (KeyBuild wants them zeroed), KeyBuild in its
 // octet form over the strings in the job's staging image, and -- stride != 0: a job of mixed counts -- KeyLenBuild into the job's
 // own rows.  Nothing is copied back; nothing waits.  Every buffer comes from the job (alloc) and lives as long as it does.
+template <class C> int job_keys_publish(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, uint32_t stride);
 template <class C>
 int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uint32_t stride, const std::function<void*(size_t)>& alloc,
                      std::shared_ptr<const void>& blob_held) {
-    const size_t nk = jk.n_keys;
+    // (a cached job: its misses only, hashed with what its generation of the cache was built under)
+    const size_t nk = jk.n_build();
     std::shared_ptr<const typename Ctx<C>::KeyBlob> kb;
-    if (const int rc = ctx->sync_key_blob(kb)) return rc;
+    if (jk.cache) kb = jk.cache->blob;
+    else if (const int rc = ctx->sync_key_blob(kb)) return rc;
     blob_held = kb;
     KeyBuildArgs<C> a{};
     size_t n_steps = 0;
@@ -337,17 +340,73 @@ int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uin
     a.suffix = kb->suffix();
     a.suffix_len = (uint32_t)kb->suffix_len();
     if (rt::launch<KeyBuild<C>>(st, a, nk)) return BBS_E_HIP;
-    if (!stride) return BBS_OK;
-    KeyLenBuildArgs<C> la{};
-    la.n_keys = nk; la.stride = stride; la.oct = jk.d_oct; la.key_status = jk.status;
-    la.cg = kb->cg(); la.api_id = kb->api(); la.api_len = (uint32_t)kb->api_len;
-    la.hash0 = kb->hash0(); la.out = jk.rows;
-    return rt::launch<KeyLenBuild<C>>(st, la, nk * stride) ? BBS_E_HIP : BBS_OK;
+    if (stride) {
+        KeyLenBuildArgs<C> la{};
+        la.n_keys = nk; la.stride = stride; la.oct = jk.d_oct; la.key_status = jk.status;
+        la.cg = kb->cg(); la.api_id = kb->api(); la.api_len = (uint32_t)kb->api_len;
+        la.hash0 = kb->hash0(); la.out = jk.rows;
+        if (rt::launch<KeyLenBuild<C>>(st, la, nk * stride)) return BBS_E_HIP;
+    }
+    return jk.cache ? job_keys_publish<C>(ctx, st, jk, stride) : (int)BBS_OK;
+}
+// A cached job's misses into their slots (KeyCachePublish), ONE event behind the kernel, and only then -- under the context's
+// mutex -- the slots become hits for the jobs planned from now on, carrying the event: a job on another stream that hits one
+// before the event has completed waits for it on the device (job_form.hpp paired_keyed_gate).
+template <class C>
+int job_keys_publish(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, uint32_t stride) {
+    typename Ctx<C>::KeyCacheGen& gen = *jk.cache;
+    const size_t m = jk.n_build();
+    if (stride != gen.stride) return BBS_E_STATE;
+    KeyCachePublishArgs<C> pa{};
+    pa.n_miss = m; pa.stride = stride; pa.slot_of = jk.d_slot_of;
+    pa.src_entries = jk.entries; pa.src_status = jk.status; pa.src_rows = jk.rows;
+    pa.dst_entries = gen.entries.template as<KeyEntry<C>>(); pa.dst_status = gen.status.template as<int8_t>(); pa.dst_rows = gen.rows.template as<HashCtx>();
+    if (rt::launch<KeyCachePublish<C>>(st, pa, KeyCachePublish<C>::lanes(m, stride))) return BBS_E_HIP;
+    auto ev = std::make_shared<typename Ctx<C>::KeyCacheEvent>();
+    ev->device = ctx->device;
+    if (rt::event_create(&ev->ev)) return BBS_E_HIP;
+    ev->ok = true;
+    if (rt::event_record(ev->ev, st)) return BBS_E_HIP;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    gen.book.commit(*jk.plan);
+    for (const uint32_t s : jk.plan->miss_slot) gen.slot_event[s] = ev;
+    return BBS_OK;
 }
 template <class C>
 int job_keys_gate(rt::Stream& st, const JobKeys<C>& jk, bool unit, size_t n, const uint32_t* kidx, int8_t* status0) {
-    JobKeyGateArgs<C> g{n, kidx, jk.entries, jk.status, unit ? 1 : 0, status0};
+    JobKeyGateArgs<C> g{n, kidx, jk.use_entries(), jk.use_status(), unit ? 1 : 0, status0};
     return rt::launch<JobKeyGate<C>>(st, g, n) ? BBS_E_HIP : BBS_OK;
+}
+
+// bbs_selftest_job_key_cache_entries: what the current generation of the cache holds for n strings -- entry, status and (where
+// the cache holds rows and rows_out is given) the L + 1 rows of each, behind the publishing kernels that wrote them.
+// BBS_E_STATE: the cache is off, or one of the strings is not resident.
+template <class C>
+int selftest_job_key_cache_entries(Ctx<C>* ctx, size_t n, const uint8_t* oct, uint8_t* entries_out, int8_t* status_out, uint8_t* rows_out) {
+    if (ctx->use()) return BBS_E_HIP;
+    std::shared_ptr<typename Ctx<C>::KeyCacheGen> gen;
+    std::vector<uint32_t> slots(n);
+    std::vector<std::shared_ptr<typename Ctx<C>::KeyCacheEvent>> evs;
+    {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        gen = ctx->job_key_cache;
+        if (!gen) return BBS_E_STATE;
+        for (size_t k = 0; k < n; k++) {
+            if (!gen->book.find_ready(oct + k * 2 * Ctx<C>::FPB, slots[k])) return BBS_E_STATE;
+            if (gen->slot_event[slots[k]]) evs.push_back(gen->slot_event[slots[k]]);
+        }
+    }
+    for (const auto& e : evs)
+        if (rt::stream_wait(ctx->stream, e->ev)) return BBS_E_HIP;
+    if (rt::sync(ctx->stream)) return BBS_E_HIP;
+    const size_t rb = (size_t)gen->stride * sizeof(HashCtx);
+    for (size_t k = 0; k < n; k++) {
+        const size_t s = slots[k];
+        if (rt::d2h(entries_out + k * sizeof(KeyEntry<C>), gen->entries.template as<KeyEntry<C>>() + s, sizeof(KeyEntry<C>), ctx->stream) ||
+            rt::d2h(status_out + k, gen->status.template as<int8_t>() + s, 1, ctx->stream)) return BBS_E_HIP;
+        if (rows_out && rb && rt::d2h(rows_out + k * rb, gen->rows.template as<uint8_t>() + s * rb, rb, ctx->stream)) return BBS_E_HIP;
+    }
+    return rt::sync(ctx->stream) ? BBS_E_HIP : BBS_OK;
 }
 
 // bbs_selftest_key_len_rows: the prefixes per (key, length) of n keys given as octets, [n][L + 1] HashCtx, by path 0 = the host

@@ -39,7 +39,7 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     std::vector<uint32_t> kwords;     // keyed: key indexes and pairing order, in the staging image
     size_t kwords_at = 0;
     if constexpr (KEYED) {
-        if (const int rck = job_keys_begin<C>(job.get(), in.job_keys, in.n_keys, in.pk_octets, job->jf.jk)) return rck;
+        if (const int rck = job_keys_begin<C>(job.get(), ctx, in.job_keys, in.n_keys, in.pk_octets, job->jf)) return rck;
         keyed_order<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
     }
     // the batch as one staging image, one asynchronous copy; checks, range checks and the SoA transposition on the

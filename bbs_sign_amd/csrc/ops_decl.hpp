@@ -155,3 +155,6 @@ extern template int sk_to_pk_batch<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t
 template <class C> int selftest_key_len_rows(Ctx<C>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
 extern template int selftest_key_len_rows<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
 extern template int selftest_key_len_rows<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
+template <class C> int selftest_job_key_cache_entries(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
+extern template int selftest_job_key_cache_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
+extern template int selftest_job_key_cache_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);

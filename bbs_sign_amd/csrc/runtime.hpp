@@ -30,6 +30,7 @@
 #include "codec_dev.hpp"
 #include "keyed.hpp"
 #include "queue_policy.hpp"
+#include "key_cache.hpp"
 
 using namespace bbs;
 
@@ -88,6 +89,7 @@ inline int event_create(Event*) { return 0; }
 inline void event_destroy(Event&) {}
 inline int event_record(Event&, Stream&) { return 0; }
 inline int stream_wait(Stream&, Event&) { return 0; }
+inline bool event_done(Event&) { return true; }
 template <class F, class A>
 inline int launch(Stream&, const A& a, size_t nthreads) {
     for (size_t t = 0; t < nthreads; t++) F::run(a, t);
@@ -413,6 +415,12 @@ inline void event_destroy(Event& e) {
 }
 inline int event_record(Event& e, Stream& s) { return hipEventRecord(e, s) == hipSuccess ? 0 : -1; }
 inline int stream_wait(Stream& s, Event& e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess ? 0 : -1; }
+// everything in front of the event's last record has finished (an event never recorded counts as done)
+inline bool event_done(Event& e) {
+    if (hipEventQuery(e) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
 
 // stages may declare `static constexpr int WAVES_PER_EU = k;` to cap their register allocation at
 // 512 / k VGPRs so that k wavefronts fit on one SIMD
@@ -697,6 +705,66 @@ struct Ctx : bbs_ctx {
             key_blob = std::move(kb);
         }
         out = key_blob;
+        return BBS_OK;
+    }
+    // The job-local key cache (bbs_ctx_set_job_key_cache; job_form.hpp job_keys_begin, DESIGN.md 8 "Job-local key cache"): off by
+    // default (capacity 0).  On: the prepared keys of the bbs_*_with_keys_* jobs stay in `capacity` slots on the device, found
+    // again by their whole compressed string (key_cache.hpp).  ONE generation = the entries prepared under one KeyBlob (generators,
+    // api_id), one line form and one row stride (0, or L + 1 under keyed mixed lengths); a job whose form differs starts a new,
+    // empty generation, the old one lives on through the jobs that hold it.  The device arrays are allocated by the first cached
+    // job of a generation.  Everything here is read and written under `mu`.
+    struct KeyCacheEvent {               // behind the publishing kernel of one job; its slots carry it until it has completed
+        rt::Event ev{};
+        int device = 0;
+        bool ok = false;
+        ~KeyCacheEvent() { if (ok) { (void)rt::set_device(device); rt::event_destroy(ev); } }
+    };
+    struct KeyCacheGen {
+        KeyCacheBook book;
+        std::shared_ptr<const KeyBlob> blob;
+        bool unit = false;
+        uint32_t stride = 0;
+        DevBuf entries, status, rows;    // [capacity] KeyEntry<C>, [capacity] codes, [capacity][stride] HashCtx
+        std::vector<std::shared_ptr<KeyCacheEvent>> slot_event;      // null: nothing to wait for
+        KeyCacheGen(size_t cap, size_t key_bytes) : book(cap, key_bytes), slot_event(cap) {}
+        size_t device_bytes() const { return entries.bytes + status.bytes + rows.bytes; }
+    };
+    size_t job_key_cache_cap = 0;
+    std::shared_ptr<KeyCacheGen> job_key_cache;
+    KeyCacheCounters job_key_cache_counters;
+    int set_job_key_cache(size_t capacity_keys) {
+        if (capacity_keys > 0xFFFFFFF0ull) return BBS_E_ARG;
+        std::lock_guard<std::mutex> g(mu);
+        if (capacity_keys != job_key_cache_cap) job_key_cache.reset();
+        job_key_cache_cap = capacity_keys;
+        return BBS_OK;
+    }
+    void job_key_cache_report(size_t* capacity, size_t* resident, size_t* pinned, uint64_t* hits, uint64_t* misses, uint64_t* evictions,
+                              uint64_t* bypassed_jobs, size_t* device_bytes) {
+        std::lock_guard<std::mutex> g(mu);
+        const auto gen = job_key_cache;
+        const KeyCacheCounters& c = job_key_cache_counters;
+        if (capacity) *capacity = job_key_cache_cap;
+        if (resident) *resident = gen ? gen->book.resident() : 0;
+        if (pinned) *pinned = gen ? gen->book.pinned() : 0;
+        if (hits) *hits = c.hits;
+        if (misses) *misses = c.misses;
+        if (evictions) *evictions = c.evictions;
+        if (bypassed_jobs) *bypassed_jobs = c.bypassed_jobs;
+        if (device_bytes) *device_bytes = gen ? gen->device_bytes() : 0;
+    }
+    // The generation a job of this form uses (mu is held): the current one if it was built under the same blob, line form and
+    // stride, else a new, empty one in its place.  The arrays are allocated here, by the first job that needs them.
+    int job_key_cache_gen(const std::shared_ptr<const KeyBlob>& kb, bool unit, uint32_t stride, std::shared_ptr<KeyCacheGen>& out) {
+        auto gen = job_key_cache;
+        if (!gen || gen->blob != kb || gen->unit != unit || gen->stride != stride) {
+            gen.reset(new KeyCacheGen(job_key_cache_cap, 2 * (size_t)FPB));
+            gen->blob = kb; gen->unit = unit; gen->stride = stride;
+            const size_t cap = job_key_cache_cap;
+            if (gen->entries.alloc(cap * sizeof(KeyEntry<C>)) || gen->status.alloc(cap) || (stride && gen->rows.alloc(cap * stride * sizeof(HashCtx)))) return BBS_E_NOMEM;
+            job_key_cache = gen;
+        }
+        out = gen;
         return BBS_OK;
     }
     // mixed message counts (bbs_ctx_set_mixed_lengths): off by default.  On: the single-key verify / proof_verify jobs created
@@ -1103,6 +1171,9 @@ struct bbs_job {
     std::function<int(std::vector<int8_t>&)> bv_verdicts;
     // bbs_job_key_statuses: set by a job with a job-local key set (job_form.hpp JobKeys): KeyBuild's code per key, read back on request
     std::function<int(std::vector<int8_t>&)> key_statuses;
+    // bbs_job_key_cache_report: a job that came through a bbs_*_with_keys_* export says what the job-local key cache did for it
+    bool has_job_keys = false, key_cache_bypassed = false;
+    uint32_t key_cache_hits = 0, key_cache_misses = 0;
     virtual int fetch_signatures(uint8_t*) { return BBS_E_ARG; }
     virtual int fetch_proofs(uint8_t*, uint8_t*, uint64_t*) { return BBS_E_ARG; }
     // One pass over the stages.  ev != nullptr: one event before the first stage, then a (start, stop) pair around
@@ -1186,6 +1257,7 @@ struct JobBase : bbs_job {
     std::shared_ptr<const void> len_set;     // mixed-length jobs: the context's per-length domain prefixes at upload (likewise)
     std::shared_ptr<const void> key_len_set; // keyed jobs of mixed counts: the prefixes per (key, length) at upload (likewise)
     std::shared_ptr<const void> key_blob;    // jobs with a job-local key set: what their keys were hashed with (likewise)
+    std::shared_ptr<void> key_cache_pin;     // cached jobs: the generation they read and their pins on its slots (likewise)
     std::shared_ptr<const void> sign_key_set;// keyed sign jobs: the context's signing set at upload (likewise; the last holder clears it)
     // every job owns its streams: independent jobs (batches) of one context overlap on the GPU
     rt::Stream main{}, aux[bbs_job::N_AUX]{};

@@ -470,4 +470,47 @@ struct KeyLenBuild {
     }
 };
 
+// ---- the job-local key cache (bbs_ctx_set_job_key_cache; job_form.hpp, key_cache.hpp) ------------------------------------------
+// Behind KeyBuild (and KeyLenBuild) of a cached job, which prepared the job's MISSES into arrays of the job: miss t -- its
+// entry, its status byte, its `stride` rows -- is copied into slot slot_of[t] of the cache's arrays, all of it (no slot is
+// cleared beforehand).  One lane per unit of U bytes, U = 16 where the two structures are whole multiples of 16 bytes (they
+// are: the assertion below says so for the curve at hand), else 4.  The lanes [t * per_key, (t + 1) * per_key) belong to key t:
+// first the units of the entry, then those of the rows, the last lane the status byte -- consecutive lanes take consecutive
+// units of one key, so the loads and stores of a wavefront coalesce.  Neither KeyBuild nor KeyLenBuild knows of the cache.
+template <class C>
+struct KeyCachePublishArgs {
+    size_t n_miss;
+    uint32_t stride;             // rows per key (0: the cache holds no rows)
+    const uint32_t* slot_of;     // [n_miss], distinct, < capacity (in the job's staging image)
+    const KeyEntry<C>* src_entries;
+    const int8_t* src_status;
+    const HashCtx* src_rows;     // [n_miss][stride]
+    KeyEntry<C>* dst_entries;    // the cache's arrays, [capacity]
+    int8_t* dst_status;
+    HashCtx* dst_rows;           // [capacity][stride]
+};
+template <class C>
+struct KeyCachePublish {
+    static constexpr bool WIDE = sizeof(KeyEntry<C>) % 16 == 0 && sizeof(HashCtx) % 16 == 0;
+    static constexpr size_t U = WIDE ? 16 : 4;
+    static_assert(sizeof(KeyEntry<C>) % U == 0 && sizeof(HashCtx) % U == 0, "KeyCachePublish copies whole units");
+    static_assert(alignof(KeyEntry<C>) >= 4 && alignof(HashCtx) >= 4, "KeyCachePublish reads words");
+    struct alignas(WIDE ? 16 : 4) Unit { uint32_t w[WIDE ? 4 : 1]; };
+    static constexpr size_t E_UNITS = sizeof(KeyEntry<C>) / U, R_UNITS = sizeof(HashCtx) / U;
+    static size_t lanes(size_t n_miss, uint32_t stride) { return n_miss * (E_UNITS + (size_t)stride * R_UNITS + 1); }
+    static __host__ __device__ void run(const KeyCachePublishArgs<C>& a, size_t i) {
+        const size_t row_units = (size_t)a.stride * R_UNITS, per_key = E_UNITS + row_units + 1;
+        const size_t t = i / per_key, u = i - t * per_key;
+        const size_t s = a.slot_of[t];
+        if (u < E_UNITS) {
+            reinterpret_cast<Unit*>(a.dst_entries + s)[u] = reinterpret_cast<const Unit*>(a.src_entries + t)[u];
+        } else if (u < E_UNITS + row_units) {
+            const size_t r = u - E_UNITS;
+            reinterpret_cast<Unit*>(a.dst_rows + s * a.stride)[r] = reinterpret_cast<const Unit*>(a.src_rows + t * a.stride)[r];
+        } else {
+            a.dst_status[s] = a.src_status[t];
+        }
+    }
+};
+
 }  // namespace bbs

@@ -11,3 +11,4 @@ template int selftest_key_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_
 template int job_keys_prepare<BlsCurve>(Ctx<BlsCurve>*, rt::Stream&, JobKeys<BlsCurve>&, bool, uint32_t, const std::function<void*(size_t)>&, std::shared_ptr<const void>&);
 template int job_keys_gate<BlsCurve>(rt::Stream&, const JobKeys<BlsCurve>&, bool, size_t, const uint32_t*, int8_t*);
 template int selftest_key_len_rows<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
+template int selftest_job_key_cache_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);

@@ -11,3 +11,4 @@ template int selftest_key_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*
 template int job_keys_prepare<BnCurve>(Ctx<BnCurve>*, rt::Stream&, JobKeys<BnCurve>&, bool, uint32_t, const std::function<void*(size_t)>&, std::shared_ptr<const void>&);
 template int job_keys_gate<BnCurve>(rt::Stream&, const JobKeys<BnCurve>&, bool, size_t, const uint32_t*, int8_t*);
 template int selftest_key_len_rows<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
+template int selftest_job_key_cache_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);

@@ -503,6 +503,43 @@ class Engine:
         key with its own message count 0 .. L (jobs created afterwards); independent of set_mixed_lengths."""
         self._chk(self.lib.bbs_ctx_set_keyed_mixed_lengths(self.h, 1 if on else 0), "bbs_ctx_set_keyed_mixed_lengths")
 
+    def set_job_key_cache(self, capacity: int):
+        """bbs_ctx_set_job_key_cache: the ``*_with_keys_*`` jobs uploaded afterwards keep their prepared keys in ``capacity``
+        slots on the device and find them again by their compressed string; 0 (the default) switches the cache off and
+        drops it.  Same statuses either way."""
+        self._chk(self.lib.bbs_ctx_set_job_key_cache(self.h, int(capacity)), "bbs_ctx_set_job_key_cache")
+
+    def job_key_cache_report(self) -> dict:
+        """bbs_ctx_job_key_cache_report: capacity, resident, pinned (slots), hits, misses, evictions, bypassed_jobs (counted
+        since the engine was created), device_bytes."""
+        s = [ctypes.c_size_t(0) for _ in range(4)]
+        u = [ctypes.c_uint64(0) for _ in range(4)]
+        self._chk(self.lib.bbs_ctx_job_key_cache_report(self.h, ctypes.byref(s[0]), ctypes.byref(s[1]), ctypes.byref(s[2]), ctypes.byref(u[0]),
+                                                        ctypes.byref(u[1]), ctypes.byref(u[2]), ctypes.byref(u[3]), ctypes.byref(s[3])),
+                  "bbs_ctx_job_key_cache_report")
+        return {"capacity": s[0].value, "resident": s[1].value, "pinned": s[2].value, "hits": u[0].value, "misses": u[1].value,
+                "evictions": u[2].value, "bypassed_jobs": u[3].value, "device_bytes": s[3].value}
+
+    def selftest_job_key_cache_entries(self, key_octets, rows: bool = False):
+        """bbs_selftest_job_key_cache_entries -> (entries [n] of bytes, statuses, rows or None): what the job-local key cache
+        holds for each string; rows[k][l] as selftest_key_len_rows gives them.  BbsRuntimeError (-102) if one is not resident."""
+        n = len(key_octets)
+        eb = int(self.lib.bbs_selftest_key_entry_bytes(self.curve))
+        hb = int(self.lib.bbs_selftest_hash_ctx_bytes())
+        S = self.L + 1
+        ko = self._key_octets(key_octets)
+        ent = np.zeros(max(n * eb, 1), dtype=np.uint8)
+        st = np.full(max(n, 1), -128, dtype=np.int8)
+        rw = np.zeros(max(n * S * hb, 1), dtype=np.uint8) if rows else None
+        self._chk(self.lib.bbs_selftest_job_key_cache_entries(self.h, n, _u8(ko), _u8(ent), st.ctypes.data_as(_lib.c_i8p), _u8(rw) if rows else None),
+                  "bbs_selftest_job_key_cache_entries")
+        e = ent.tobytes()
+        out_rows = None
+        if rows:
+            b = rw.tobytes()
+            out_rows = [[b[(k * S + l) * hb:(k * S + l + 1) * hb] for l in range(S)] for k in range(n)]
+        return [e[k * eb:(k + 1) * eb] for k in range(n)], st[:n], out_rows
+
     def set_unit_lines(self, on: bool):
         """bbs_ctx_set_unit_lines: the Miller-loop line tables of this engine in the unit form (the default) or the (c, nl)
         form; rebuilds the tables, same verdicts."""
@@ -1369,6 +1406,13 @@ class Job:
             rc = self.eng.lib.bbs_job_key_statuses(self.h, out.ctypes.data_as(_lib.c_i8p), out.size, ctypes.byref(cnt))
         Engine._chk(rc, "bbs_job_key_statuses")
         return out[:cnt.value]
+
+    def key_cache_report(self) -> dict:
+        """bbs_job_key_cache_report: what the job-local key cache did for this ``*_with_keys_*`` job -- hits, misses (hits +
+        misses == the number of keys for a cached job; both 0 with the cache off) and bypassed."""
+        h, m, b = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int(0)
+        Engine._chk(self.eng.lib.bbs_job_key_cache_report(self.h, ctypes.byref(h), ctypes.byref(m), ctypes.byref(b)), "bbs_job_key_cache_report")
+        return {"hits": h.value, "misses": m.value, "bypassed": b.value}
 
     def bv_verdicts(self) -> np.ndarray:
         """bbs_job_bv_verdicts, after wait(): the raw verdict flags of the last run's combined checks (1 = passed) -- 16 for a

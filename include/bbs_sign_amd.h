@@ -539,8 +539,8 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
  * bbs_job_device_bytes: per key the entry, 22 848 bytes of workspace on BLS12-381, a status byte, and (L + 1) prefixes of
  * 368 bytes in jobs of mixed counts) and releases with the job.  The context's key set is neither read nor changed; a context
  * without a public key or a key set serves these calls.  The key bytes are copied into the job's staging image by the call: the
- * caller's array is free when _submit returns.  The library does NOT deduplicate: a key given twice is prepared twice and is
- * two keys.  The keys are prepared with the upload, as the ingest kernel runs with the upload: bbs_job_run on the same job
+ * caller's array is free when _submit returns.  The library does NOT deduplicate with the cache off: a key given twice is
+ * prepared twice and is two keys.  The keys are prepared with the upload, as the ingest kernel runs with the upload: bbs_job_run on the same job
  * runs the stages again over the same prepared keys.
  * Arguments: those of the keyed twin with n_keys and pk_octets in front of key_index.
  * STATUS RULE: the status array is, bit for bit, what the keyed twin returns on a context with the same generators, api_id and
@@ -563,8 +563,8 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
  * bbs_job_key_statuses: after bbs_job_wait, the per-key codes (1, BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE) in the order of
  * pk_octets, copied from the device on request (nothing is added to a run); *n_out = n_keys; BBS_E_ARG where cap < n_keys;
  * BBS_E_STATE for a job without a key set of its own.
- * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys; a
- * cache of prepared keys across jobs; preparing a handful of keys on the host instead (one call of the key stage costs one walk
+ * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys;
+ * preparing a handful of keys on the host instead (one call of the key stage costs one walk
  * however few keys it brings); running the key stage beside the MSM stages on a side stream; a faster subgroup test by the
  * curve endomorphism; registration through the device stage. */
 int bbs_core_proof_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
@@ -610,6 +610,50 @@ int bbs_verify_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const
                                     const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
                                     const uint8_t* headers, const uint64_t* hdr_off, int8_t* status);
 int bbs_job_key_statuses(bbs_job* job, int8_t* out, size_t cap, size_t* n_out);
+/* ------------------------------------------------------------------------------------------
+ * THE JOB-LOCAL KEY CACHE: prepared keys kept across the jobs of the eight exports above.  A verifier that resolves the issuer
+ * per presentation sees the same issuers again and again; without the cache every job pays one walk of the key stage for keys
+ * a job before it prepared and released.  bbs_ctx_set_job_key_cache with capacity_keys > 0 gives the context that many key
+ * SLOTS on the device; the jobs of the eight exports uploaded afterwards look every key string up, prepare only the strings no
+ * slot holds (the MISSES, by the same two kernels, into arrays of the job), copy them into their slots with one more small
+ * kernel and read ALL their keys -- entries, statuses, prefixes per (key, length) -- from the cache's arrays.  0 (the default)
+ * switches the cache off and drops it; with it off every job takes the uncached path, bit for bit.  A new capacity starts an empty
+ * cache.
+ * STATUS RULE: unchanged.  The statuses, bbs_job_key_statuses, bbs_job_bv_report and bbs_job_bv_verdicts of a cached job are, bit
+ * for bit, those of the same call with the cache off: the host plans in the job's own key numbering (groups and verdict order
+ * are the keyed twin's) and translates key -> slot where the job's words hold a key id.
+ * LOOKUP: by the WHOLE compressed string of 2 * fp_bytes bytes, compared in full, never by a digest alone.  A refused string is
+ * cached as refused under its own bytes, the identity encoding as the accepted key it is.  hits + misses == n_keys for every
+ * cached job; a string given twice in one call is one miss (or one hit) the first time, a hit after that, and both indexes name
+ * the same slot.
+ * ORDER ACROSS JOBS: a string is entered when the job is planned, its slot carries an event recorded behind the copying kernel.
+ * A later job on another stream that hits the slot before the event has completed waits for it ON THE DEVICE, in front of its
+ * key gate; nothing waits on the host.  An upload that fails after claiming slots gives them back.
+ * PINS AND EVICTION: every slot a job names is pinned from its upload until bbs_job_free (a job may be run again).  Slots for
+ * misses come from the free slots first, then from the unpinned slots, least recently used first (a hit, and a pin by the job
+ * being planned, count as use).  A job is BYPASSED -- takes the uncached path, correct and slower -- if n_keys > capacity, if its
+ * misses outnumber the free and evictable slots, or if one of its strings is claimed by an upload another host thread has not
+ * finished yet.
+ * GENERATIONS: the cached entries depend on the generators and api_id, on the line form and on whether prefixes per
+ * (key, length) are kept.  A job whose form differs from the cache's -- after bbs_ctx_set_generators, bbs_ctx_set_unit_lines, a
+ * registration that moved the context to the (c, nl) form, bbs_ctx_set_keyed_mixed_lengths -- starts a new, empty generation; the
+ * old one lives on through the jobs that hold it.
+ * MEMORY: allocated by the first cached job, capacity * (entry + 1 + (L + 1) * 368 bytes under keyed mixed lengths; 0 otherwise):
+ * about 41 KB per key on BLS12-381 at L = 32 with mixed counts.  BBS_E_NOMEM from that upload if it cannot be had.
+ * The fail-closed case above is unchanged: a cached key without a unit form is refused by the gate of every job.
+ * Key strings are public; what the cache reveals (through timing and the reports) is which issuers a context has seen.
+ * bbs_ctx_set_job_key_cache: BBS_E_ARG for a NULL ctx or capacity_keys > 0xFFFFFFF0.
+ * bbs_ctx_job_key_cache_report: capacity, slots that hold a string, slots pinned by jobs; hits, misses, evictions and bypassed
+ * jobs counted since the context was created; device bytes of the current generation.  Any out-pointer may be NULL.
+ * bbs_job_key_cache_report: hits and misses of this job (both 0 where the cache was off or the job was bypassed), *bypassed;
+ * any out-pointer may be NULL; BBS_E_STATE for a job that did not come through one of the eight exports.
+ * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys; a
+ * lookup on the device. */
+int bbs_ctx_set_job_key_cache(bbs_ctx* ctx, size_t capacity_keys);
+int bbs_ctx_job_key_cache_report(bbs_ctx* ctx, size_t* capacity, size_t* resident, size_t* pinned,
+                                 uint64_t* hits, uint64_t* misses, uint64_t* evictions,
+                                 uint64_t* bypassed_jobs, size_t* device_bytes);
+int bbs_job_key_cache_report(bbs_job* job, uint32_t* hits, uint32_t* misses, int* bypassed);
 /* Keyed forms of bbs_core_proof_gen_* and bbs_proof_gen_wire_*: ONE context derives proofs from signatures of MANY issuers.
  * The reference takes the public key per call (src/proof_gen.rs:78-113) and uses it in calculate_domain alone -- no pairing,
  * no W -- so a keyed item reads its key's domain midstate from the key set the keyed verify entry points use, and everything
@@ -1102,6 +1146,11 @@ size_t bbs_selftest_key_entry_bytes(int curve);
  * set runs (the key stage, then one lane per (key, length)).  rows_out: n x (L + 1) x bbs_selftest_hash_ctx_bytes() bytes, rows of
  * a refused key as every row starts out; status_out: n.  Needs the generators; does not touch the context's key set. */
 int bbs_selftest_key_len_rows(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int path, uint8_t* rows_out, int8_t* status_out);
+/* self-test of the job-local key cache: what the cache holds for each of n strings -- the entry (bbs_selftest_key_entry_bytes
+ * each), the status and, where the cache holds rows and rows_out is not NULL, the L + 1 prefixes (bbs_selftest_hash_ctx_bytes
+ * each); BBS_E_STATE if the cache is off or one of the strings is not resident */
+int bbs_selftest_job_key_cache_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets,
+                                       uint8_t* entries_out, int8_t* status_out, uint8_t* rows_out /* may be NULL */);
 size_t bbs_selftest_hash_ctx_bytes(void);
 /* Keyed batch verification self-test: the segmented bucket kernel and the group sums alone (stages keyed_pip_windows and
  * keyed_pip_group_sums).  n affine G1 points (2 * fp_bytes each, canonical LE, zeros = the identity) given in group order,
