@@ -157,6 +157,16 @@ SIGNATURES = {
                                              c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
     "bbs_proof_gen_wire_keyed_batch": (ci, [vp, sz, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p,
                                             c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    # proof_gen under a key set of the call: the keyed forms with n_keys, pk_octets in front of key_index
+    "bbs_core_proof_gen_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                                 c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_core_proof_gen_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                                c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u8p, c_u64p, c_i8p]),
+    "bbs_proof_gen_wire_with_keys_submit": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                                 c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p, ctypes.POINTER(vp)]),
+    "bbs_proof_gen_wire_with_keys_batch": (ci, [vp, sz, sz, c_u8p, c_u32p, c_u8p, c_u8p, c_u64p, c_u64p, c_u64p, c_u64p, c_u8p, c_u64p,
+                                                c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, c_u64p, c_i8p]),
+    "bbs_selftest_key_domain_entries": (ci, [vp, sz, c_u8p, c_u8p, c_i8p]),
     # keyed sign: the signing key set, and the un-keyed forms with key_index after n
     "bbs_ctx_set_secret_keys": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, c_i8p]),
     "bbs_ctx_add_secret_keys": (ci, [vp, sz, c_u8p, c_i8p, c_u8p, c_i8p, c_u32p]),

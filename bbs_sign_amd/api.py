@@ -464,6 +464,21 @@ def sign_many_issuers(items: Sequence[tuple]) -> list:
     return out
 
 
+def _own_keys(ie: _IssuerEngine, its, key_cache=0):
+    """register_keys=False: the distinct keys of ``its`` (entry 0 of an item) as compressed strings, in the order they are met,
+    and the index of every item's key among them -- what the ``*_with_keys_*`` forms take.  Sets the capacity of the cached
+    engine's job-local key cache where it differs from ``key_cache``."""
+    if ie.eng.job_key_cache_report()["capacity"] != int(key_cache):
+        ie.eng.set_job_key_cache(int(key_cache))
+    local: Dict[object, int] = {}
+    key_octets = []
+    for it in its:
+        if ie.name(it[0].pk) not in local:
+            local[ie.name(it[0].pk)] = len(key_octets)
+            key_octets.append(ie.key_octets(it[0]))
+    return key_octets, [local[ie.name(it[0].pk)] for it in its]
+
+
 def _many_issuers(items, count, to_octets, run, batch_verification=False, register_keys=True, run_own=None, key_cache=0):
     """Items of any issuers and counts: ONE device call per (curve, device, lib_path) through the wire keyed forms.
     register_keys=False: the keys are NOT registered on the cached engine -- the call deduplicates the keys of its items, writes
@@ -489,17 +504,9 @@ def _many_issuers(items, count, to_octets, run, batch_verification=False, regist
             call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path),
                                  lambda octs, kept: run(ie.eng, [ie.index[ie.name(it[0].pk)] for it in kept], octs, kept), at=1)
         else:
-            if ie.eng.job_key_cache_report()["capacity"] != int(key_cache):
-                ie.eng.set_job_key_cache(int(key_cache))
-
             def own(octs, kept):
-                local: Dict[object, int] = {}
-                key_octets = []
-                for it in kept:
-                    if ie.name(it[0].pk) not in local:
-                        local[ie.name(it[0].pk)] = len(key_octets)
-                        key_octets.append(ie.key_octets(it[0]))
-                return run_own(ie.eng, key_octets, [local[ie.name(it[0].pk)] for it in kept], octs, kept)
+                key_octets, kidx = _own_keys(ie, kept, key_cache)
+                return run_own(ie.eng, key_octets, kidx, octs, kept)
             call = lambda: _many(its, lambda obj: to_octets(curve, obj, lib_path), own, at=1)
         if batch_verification:
             with _bv_lock:
@@ -552,7 +559,7 @@ def proof_verify_many_issuers(items: Sequence[tuple], batch_verification: bool =
                          key_cache)
 
 
-def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) -> list:
+def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False, register_keys: bool = True, key_cache: int = 0) -> list:
     """proof_gen for many items ``(pk, signature, header, ph, messages, disclosed_indexes[, random_scalars])`` of ANY issuers
     and ANY message counts, in ONE device call per (curve, device, lib_path): the cached engine of verify_many_issuers (its
     keys are registered once, whichever side meets them first), through bbs_proof_gen_wire_keyed_batch.  Entry i is the Proof
@@ -561,14 +568,19 @@ def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) 
     codec's error; a wrong number of random scalars in one item fails the whole call (BbsRuntimeError, BBS_E_ARG), as in
     proof_gen_many; a ``pk`` the library refuses gives ``BbsError(-44)``, the divergence verify_many_issuers describes.
     ``device_random=True``: as proof_gen_many -- when no item gives scalars of its own they are drawn on the device, from one
-    fresh job seed per device call."""
+    fresh job seed per device call.
+    ``register_keys=False`` is for a holder-side service that meets its issuer keys next to the credentials: the keys of THIS
+    list travel with the job (bbs_proof_gen_wire_with_keys_batch), which prepares their domain midstates on the device and
+    releases them; the cached engine's key set and ``index`` stay as they were.  ``key_cache=N`` (with ``register_keys=False``
+    only): as verify_many_issuers -- the prepared keys stay in N slots of the cached engine, shared with the verify functions.
+    The entries are the same."""
     out: list = [None] * len(items)
     on_device = device_random and not any(len(it) > 6 and it[6] is not None for it in items)
     groups: Dict[tuple, List[int]] = {}
     for i, it in enumerate(items):
         groups.setdefault((it[0].curve, it[0].device, it[0].lib_path), []).append(i)
     for (curve, device, lib_path), group in groups.items():
-        ie = _issuer_engine(curve, device, lib_path, max(len(items[i][4]) for i in group), [items[i][0].pk for i in group])
+        ie = _issuer_engine(curve, device, lib_path, max(len(items[i][4]) for i in group), [items[i][0].pk for i in group] if register_keys else [])
         octs, idx = [], []
         for i in group:
             try:
@@ -580,8 +592,10 @@ def proof_gen_many_issuers(items: Sequence[tuple], device_random: bool = False) 
             continue
         its = [items[i] for i in idx]
         def call(r, ie=ie, its=its, octs=octs):
-            return ie.eng.proof_gen_wire_keyed_batch([ie.index[ie.name(it[0].pk)] for it in its], octs, [list(it[4]) for it in its],
-                                                     [list(it[5]) for it in its], r, [it[2] for it in its], [it[3] for it in its])
+            rest = (octs, [list(it[4]) for it in its], [list(it[5]) for it in its], r, [it[2] for it in its], [it[3] for it in its])
+            if register_keys:
+                return ie.eng.proof_gen_wire_keyed_batch([ie.index[ie.name(it[0].pk)] for it in its], *rest)
+            return ie.eng.proof_gen_wire_with_keys_batch(*_own_keys(ie, its, key_cache), *rest)
         if on_device:
             po, st = _device_draw(ie.eng, curve, call)
         else:

@@ -395,17 +395,29 @@ template <bool KEYED>
 static int proof_gen_wire_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sig_octets, const uint8_t* msg_bytes,
                                  const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio,
                                  const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
-                                 uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
+                                 uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
     if (!ctx || !status || !job_out || !oct_off_out || (n && (!octets_out || !sig_octets || !msg_item_off))) return BBS_E_ARG;
     int rc = empty_raw_batch(msg_byte_off, msg_item_off, n);
     if (rc) return rc;
     bbs_job* job = nullptr;
-    rc = upload<KEYED>(ctx, n, PgIn{.msg_off = msg_item_off, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd, .rnd_off = rno, .headers = h,
-                                    .hdr_off = ho, .ph = ph, .ph_off = pho, .signature_octets = sig_octets, .msg_bytes = msg_bytes,
-                                    .msg_byte_off = msg_byte_off, .key_index = key_index}, &job);
+    rc = upload<KEYED>(ctx, n, with_keys(PgIn{.msg_off = msg_item_off, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd, .rnd_off = rno, .headers = h,
+                                              .hdr_off = ho, .ph = ph, .ph_off = pho, .signature_octets = sig_octets, .msg_bytes = msg_bytes,
+                                              .msg_byte_off = msg_byte_off, .key_index = key_index}, wk), &job);
     if (rc) return rc;
     if ((rc = job->set_octet_form())) { delete job; return rc; }
     return submit_with_results(job, status, octets_out, nullptr, oct_off_out, job_out);
+}
+// keyed proof_gen (stages_pg.hpp PgScalarsIn; op_pg.hpp): item i under key key_index[i] of the context's key set, or of the call's (wk)
+static int core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
+                                       const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
+                                       const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                       uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status, bbs_job** job_out, const WithKeys* wk = nullptr) {
+    if (!ctx || !status || !job_out) return BBS_E_ARG;
+    bbs_job* job = nullptr;
+    int rc = upload<true>(ctx, n, with_keys(PgIn{.signatures = sigs, .messages = m, .msg_off = mo, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd,
+                                                 .rnd_off = rno, .headers = h, .hdr_off = ho, .ph = ph, .ph_off = pho, .key_index = key_index}, wk), &job);
+    if (rc) return rc;
+    return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
 }
 
 // the reference's PUBLIC sign (src/sign.rs:63-132) in one call: raw messages in, signatures as octet strings out
@@ -1018,17 +1030,11 @@ int bbs_core_proof_gen_submit(bbs_ctx* ctx, size_t n, const uint8_t* sigs, const
     if (rc) return rc;
     return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
 }
-// keyed proof_gen (stages_pg.hpp PgScalarsIn; op_pg.hpp): item i under key key_index[i] of the context's key set
 int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                                     const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
                                     const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
                                     uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status, bbs_job** job_out) {
-    if (!ctx || !status || !job_out) return BBS_E_ARG;
-    bbs_job* job = nullptr;
-    int rc = upload<true>(ctx, n, PgIn{.signatures = sigs, .messages = m, .msg_off = mo, .disclosed_idx = di, .didx_off = dio, .random_scalars = rnd,
-                                       .rnd_off = rno, .headers = h, .hdr_off = ho, .ph = ph, .ph_off = pho, .key_index = key_index}, &job);
-    if (rc) return rc;
-    return submit_with_results(job, status, pf_out, cm_out, cmo_out, job_out);
+    return core_proof_gen_keyed_submit(ctx, n, key_index, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho, pf_out, cm_out, cmo_out, status, job_out);
 }
 int bbs_core_proof_gen_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* sigs, const uint8_t* m, const uint64_t* mo,
                                    const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
@@ -1092,6 +1098,38 @@ int bbs_proof_gen_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_i
     bbs_job* job = nullptr;
     return wait_and_free(bbs_proof_gen_wire_keyed_submit(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho,
                                                          octets_out, oct_off_out, status, &job), job);
+}
+// proof_gen under a key set of the call (job_form.hpp JobKeys, stages_key.hpp KeyDomainBuild): the keyed functions with `wk`
+int bbs_core_proof_gen_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sigs,
+                                        const uint8_t* m, const uint64_t* mo, const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
+                                        const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                        uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return core_proof_gen_keyed_submit(ctx, n, key_index, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho, pf_out, cm_out, cmo_out, status, job_out, &wk);
+}
+int bbs_core_proof_gen_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sigs,
+                                       const uint8_t* m, const uint64_t* mo, const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
+                                       const uint8_t* h, const uint64_t* ho, const uint8_t* ph, const uint64_t* pho,
+                                       uint8_t* pf_out, uint8_t* cm_out, uint64_t* cmo_out, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_core_proof_gen_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, sigs, m, mo, di, dio, rnd, rno, h, ho, ph, pho,
+                                                             pf_out, cm_out, cmo_out, status, &job), job);
+}
+int bbs_proof_gen_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sig_octets,
+                                        const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di,
+                                        const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho,
+                                        const uint8_t* ph, const uint64_t* pho, uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out) {
+    const WithKeys wk{n_keys, pk_octets};
+    return proof_gen_wire_submit<true>(ctx, n, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio, rnd, rno, h, ho, ph, pho,
+                                       octets_out, oct_off_out, status, job_out, &wk);
+}
+int bbs_proof_gen_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets, const uint32_t* key_index, const uint8_t* sig_octets,
+                                       const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off, const uint64_t* di,
+                                       const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno, const uint8_t* h, const uint64_t* ho,
+                                       const uint8_t* ph, const uint64_t* pho, uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status) {
+    bbs_job* job = nullptr;
+    return wait_and_free(bbs_proof_gen_wire_with_keys_submit(ctx, n, n_keys, pk_octets, key_index, sig_octets, msg_bytes, msg_byte_off, msg_item_off, di, dio,
+                                                             rnd, rno, h, ho, ph, pho, octets_out, oct_off_out, status, &job), job);
 }
 int bbs_proof_gen_wire_batch(bbs_ctx* ctx, size_t n, const uint8_t* sig_octets, const uint8_t* msg_bytes, const uint64_t* msg_byte_off,
                              const uint64_t* msg_item_off, const uint64_t* di, const uint64_t* dio, const uint8_t* rnd, const uint64_t* rno,
@@ -1392,6 +1430,10 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
 int bbs_selftest_key_len_rows(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, int path, uint8_t* rows_out, int8_t* status_out) {
     if (!ctx || (path != 0 && path != 1) || (n && (!pk_octets || !rows_out || !status_out))) return BBS_E_ARG;
     return with_curve(ctx, [&](auto* c) { return selftest_key_len_rows(c, n, pk_octets, path, rows_out, status_out); });
+}
+int bbs_selftest_key_domain_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, uint8_t* entries_out, int8_t* status_out) {
+    if (!ctx || (n && (!pk_octets || !entries_out || !status_out))) return BBS_E_ARG;
+    return with_curve(ctx, [&](auto* c) { return selftest_key_domain_entries(c, n, pk_octets, entries_out, status_out); });
 }
 size_t bbs_selftest_hash_ctx_bytes(void) { return sizeof(HashCtx); }
 size_t bbs_selftest_key_entry_bytes(int curve) {

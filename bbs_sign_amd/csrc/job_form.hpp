@@ -5,14 +5,6 @@
 #pragma once
 #include "runtime.hpp"
 
-// what a job keeps of its form
-template <class C>
-struct JobForm {
-    Form form = Form::Single;
-    DomainSrc<C> src{};                      // what the scalar stage reads (kidx: KEY_NONE = unknown / refused, decided by KeyGate)
-    uint32_t* len = nullptr;                 // src.len as the MIXED ingest bodies write it
-    bool mixed() const { return form_mixed(form); }
-};
 // keyed batch verification (bbs_ctx_set_keyed_batch_verification; pippenger.hpp): the plan keyed_bv_plan makes of a job whose
 // context has the switch on, and the arguments of the five stages add_keyed_bv_stages builds on it.  G == 0: no group formed.
 template <class C>
@@ -40,8 +32,12 @@ struct KeyedBv {
 template <class C>
 struct JobKeys {
     bool on = false;
+    // proof_gen (bbs_*proof_gen*_with_keys_*): the job reads the `hash` of an entry and nothing else.  Uncached, its keys are
+    // prepared by KeyDomainBuild (no line table, no workspace); its gate refuses no key for the form of its table.  The MISSES
+    // of a cached job are prepared by the full KeyBuild all the same: a slot of the cache is whole, whoever published it.
+    bool domain_only = false;
     size_t n_keys = 0;
-    const uint8_t* pk_octets = nullptr;      // the caller's array (read by keyed_order only)
+    const uint8_t* pk_octets = nullptr;      // the caller's array (read while the staging words are planned)
     size_t oct_at = 0;                       // place of the strings in the staging words, in words
     const uint32_t* d_oct = nullptr;         // the strings on the device
     KeyEntry<C>* entries = nullptr;          // [n_keys]
@@ -78,13 +74,21 @@ struct KeyCachePin {
         gen->book.release(plan);
     }
 };
+// what a job keeps of its form
+template <class C>
+struct JobForm {
+    Form form = Form::Single;
+    DomainSrc<C> src{};                      // what the scalar stage reads (kidx: KEY_NONE = unknown / refused, decided by KeyGate)
+    uint32_t* len = nullptr;                 // src.len as the MIXED ingest bodies write it
+    JobKeys<C> jk{};                         // the job's own keys (bbs_*_with_keys_*); off: the context's key set
+    bool mixed() const { return form_mixed(form); }
+};
 // verify / proof_verify: plus the keyed pairing order
 template <class C>
 struct PairedJobForm : JobForm<C> {
     PairKeyedArgs<C> pair{};                 // the pairing step (points, gate, output: copied from the job's PairArgs at launch)
     bool unit = false;                       // line form of the key set the job holds (KeySet::unit)
     KeyedBv<C> bv{};                         // keyed batch verification, where the context's switch was on at upload
-    JobKeys<C> jk{};                         // the job's own keys (bbs_*_with_keys_*); off: the context's key set
 };
 // op_key.hpp (instantiated in tu_key_*.hip).  prepare: allocates status (and rows, stride = L + 1; 0: none) through `alloc`
 // (device bytes owned by the job, null = no memory), clears the entries and launches KeyBuild (and KeyLenBuild) on st.
@@ -212,6 +216,32 @@ void keyed_bv_plan(size_t n, const std::vector<uint32_t>& cnt, size_t min_items,
     bv.at = words.size();
     words.insert(words.end(), pw.begin(), pw.end());
 }
+// A job-local key set in the staging words, shared by the paired jobs (keyed_order) and proof_gen (keyed_indexes).
+// to_slots: a cached job planned in its own key numbering; `count` words that hold a key id become slots of the cache.
+// strings: behind the plan, the strings of the keys the job prepares -- all of them, or a cached job's misses and then their slots.
+template <class C>
+void job_keys_to_slots(const JobKeys<C>& jk, uint32_t* w, size_t count) {
+    const KeyCachePlan& p = *jk.plan;
+    for (size_t i = 0; i < count; i++) if (w[i] != KEY_NONE) w[i] = p.slot_of[w[i]];
+}
+template <class C>
+void job_keys_strings(JobKeys<C>& jk, std::vector<uint32_t>& words) {
+    constexpr size_t KW = 2 * C::FpP::NC, KB = 2 * Ctx<C>::FPB;
+    jk.oct_at = words.size();
+    if (!jk.cache) {
+        words.resize(jk.oct_at + jk.n_keys * KW);
+        if (jk.n_keys) std::memcpy(words.data() + jk.oct_at, jk.pk_octets, jk.n_keys * KB);
+        return;
+    }
+    const KeyCachePlan& p = *jk.plan;
+    const size_t m = p.miss_key.size();
+    jk.slot_at = jk.oct_at + m * KW;
+    words.resize(jk.slot_at + m);
+    for (size_t t = 0; t < m; t++) {
+        std::memcpy(words.data() + jk.oct_at + t * KW, jk.pk_octets + (size_t)p.miss_key[t] * KB, KB);
+        words[jk.slot_at + t] = p.miss_slot[t];
+    }
+}
 // A job-local key set (jf.jk.on): the set is the job's own, every index < n_keys counts as accepted here (JobKeyGate decides on
 // the device), and the key strings follow the plan in `words`.
 template <class C, class J>
@@ -240,40 +270,35 @@ void keyed_order(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, PairedJ
     if (jf.bv.G)                               // (the groups in key order, as keyed_bv_plan numbers them)
         for (size_t k = 0; k < nk; k++)
             if (cnt[k] && cnt[k] >= ctx->keyed_bv_min) { jk.grp_key.push_back((uint32_t)k); jk.grp_items.push_back(cnt[k]); }
-    jk.oct_at = words.size();
-    if (!jk.cache) {
-        words.resize(jk.oct_at + jk.n_keys * (2 * C::FpP::NC));
-        if (jk.n_keys) std::memcpy(words.data() + jk.oct_at, jk.pk_octets, jk.n_keys * 2 * Ctx<C>::FPB);
-        return;
+    if (jk.cache) {
+        // a cached job: everything above was planned in the job's numbering; now key -> slot wherever the words hold a key id
+        job_keys_to_slots<C>(jk, words.data(), n);                                                      // kidx
+        job_keys_to_slots<C>(jk, words.data() + n + ns, nu / KEY_SLOTS_PER_WAVE);                       // the wave keys
+        if (jf.bv.G) {
+            uint32_t* b = words.data() + jf.bv.at;
+            job_keys_to_slots<C>(jk, b + jf.bv.o_vkidx, (size_t)16 * jf.bv.G);                          // the virtual items' kidx
+            job_keys_to_slots<C>(jk, b + jf.bv.o_vslots + jf.bv.v_slots, jf.bv.v_uni / KEY_SLOTS_PER_WAVE);     // and their wave keys
+        }
     }
-    // a cached job: everything above was planned in the job's numbering; now key -> slot wherever the words hold a key id,
-    // and behind the plan only the strings of the misses, then their slots
-    const KeyCachePlan& p = *jk.plan;
-    auto to_slots = [&p](uint32_t* w, size_t count) {
-        for (size_t i = 0; i < count; i++) if (w[i] != KEY_NONE) w[i] = p.slot_of[w[i]];
-    };
-    to_slots(words.data(), n);                                                       // kidx
-    to_slots(words.data() + n + ns, nu / KEY_SLOTS_PER_WAVE);                        // the wave keys
-    if (jf.bv.G) {
-        uint32_t* b = words.data() + jf.bv.at;
-        to_slots(b + jf.bv.o_vkidx, (size_t)16 * jf.bv.G);                           // the virtual items' kidx
-        to_slots(b + jf.bv.o_vslots + jf.bv.v_slots, jf.bv.v_uni / KEY_SLOTS_PER_WAVE);      // and their wave keys
-    }
-    constexpr size_t KW = 2 * C::FpP::NC;
-    const size_t m = p.miss_key.size();
-    jk.slot_at = jk.oct_at + m * KW;
-    words.resize(jk.slot_at + m);
-    for (size_t t = 0; t < m; t++) {
-        std::memcpy(words.data() + jk.oct_at + t * KW, jk.pk_octets + (size_t)p.miss_key[t] * 2 * Ctx<C>::FPB, 2 * Ctx<C>::FPB);
-        words[jk.slot_at + t] = p.miss_slot[t];
-    }
+    job_keys_strings<C>(jk, words);
 }
 // the device half of a job-local key set, behind the staging image: d = the words' place on the device
 template <class C>
 void job_keys_bind(JobKeys<C>& jk, const uint32_t* d) { jk.d_oct = d + jk.oct_at; jk.d_slot_of = d + jk.slot_at; }
 // the same look at the key set for a job without a pairing step (keyed proof_gen): `words` = [kidx n] and nothing else
+// A job-local key set (jf.jk.on) as in keyed_order: every index < n_keys is passed on (the gate decides on the device), a cached
+// job's indexes become slots, and the key strings follow.
 template <class C, class J>
 void keyed_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, JobForm<C>& jf, std::vector<uint32_t>& words) {
+    if (JobKeys<C>& jk = jf.jk; jk.on) {
+        j->key_set = nullptr;
+        words.resize(n);
+        for (size_t i = 0; i < n; i++) words[i] = key_index[i] < jk.n_keys ? key_index[i] : KEY_NONE;
+        if (jk.cache) job_keys_to_slots<C>(jk, words.data(), n);
+        job_keys_strings<C>(jk, words);
+        jf.src.keys = jk.use_entries();
+        return;
+    }
     const auto ks = ctx->keys;
     j->key_set = ks;
     const size_t nk = ks ? ks->n : 0;         // (no set: only where bbs_ctx_set_keyed_mixed_lengths is on -- every index is unknown)
@@ -309,7 +334,7 @@ int keyed_sign_indexes(J* j, Ctx<C>* ctx, size_t n, const uint32_t* key_index, J
 // job's form, the plan of its keys -- hits pinned, slots claimed for the misses, or the job bypassed -- and the events of hit
 // slots another job is still publishing.  The job's own arrays then hold its misses only.
 template <class C, class J>
-int job_keys_cache_plan(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
+int job_keys_cache_plan(J* j, Ctx<C>* ctx, JobForm<C>& jf) {
     JobKeys<C>& jk = jf.jk;
     {
         std::lock_guard<std::mutex> g(ctx->mu);
@@ -340,10 +365,11 @@ int job_keys_cache_plan(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
     return BBS_OK;
 }
 template <class C, class J>
-int job_keys_begin(J* j, Ctx<C>* ctx, bool on, size_t n_keys, const uint8_t* pk_octets, PairedJobForm<C>& jf) {
+int job_keys_begin(J* j, Ctx<C>* ctx, bool on, size_t n_keys, const uint8_t* pk_octets, JobForm<C>& jf, bool domain_only = false) {
     JobKeys<C>& jk = jf.jk;
     jk.on = on;
     if (!on) return BBS_OK;
+    jk.domain_only = domain_only;
     if ((n_keys && !pk_octets) || n_keys > 0xFFFFFFF0ull) return BBS_E_ARG;
     jk.n_keys = n_keys; jk.pk_octets = pk_octets;
     j->has_job_keys = true;
@@ -352,16 +378,18 @@ int job_keys_begin(J* j, Ctx<C>* ctx, bool on, size_t n_keys, const uint8_t* pk_
     jk.entries = j->template scratch<KeyEntry<C>>(std::max<size_t>(jk.n_build(), 1), rc);
     return rc;
 }
-// second half, behind form_bind and in front of the ingest kernel: KeyBuild (and KeyLenBuild) on the job's main stream, the
-// job's own prefixes per (key, length) bound, bbs_job_key_statuses answered from the device array on request
+// second half, behind form_bind and in front of the ingest kernel: the key stage (and KeyLenBuild) on the job's main stream, the
+// job's own prefixes per (key, length) bound, bbs_job_key_statuses answered from the device array on request.  unit: the line
+// form of the tables the job reads (a paired job's jf.unit) or, where it reads none (proof_gen), the context's -- the form a
+// cached job's misses are published in.
 template <class C, class J>
-int job_keys_launch(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
+int job_keys_launch(J* j, Ctx<C>* ctx, JobForm<C>& jf, bool unit) {
     JobKeys<C>* jk = &jf.jk;
     if (!jk->on) return BBS_OK;
     const uint32_t stride = jf.form == Form::KeyedMixed ? (uint32_t)ctx->L + 1 : 0;
-    if (jk->cache && (jk->cache->unit != jf.unit || jk->cache->stride != stride)) return BBS_E_STATE;      // (a form switched between the two looks: fail closed)
+    if (jk->cache && (jk->cache->unit != unit || jk->cache->stride != stride)) return BBS_E_STATE;      // (a form switched between the two looks: fail closed)
     auto alloc = [j](size_t b) -> void* { int rc = BBS_OK; return j->template scratch<uint8_t>(std::max<size_t>(b, 1), rc); };
-    if (const int rc = job_keys_prepare<C>(ctx, j->stream(), *jk, jf.unit, stride, alloc, j->key_blob)) return rc;
+    if (const int rc = job_keys_prepare<C>(ctx, j->stream(), *jk, unit, stride, alloc, j->key_blob)) return rc;
     if (stride) jf.src.pref = jk->use_rows();
     j->key_statuses = [j, jk](std::vector<int8_t>& v) {
         v.assign(jk->n_keys, 0);
@@ -380,7 +408,10 @@ int job_keys_launch(J* j, Ctx<C>* ctx, PairedJobForm<C>& jf) {
 }
 // the device half: d = the words' place in the device copy of the staging image
 template <class C>
-void keyed_bind(JobForm<C>& jf, const uint32_t* d) { jf.src.kidx = d; }
+void keyed_bind(JobForm<C>& jf, const uint32_t* d) {
+    jf.src.kidx = d;
+    if (jf.jk.on) job_keys_bind<C>(jf.jk, d);
+}
 template <class C>
 void keyed_bind(PairedJobForm<C>& jf, size_t n, const uint32_t* d) {
     jf.src.kidx = d;
@@ -402,16 +433,19 @@ template <class J>
 int keyed_gate(J* j, size_t n, const uint32_t* kidx, int8_t* status0) {
     return rt::launch<KeyGate>(j->stream(), KeyGateArgs{n, kidx, status0}, n) ? BBS_E_HIP : BBS_OK;
 }
-// the same place in a verify / proof_verify job: the context's key set, or the job's own (JobKeyGate: the device decides)
+// the same place in a job that may bring its own keys: the context's key set, or the job's own (JobKeyGate, proof_gen:
+// JobKeyStatusGate -- the device decides); unit: the line form of the job (not looked at by proof_gen's gate)
 template <class C, class J>
-int paired_keyed_gate(J* j, size_t n, const PairedJobForm<C>& jf, int8_t* status0) {
+int job_keyed_gate(J* j, size_t n, const JobForm<C>& jf, bool unit, int8_t* status0) {
     if (!jf.jk.on) return keyed_gate(j, n, jf.src.kidx, status0);
     // a cached job that hit a slot another job is still publishing: its main stream waits on the device, here, in front of the
     // first kernel that reads an entry (the host never waits)
     for (const auto& e : jf.jk.wait_events)
         if (rt::stream_wait(j->stream(), e->ev)) return BBS_E_HIP;
-    return job_keys_gate<C>(j->stream(), jf.jk, jf.unit, n, jf.src.kidx, status0);
+    return job_keys_gate<C>(j->stream(), jf.jk, unit, n, jf.src.kidx, status0);
 }
+template <class C, class J>
+int paired_keyed_gate(J* j, size_t n, const PairedJobForm<C>& jf, int8_t* status0) { return job_keyed_gate<C>(j, n, jf, jf.unit, status0); }
 #if !defined(BBS_HOST_TWIN)
 // the keyed fused kernel over the slots of the pairing order (runtime.hpp launch_line_form)
 template <class C>

@@ -313,6 +313,38 @@ int selftest_key_entries(Ctx<C>* ctx, size_t n, const uint8_t* rec, const int8_t
 // octet form over the strings in the job's staging image, and -- stride != 0: a job of mixed counts -- KeyLenBuild into the job's
 // own rows.  Nothing is copied back; nothing waits.  Every buffer comes from the job (alloc) and lives as long as it does.
 template <class C> int job_keys_publish(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, uint32_t stride);
+// KeyLenBuild over the nk keys the job prepares, into jk.rows
+template <class C>
+int job_key_rows_launch(rt::Stream& st, const JobKeys<C>& jk, const typename Ctx<C>::KeyBlob& kb, size_t nk, uint32_t stride) {
+    KeyLenBuildArgs<C> la{};
+    la.n_keys = nk; la.stride = stride; la.oct = jk.d_oct; la.key_status = jk.status;
+    la.cg = kb.cg(); la.api_id = kb.api(); la.api_len = (uint32_t)kb.api_len;
+    la.hash0 = kb.hash0(); la.out = jk.rows;
+    return rt::launch<KeyLenBuild<C>>(st, la, nk * stride) ? BBS_E_HIP : BBS_OK;
+}
+// What a launch of KeyDomainBuild takes that depends on the curve alone, and the launch over n strings
+template <class C>
+int key_domain_launch(rt::Stream& st, size_t n, const uint32_t* d_oct, KeyEntry<C>* entries, int8_t* status, const typename Ctx<C>::KeyBlob& kb) {
+    KeyDomainBuildArgs<C> a{};
+    a.b2 = g2_b<C>();
+    const G2Aff<C> gen = g2_generator<C>();
+    a.gen_x = gen.x; a.gen_y = gen.y;
+    a.n = n; a.oct = d_oct; a.out = entries; a.status = status;
+    a.hash0 = kb.hash0(); a.suffix = kb.suffix(); a.suffix_len = (uint32_t)kb.suffix_len();
+    if (rt::dmemset(entries, 0, n * sizeof(KeyEntry<C>), st)) return BBS_E_HIP;
+    return rt::launch<KeyDomainBuild<C>>(st, a, n) ? BBS_E_HIP : BBS_OK;
+}
+// The keys of a proof_gen job that is not cached (JobKeys::domain_only): KeyDomainBuild in place of KeyBuild, the rest as below.
+template <class C>
+int job_keys_prepare_domain(rt::Stream& st, JobKeys<C>& jk, const typename Ctx<C>::KeyBlob& kb, uint32_t stride, const std::function<void*(size_t)>& alloc) {
+    const size_t nk = jk.n_keys;
+    jk.status = static_cast<int8_t*>(alloc(nk));
+    if (stride) jk.rows = static_cast<HashCtx*>(alloc(nk * stride * sizeof(HashCtx)));
+    if (!jk.status || (stride && !jk.rows)) return BBS_E_NOMEM;
+    if (!nk) return BBS_OK;
+    if (const int rc = key_domain_launch<C>(st, nk, jk.d_oct, jk.entries, jk.status, kb)) return rc;
+    return stride ? job_key_rows_launch<C>(st, jk, kb, nk, stride) : (int)BBS_OK;
+}
 template <class C>
 int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uint32_t stride, const std::function<void*(size_t)>& alloc,
                      std::shared_ptr<const void>& blob_held) {
@@ -322,6 +354,8 @@ int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uin
     if (jk.cache) kb = jk.cache->blob;
     else if (const int rc = ctx->sync_key_blob(kb)) return rc;
     blob_held = kb;
+    // (proof_gen, uncached: the domain-only stage -- no workspace, no line form; a cached job's misses fill whole slots below)
+    if (jk.domain_only && !jk.cache) return job_keys_prepare_domain<C>(st, jk, *kb, stride, alloc);
     KeyBuildArgs<C> a{};
     size_t n_steps = 0;
     if (const int rc = key_build_consts<C>(a, unit, n_steps)) return rc;
@@ -340,13 +374,8 @@ int job_keys_prepare(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, bool unit, uin
     a.suffix = kb->suffix();
     a.suffix_len = (uint32_t)kb->suffix_len();
     if (rt::launch<KeyBuild<C>>(st, a, nk)) return BBS_E_HIP;
-    if (stride) {
-        KeyLenBuildArgs<C> la{};
-        la.n_keys = nk; la.stride = stride; la.oct = jk.d_oct; la.key_status = jk.status;
-        la.cg = kb->cg(); la.api_id = kb->api(); la.api_len = (uint32_t)kb->api_len;
-        la.hash0 = kb->hash0(); la.out = jk.rows;
-        if (rt::launch<KeyLenBuild<C>>(st, la, nk * stride)) return BBS_E_HIP;
-    }
+    if (stride)
+        if (const int rc = job_key_rows_launch<C>(st, jk, *kb, nk, stride)) return rc;
     return jk.cache ? job_keys_publish<C>(ctx, st, jk, stride) : (int)BBS_OK;
 }
 // A cached job's misses into their slots (KeyCachePublish), ONE event behind the kernel, and only then -- under the context's
@@ -374,8 +403,29 @@ int job_keys_publish(Ctx<C>* ctx, rt::Stream& st, JobKeys<C>& jk, uint32_t strid
 }
 template <class C>
 int job_keys_gate(rt::Stream& st, const JobKeys<C>& jk, bool unit, size_t n, const uint32_t* kidx, int8_t* status0) {
+    if (jk.domain_only) return rt::launch<JobKeyStatusGate>(st, JobKeyStatusGateArgs{n, kidx, jk.use_status(), status0}, n) ? BBS_E_HIP : BBS_OK;
     JobKeyGateArgs<C> g{n, kidx, jk.use_entries(), jk.use_status(), unit ? 1 : 0, status0};
     return rt::launch<JobKeyGate<C>>(st, g, n) ? BBS_E_HIP : BBS_OK;
+}
+
+// bbs_selftest_key_domain_entries: the entries and statuses of n strings by the KeyDomainBuild stage, read back from the device;
+// the context's key set is not touched
+template <class C>
+int selftest_key_domain_entries(Ctx<C>* ctx, size_t n, const uint8_t* oct, uint8_t* entries_out, int8_t* status_out) {
+    constexpr size_t FPB = Ctx<C>::FPB;
+    if (!ctx->gens_set) return BBS_E_STATE;
+    if (ctx->use()) return BBS_E_HIP;
+    if (!n) return BBS_OK;
+    std::shared_ptr<const typename Ctx<C>::KeyBlob> kb;
+    if (const int rc = ctx->sync_key_blob(kb)) return rc;
+    DevBuf d_oct, d_entries, d_st;
+    if (d_oct.alloc(n * 2 * FPB) || d_entries.alloc(n * sizeof(KeyEntry<C>)) || d_st.alloc(n)) return BBS_E_NOMEM;
+    int rc = rt::h2d(d_oct.p, oct, n * 2 * FPB, ctx->stream) ? BBS_E_HIP : BBS_OK;
+    if (!rc) rc = key_domain_launch<C>(ctx->stream, n, d_oct.as<uint32_t>(), d_entries.as<KeyEntry<C>>(), d_st.as<int8_t>(), *kb);
+    if (!rc && (rt::sync(ctx->stream) || rt::d2h(entries_out, d_entries.p, n * sizeof(KeyEntry<C>), ctx->stream) ||
+                rt::d2h(status_out, d_st.p, n, ctx->stream))) rc = BBS_E_HIP;
+    (void)rt::sync(ctx->stream);                  // (the buffers go back with the locals, behind the synchronisation)
+    return rc;
 }
 
 // bbs_selftest_job_key_cache_entries: what the current generation of the cache holds for n strings -- entry, status and (where

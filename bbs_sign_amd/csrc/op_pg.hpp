@@ -92,14 +92,17 @@ constexpr const char* PG_SCALARS[4] = {"pg_scalars", "pg_scalars_mixed", "pg_sca
 // KEYED (bbs_*proof_gen*_keyed_*, instantiated in tu_pgk_*.hip): item i is derived under key key_index[i] of the context's key
 // set (keyed.hpp).  The key enters through the domain alone (proof_gen.rs:78-113 -> calculate_domain): the scalar stage reads
 // the key's midstate, or the prefix of (key, length), and every other stage is the single-key job's.  The context's single
-// public key is neither needed nor looked at.
+// public key is neither needed nor looked at.  With a key set of the call (in.job_keys, bbs_*proof_gen*_with_keys_*) the keys are
+// the job's own: prepared on its main stream in front of the ingest kernel (job_form.hpp JobKeys, stages_key.hpp KeyDomainBuild),
+// gated on the device where KeyGate stands for the registered set -- behind PgIngest and PgDrawGate, so that an unknown key wins
+// whatever the other checks decided.
 template <class C, bool KEYED>
 int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     constexpr int N = C::FpP::N;
     constexpr int NC = C::FpP::NC;
     constexpr int FPB = 4 * NC;
     Form form;
-    if (const int rcf = decide_form<KEYED>(ctx, FormOp::ProofGen, n, in.key_index, form)) return rcf;
+    if (const int rcf = decide_form<KEYED>(ctx, FormOp::ProofGen, n, in.key_index, form, KEYED && in.job_keys)) return rcf;
     const bool wire = in.signature_octets != nullptr, raw = in.msg_byte_off != nullptr;
     // SEEDED (bbs_ctx_set_seeded_random_scalars): random_scalars / rnd_off are seeds -- bytes per item, or with rnd_off == nullptr
     // one 32-byte job seed -- and the scalars are drawn on the device in front of the ingest stage (stages_draw.hpp PgDraw)
@@ -158,7 +161,11 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     }
     std::vector<uint32_t> kwords;     // keyed: the key indexes, in the staging image
     size_t kwords_at = 0;
-    if constexpr (KEYED) keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    if constexpr (KEYED) {
+        // (a key set of the call: proof_gen reads the domain midstate of a key alone -- JobKeys::domain_only)
+        if (const int rck = job_keys_begin<C>(job.get(), ctx, in.job_keys, in.n_keys, in.pk_octets, job->jf, true)) return rck;
+        keyed_indexes<C>(job.get(), ctx, n, in.key_index, job->jf, kwords);
+    }
     if (int rc0 = seeded ? stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb, &sd}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)
                          : stage_image(job.get(), n, sigs, rec, {&ms, &di, &rs, &hb, &pb}, raw ? &mb : nullptr, nm, KEYED ? &kwords : nullptr, &kwords_at)) return rc0;
     const uint8_t* dimg = job->d_raw.template as<uint8_t>();
@@ -254,10 +261,13 @@ int pg_upload(Ctx<C>* ctx, size_t n, const PgIn& in, bbs_job** out) {
     a.status = job->d_status.template as<int8_t>();
     ia.status0 = job->d_status0.template as<int8_t>();
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
+    if constexpr (KEYED) {
+        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf, ctx->lines_unit()))) return rc;
+    }
     if ((rc = launch_ingest<PgIngest<C>, PgIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if (seeded && rt::launch<PgDrawGate>(job->stream(), PgDrawGateArgs{n, job->draw.dcode, ia.status0}, n)) return BBS_E_HIP;
     if constexpr (KEYED) {
-        if ((rc = keyed_gate(job.get(), n, job->jf.src.kidx, ia.status0))) return rc;
+        if ((rc = job_keyed_gate<C>(job.get(), n, job->jf, false, ia.status0))) return rc;
     }
     PgJob<C>* j = job.get();
     add_scalar_stage<C, KEYED, PgScalars<C>, PgScalarsIn>(j, PG_SCALARS);

@@ -113,7 +113,7 @@ int pv_upload(Ctx<C>* ctx, size_t n, const PvIn& in, bbs_job** out) {
     job->zero_on_reset.push_back({pair_ok, nn});          // a pairing lane that never ran reads as "product != 1"
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
     if constexpr (KEYED) {
-        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf))) return rc;
+        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf, job->jf.unit))) return rc;
     }
     if (!wire) {
         PvIngestArgs<C>& ia = job->ingest;

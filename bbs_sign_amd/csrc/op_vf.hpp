@@ -96,7 +96,7 @@ int vf_upload(Ctx<C>* ctx, size_t n, const VfIn& in, bbs_job** out) {
     ia.status0 = job->d_status0.template as<int8_t>();
     if ((rc = form_bind<C>(job.get(), ctx, nn, job->jf))) return rc;
     if constexpr (KEYED) {
-        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf))) return rc;
+        if ((rc = job_keys_launch<C>(job.get(), ctx, job->jf, job->jf.unit))) return rc;
     }
     if ((rc = launch_ingest<VfIngest<C>, VfIngestMixed<C>>(job.get(), job->jf, ia, n))) return rc;
     if constexpr (KEYED) {

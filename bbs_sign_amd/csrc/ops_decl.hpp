@@ -74,6 +74,9 @@ struct PgIn {
     const uint8_t* msg_bytes = nullptr;
     const uint64_t* msg_byte_off = nullptr;
     const uint32_t* key_index = nullptr;        // KEYED only: item i is derived under key key_index[i] of the context's key set
+    bool job_keys = false;                      // KEYED only, as PvIn (bbs_*proof_gen*_with_keys_*)
+    size_t n_keys = 0;
+    const uint8_t* pk_octets = nullptr;
 };
 // declarations of the per-operation templates (defined in op_*.hpp, instantiated in tu_*.hip)
 template <class C, bool KEYED = false> int pv_upload(Ctx<C>*, size_t, const PvIn&, bbs_job**);
@@ -158,3 +161,6 @@ extern template int selftest_key_len_rows<BnCurve>(Ctx<BnCurve>*, size_t, const 
 template <class C> int selftest_job_key_cache_entries(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
 extern template int selftest_job_key_cache_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
 extern template int selftest_job_key_cache_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
+template <class C> int selftest_key_domain_entries(Ctx<C>*, size_t, const uint8_t*, uint8_t*, int8_t*);
+extern template int selftest_key_domain_entries<BlsCurve>(Ctx<BlsCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*);
+extern template int selftest_key_domain_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*);

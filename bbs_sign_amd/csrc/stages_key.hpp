@@ -23,6 +23,7 @@
 // on the bits of r and of the Miller loop count, the same for every lane.
 // The per-step values live in a workspace in global memory laid out [word][key] (a wavefront's accesses coalesce), never in
 // the kernel's frame; op_key.hpp key_build sizes it per call by the steps of the walk.
+// KeyDomainBuild, behind KeyBuild, is the same stage without the line table, for the jobs that read a key's midstate alone.
 #pragma once
 #include "keyed.hpp"
 
@@ -371,6 +372,104 @@ struct KeyBuild {
     }
 };
 
+// ---- the domain-only key stage (bbs_*proof_gen*_with_keys_*; job_form.hpp JobKeys::domain_only) ------------------------------
+// proof_gen meets the key in calculate_domain alone: of a KeyEntry it reads `hash`.  This stage prepares a key for such a job:
+// steps 1, 2, 3 and 5 of KeyBuild::run in its octet form -- decode, on-twist test, [r]Q = identity, domain midstate -- and
+// nothing of step 4: no line walk, no workspace, no Miller loop count, no line form, no f2_inv.  `hash` and the status are, bit
+// for bit, what KeyBuild writes for the same string (the two bodies are kept side by side; KeyBuild's is left as it was so that
+// its code does not move); `tab` is that of a key without a table -- n_lines = 0, q_is_identity = 1, unit = 0, entries zero
+// as the caller cleared them -- so PgScalars reads the entry unchanged and no pairing kernel must ever be given it.
+// Convergence as KeyBuild's: a refused or identity key walks the generator, its result is dropped by a select; the branches
+// that remain are on the bits of r.
+template <class C>
+struct KeyDomainBuildArgs {
+    size_t n;
+    const uint32_t* oct;         // [n][2 NC] words holding the n compressed strings
+    KeyEntry<C>* out;            // [n] entries, ZEROED by the caller
+    int8_t* status;              // [n] 1 accepted / BBS_ST_NOT_ON_CURVE / BBS_ST_NONCANONICAL
+    const uint8_t* suffix;       // as KeyBuildArgs
+    uint32_t suffix_len;
+    const HashCtx* hash0;
+    Fp2<C> b2, gen_x, gen_y;     // twist constant, the generator (stand-in point)
+};
+template <class C>
+struct KeyDomainBuild {
+    static __host__ __device__ __forceinline__ void run(const KeyDomainBuildArgs<C>& a, size_t t) {
+        using P = typename C::FpP;
+        constexpr int NC = P::NC;
+        // ---- 1. decode (KeyBuild's octet form)
+        uint32_t w0[NC], w1[NC];                                       // x.c0, x.c1 as canonical little-endian words
+        const uint32_t* oc = a.oct + t * 2 * NC;
+        bool inf, ybig, noncanon = false;
+        if constexpr (C::ID == 0) {                                    // big-endian x.c1 || x.c0, flags in the first byte
+            for (int i = 0; i < NC; i++) { w1[i] = kb_bswap(oc[NC - 1 - i]); w0[i] = kb_bswap(oc[2 * NC - 1 - i]); }
+            const uint32_t fl = w1[NC - 1] >> 24;
+            noncanon |= !(fl & 0x80);
+            inf = (fl & 0x40) != 0; ybig = (fl & 0x20) != 0;
+            w1[NC - 1] &= 0x1FFFFFFFu;
+        } else {                                                       // little-endian x.c0 || x.c1, flags in the last byte
+            for (int i = 0; i < NC; i++) { w0[i] = oc[i]; w1[i] = oc[NC + i]; }
+            const uint32_t fl = w1[NC - 1] >> 24;
+            inf = (fl & 0x40) != 0; ybig = (fl & 0x80) != 0;
+            w1[NC - 1] &= 0x3FFFFFFFu;
+        }
+        uint32_t any = 0;
+        for (int i = 0; i < NC; i++) any |= w0[i] | w1[i];
+        noncanon |= inf ? ((any != 0) | ybig) : (!limbs_lt_mod<P>(w0) | !limbs_lt_mod<P>(w1));
+        if (inf | noncanon) for (int i = 0; i < NC; i++) { w0[i] = 0; w1[i] = 0; }
+        const Fp2<C> qx = {fe_from_words<P>(w0), fe_from_words<P>(w1)};
+        const Fp2<C> rhs = f2_add<C>(f2_mul<C>(f2_sqr<C>(qx), qx), a.b2);
+        Fp2<C> y;
+        const bool root = kb_f2_sqrt<C>(rhs, y);
+        const bool big = fe_is_zero<P>(y.c1) ? kb_fe_gt_half<P>(y.c0) : kb_fe_gt_half<P>(y.c1);
+        const Fp2<C> qy = f2_select<C>(big != ybig, f2_neg<C>(y), y);
+        bool refused = noncanon | (!inf & !root);
+        // ---- 2. on the twist?  (a refused or identity key goes on with the generator: its lane stays with the wavefront)
+        refused |= !inf & !f2_eq<C>(f2_sqr<C>(qy), rhs);
+        const bool stand_in = inf | refused;
+        const Fp2<C> wx = f2_select<C>(stand_in, a.gen_x, qx), wy = f2_select<C>(stand_in, a.gen_y, qy);
+        // ---- 3. [r]Q = identity?  (g2_mul's loop: 256 bits of r, most significant first)
+        {
+            const G2Jac<C> Q1 = {wx, wy, f2_one<C>()};
+            const G2Jac<C> Q2 = g2j_dbl<C>(Q1);
+            G2Jac<C> T = {f2_zero<C>(), f2_zero<C>(), f2_zero<C>()};
+#pragma unroll 1
+            for (int i = 255; i >= 0; i--) {
+                T = g2j_dbl<C>(T);
+                if ((C::FrP::MOD[i >> 5] >> (i & 31)) & 1) T = g2j_add_affine<C>(T, wx, wy, Q2);
+            }
+            refused |= !f2_is_zero<C>(T.z);
+        }
+        // ---- 5. domain midstate: Z_pad || compress(pk) || suffix.  For a key that is not refused compress(pk) is the input
+        // string itself (decoding is canonical): the words of x as decoded, the sign flag recomputed from the y that was chosen
+        const bool largest = fe_is_zero<P>(qy.c1) ? kb_fe_gt_half<P>(qy.c0) : kb_fe_gt_half<P>(qy.c1);
+        Sha256 s;
+        xmd48_begin(s);
+        if constexpr (C::ID == 0) {
+            const uint32_t fl = inf ? 0xC0000000u : (0x80000000u | (largest ? 0x20000000u : 0u));
+            for (int i = NC - 1; i >= 0; i--) sha256_word(s, (inf ? 0u : w1[i]) | (i == NC - 1 ? fl : 0u));
+            for (int i = NC - 1; i >= 0; i--) sha256_word(s, inf ? 0u : w0[i]);
+        } else {
+            const uint32_t fl = inf ? 0x40000000u : (largest ? 0x80000000u : 0u);
+            for (int i = 0; i < NC; i++) sha256_word(s, kb_bswap(inf ? 0u : w0[i]));
+            for (int i = 0; i < NC; i++) sha256_word(s, kb_bswap((inf ? 0u : w1[i]) | (i == NC - 1 ? fl : 0u)));
+        }
+        sha256_bytes(s, a.suffix, a.suffix_len);
+        KeyEntry<C>& o = a.out[t];
+        o.tab.n_lines = 0;
+        o.tab.q_is_identity = 1;
+        o.tab.unit = 0;
+        o.hash = *a.hash0;
+        if (!refused) {
+            for (int k = 0; k < 8; k++) o.hash.dom_mid[k] = s.h[k];
+            o.hash.dom_mid_total = s.total - s.fill;
+            o.hash.dom_tail_len = s.fill;
+            for (int k = 0; k < 64; k++) o.hash.dom_tail[k] = (uint8_t)(s.w[k >> 2] >> ((3 - (k & 3)) * 8));
+        }
+        a.status[t] = (int8_t)(noncanon ? BBS_ST_NONCANONICAL : refused ? BBS_ST_NOT_ON_CURVE : 1);
+    }
+};
+
 #undef BBS_KB_HD
 
 // ---- job-local key sets (bbs_*_with_keys_*; job_form.hpp JobKeys) ------------------------------------------------------------
@@ -402,6 +501,20 @@ struct JobKeyGate {
             ok = t.q_is_identity != 0 || (t.unit != 0) == (a.unit != 0);
         }
         if (!ok) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
+    }
+};
+// The same gate for a job that reads the `hash` of an entry alone (proof_gen: it never pairs).  No key is refused for the form
+// of its table: the entry may have none (KeyDomainBuild), or one in either form (a slot of the job-local key cache).
+struct JobKeyStatusGateArgs {
+    size_t n;
+    const uint32_t* kidx;        // [n] key of item i, KEY_NONE: index >= n_keys
+    const int8_t* key_status;    // [n_keys] the key stage's codes
+    int8_t* status0;
+};
+struct JobKeyStatusGate {
+    static __host__ __device__ void run(const JobKeyStatusGateArgs& a, size_t i) {
+        const uint32_t k = a.kidx[i];
+        if (k == KEY_NONE || a.key_status[k] != 1) a.status0[i] = (int8_t)BBS_ST_UNKNOWN_KEY;
     }
 };
 

@@ -12,3 +12,4 @@ template int job_keys_prepare<BnCurve>(Ctx<BnCurve>*, rt::Stream&, JobKeys<BnCur
 template int job_keys_gate<BnCurve>(rt::Stream&, const JobKeys<BnCurve>&, bool, size_t, const uint32_t*, int8_t*);
 template int selftest_key_len_rows<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, int, uint8_t*, int8_t*);
 template int selftest_job_key_cache_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*, uint8_t*);
+template int selftest_key_domain_entries<BnCurve>(Ctx<BnCurve>*, size_t, const uint8_t*, uint8_t*, int8_t*);

@@ -1025,39 +1025,63 @@ class Engine:
 
     # keyed proof_gen: item i under key key_index[i] of the key set (set_public_keys / add_public_keys*); an item with an
     # unknown or refused key has status -44 and no output.  The context's single public key is not needed.
-    def core_proof_gen_keyed_submit(self, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
-        """bbs_core_proof_gen_keyed_submit; ``job.wait()`` then ``job.result`` and ``job.output()`` -> (proofs | None, statuses)."""
+    def _pg_core_keyed(self, fn, key_index, signatures, messages, disclosed_idx, random_scalars, headers, phs, tail=(), key_octets=None):
+        """The one call of the keyed core proof_gen exports and, with ``key_octets``, of their ``with_keys`` forms (n_keys and
+        pk_octets in front of key_index) -> (n, statuses, records, commitments, offsets) as the library wrote them."""
         n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)
         ki, kip = self._key_index(key_index, n)
+        own = ()
+        if key_octets is not None:
+            ko = self._key_octets(key_octets)
+            own = (len(key_octets), _u8(ko))
         total = sum(len(m) for m in messages)
         st = np.full(max(n, 1), -128, dtype=np.int8)
         pf = np.zeros(max(n, 1) * (6 * self.fpb + 128), dtype=np.uint8)
         cm = np.zeros(max(total, 1) * 32, dtype=np.uint8)
         cmo = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(getattr(self.lib, fn)(self.h, n, *own, kip, *args, _u8(pf), _u8(cm), _u64(cmo), st.ctypes.data_as(_lib.c_i8p), *tail), fn)
+        return n, st, pf, cm, cmo
+
+    def _pg_core_keyed_submit(self, fn, *a, key_octets=None) -> "Job":
         j = ctypes.c_void_p()
-        self._chk(self.lib.bbs_core_proof_gen_keyed_submit(self.h, n, kip, *args, _u8(pf), _u8(cm), _u64(cmo),
-                                                           st.ctypes.data_as(_lib.c_i8p), ctypes.byref(j)), "bbs_core_proof_gen_keyed_submit")
+        n, st, pf, cm, cmo = self._pg_core_keyed(fn, *a, tail=(ctypes.byref(j),), key_octets=key_octets)
         job = Job(self, j, n)
         job.result = st[:n]
+        job.raw = (pf, cm, cmo)
         job._decode = lambda: (self._dec_proofs(pf, cm, cmo, st, n), st[:n])
         return job
 
+    def core_proof_gen_keyed_submit(self, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
+        """bbs_core_proof_gen_keyed_submit; ``job.wait()`` then ``job.result`` and ``job.output()`` -> (proofs | None, statuses)."""
+        return self._pg_core_keyed_submit("bbs_core_proof_gen_keyed_submit", key_index, signatures, messages, disclosed_idx, random_scalars, headers, phs)
+
     def core_proof_gen_keyed_batch(self, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None):
         """bbs_core_proof_gen_keyed_batch -> (proofs | None, statuses)."""
-        n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)
-        ki, kip = self._key_index(key_index, n)
-        total = sum(len(m) for m in messages)
-        st = np.full(max(n, 1), -128, dtype=np.int8)
-        pf = np.zeros(max(n, 1) * (6 * self.fpb + 128), dtype=np.uint8)
-        cm = np.zeros(max(total, 1) * 32, dtype=np.uint8)
-        cmo = np.zeros(n + 1, dtype=np.uint64)
-        self._chk(self.lib.bbs_core_proof_gen_keyed_batch(self.h, n, kip, *args, _u8(pf), _u8(cm), _u64(cmo),
-                                                          st.ctypes.data_as(_lib.c_i8p)), "bbs_core_proof_gen_keyed_batch")
+        n, st, pf, cm, cmo = self._pg_core_keyed("bbs_core_proof_gen_keyed_batch", key_index, signatures, messages, disclosed_idx, random_scalars, headers, phs)
         return self._dec_proofs(pf, cm, cmo, st, n), st[:n]
 
-    def _pg_wire_keyed(self, fn, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers, phs, tail=()):
+    # proof_gen under a job-local key set (bbs_*proof_gen*_with_keys_*): ``key_octets`` = the distinct keys of THIS call as
+    # compressed strings, ``key_index[i]`` names one of them; the job prepares their domain midstates on the device and releases
+    # them, the engine's key set is neither read nor changed.  Statuses and bytes as the keyed twin's on an engine whose key set
+    # was registered from the same strings; Job.key_statuses() and Job.key_cache_report() answer as for the verify jobs.
+    def core_proof_gen_with_keys_submit(self, key_octets, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
+        """bbs_core_proof_gen_with_keys_submit; ``job.wait()`` then ``job.result`` and ``job.output()`` -> (proofs | None, statuses)."""
+        return self._pg_core_keyed_submit("bbs_core_proof_gen_with_keys_submit", key_index, signatures, messages, disclosed_idx, random_scalars,
+                                          headers, phs, key_octets=key_octets)
+
+    def core_proof_gen_with_keys_batch(self, key_octets, key_index, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None):
+        """bbs_core_proof_gen_with_keys_batch -> (proofs | None, statuses)."""
+        n, st, pf, cm, cmo = self._pg_core_keyed("bbs_core_proof_gen_with_keys_batch", key_index, signatures, messages, disclosed_idx, random_scalars,
+                                                 headers, phs, key_octets=key_octets)
+        return self._dec_proofs(pf, cm, cmo, st, n), st[:n]
+
+    def _pg_wire_keyed(self, fn, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers, phs, tail=(), key_octets=None):
         n = len(sig_octets)
         ki, kip = self._key_index(key_index, n)
+        own = ()
+        if key_octets is not None:
+            ko = self._key_octets(key_octets)
+            own = (len(key_octets), _u8(ko))
         ob, bad = self._sig_octets(sig_octets)
         mb, mbo, mio = self._raw_msgs(messages_raw)
         di, dio = self._indexes(disclosed_idx)
@@ -1068,7 +1092,7 @@ class Engine:
         st = np.full(max(n, 1), -128, dtype=np.int8)
         oc = np.zeros(max(cap, 1), dtype=np.uint8)
         oo = np.zeros(n + 1, dtype=np.uint64)
-        self._chk(getattr(self.lib, fn)(self.h, n, kip, _u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u64(di), _u64(dio), _u8(rs), _u64(ro),
+        self._chk(getattr(self.lib, fn)(self.h, n, *own, kip, _u8(ob), _u8(mb), _u64(mbo), _u64(mio), _u64(di), _u64(dio), _u8(rs), _u64(ro),
                                         _u8(hb), _u64(ho), _u8(pb), _u64(po), _u8(oc), _u64(oo), st.ctypes.data_as(_lib.c_i8p), *tail), fn)
 
         fix = self._wrong_length_fixup(bad)
@@ -1099,6 +1123,34 @@ class Engine:
         job._fixup = (lambda: fix(st)) if fix else None
         job._decode = decode
         return job
+
+    def proof_gen_wire_with_keys_batch(self, key_octets, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers=None, phs=None):
+        """bbs_proof_gen_wire_with_keys_batch: proof_gen_wire_keyed_batch under the key set of this call -> (proof octet strings, statuses)."""
+        n, st, fix, decode = self._pg_wire_keyed("bbs_proof_gen_wire_with_keys_batch", key_index, sig_octets, messages_raw, disclosed_idx,
+                                                 random_scalars, headers, phs, key_octets=key_octets)
+        return decode()
+
+    def proof_gen_wire_with_keys_submit(self, key_octets, key_index, sig_octets, messages_raw, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
+        """bbs_proof_gen_wire_with_keys_submit; ``job.wait()`` then ``job.output()`` -> (proof octet strings, statuses)."""
+        j = ctypes.c_void_p()
+        n, st, fix, decode = self._pg_wire_keyed("bbs_proof_gen_wire_with_keys_submit", key_index, sig_octets, messages_raw, disclosed_idx,
+                                                 random_scalars, headers, phs, (ctypes.byref(j),), key_octets=key_octets)
+        job = Job(self, j, n)
+        job.result = st[:n]
+        job._fixup = (lambda: fix(st)) if fix else None
+        job._decode = decode
+        return job
+
+    def selftest_key_domain_entries(self, key_octets):
+        """bbs_selftest_key_domain_entries -> (entries [n] of bytes, statuses): the domain-only key stage alone."""
+        n = len(key_octets)
+        eb = int(self.lib.bbs_selftest_key_entry_bytes(self.curve))
+        ko = self._key_octets(key_octets)
+        ent = np.zeros(max(n * eb, 1), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.int8)
+        self._chk(self.lib.bbs_selftest_key_domain_entries(self.h, n, _u8(ko), _u8(ent), st.ctypes.data_as(_lib.c_i8p)), "bbs_selftest_key_domain_entries")
+        b = ent.tobytes()
+        return [b[k * eb:(k + 1) * eb] for k in range(n)], st[:n]
 
     def core_proof_gen_upload(self, signatures, messages, disclosed_idx, random_scalars, headers=None, phs=None) -> "Job":
         n, keep, args = self._pg_inputs(signatures, messages, disclosed_idx, random_scalars, headers, phs)

@@ -563,8 +563,8 @@ int bbs_verify_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_inde
  * bbs_job_key_statuses: after bbs_job_wait, the per-key codes (1, BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE) in the order of
  * pk_octets, copied from the device on request (nothing is added to a run); *n_out = n_keys; BBS_E_ARG where cap < n_keys;
  * BBS_E_STATE for a job without a key set of its own.
- * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys;
- * preparing a handful of keys on the host instead (one call of the key stage costs one walk
+ * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed sign with job-local keys (proof_gen has them:
+ * bbs_*proof_gen*_with_keys_* below); preparing a handful of keys on the host instead (one call of the key stage costs one walk
  * however few keys it brings); running the key stage beside the MSM stages on a side stream; a faster subgroup test by the
  * curve endomorphism; registration through the device stage. */
 int bbs_core_proof_verify_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
@@ -647,8 +647,8 @@ int bbs_job_key_statuses(bbs_job* job, int8_t* out, size_t cap, size_t* n_out);
  * jobs counted since the context was created; device bytes of the current generation.  Any out-pointer may be NULL.
  * bbs_job_key_cache_report: hits and misses of this job (both 0 where the cache was off or the job was bypassed), *bypassed;
  * any out-pointer may be NULL; BBS_E_STATE for a job that did not come through one of the eight exports.
- * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed proof_gen and keyed sign with job-local keys; a
- * lookup on the device. */
+ * The four bbs_*proof_gen*_with_keys_* exports below go through the same generation of the cache (their own paragraph says how).
+ * NOT covered: bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; keyed sign with job-local keys; a lookup on the device. */
 int bbs_ctx_set_job_key_cache(bbs_ctx* ctx, size_t capacity_keys);
 int bbs_ctx_job_key_cache_report(bbs_ctx* ctx, size_t* capacity, size_t* resident, size_t* pinned,
                                  uint64_t* hits, uint64_t* misses, uint64_t* evictions,
@@ -669,7 +669,8 @@ int bbs_job_key_cache_report(bbs_job* job, uint32_t* hits, uint32_t* misses, int
  * bbs_ctx_set_keyed_mixed_lengths is on too.  BBS_E_ARG for a NULL key_index with n > 0, a NULL status, and -- whatever the
  * item's key -- for an item whose number of random scalars is not 5 + l_i - r_i.  Both job forms; the _submit forms return
  * ordinary jobs.  A key costs its full entry (~30 KB on BLS12-381, the W line table included) although proof_gen reads only the
- * midstate: there is no cheaper registration for proof-only keys.
+ * midstate: there is no cheaper registration for proof-only keys -- a holder-side service that meets its issuer keys next to
+ * the credentials uses the bbs_*proof_gen*_with_keys_* exports below, which register nothing.
  * NOT covered: the octets (non-wire) keyed form and an _upload form; bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim
  * do not route through these. */
 int bbs_core_proof_gen_keyed_submit(bbs_ctx* ctx, size_t n, const uint32_t* key_index, const uint8_t* signatures,
@@ -702,6 +703,70 @@ int bbs_proof_gen_wire_keyed_batch(bbs_ctx* ctx, size_t n, const uint32_t* key_i
                                    const uint8_t* headers, const uint64_t* hdr_off,
                                    const uint8_t* ph, const uint64_t* ph_off,
                                    uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status);
+/* proof_gen under issuer keys that ARRIVE WITH THE JOB: the four keyed proof_gen exports above with the key set of the call --
+ * n_keys and pk_octets in front of key_index, as the eight bbs_*verify*_with_keys_* exports take them: the DISTINCT keys of the
+ * job as compressed octets, key_index[i] names a key OF THIS CALL.  A context with no public key and no key set serves the
+ * call; the registered set is neither read nor changed; the key bytes are copied by the call.
+ * The job prepares its keys on the device as its own first work, on its main stream in front of its ingest kernel.  proof_gen
+ * meets the key in the domain alone, so these jobs run a DOMAIN-ONLY key stage: one lane per key decodes the string, tests the
+ * twist and [r]Q and hashes the domain midstate -- no Miller-loop line table, no workspace, no field inversion.  Per key the job
+ * holds the entry, a status byte and, under bbs_ctx_set_keyed_mixed_lengths, (L + 1) prefixes of 368 bytes (counted by
+ * bbs_job_device_bytes); the entry has the layout of a registered key's with an empty table.  The keys are prepared with the
+ * upload, once: bbs_job_run on the same job gives the same bytes.
+ * STATUS RULE: status AND output bytes are, bit for bit, those of the keyed twin (bbs_*proof_gen*_keyed_*) on a context with the
+ * same generators, api_id, window bits, switches and random scalars or seeds whose key set was built by
+ * bbs_ctx_add_public_keys_octets(pk_octets), given the same key_index and items.  So an index >= n_keys, or a string
+ * registration would refuse (BBS_ST_NONCANONICAL, BBS_ST_NOT_ON_CURVE), gives BBS_ST_UNKNOWN_KEY whatever the other checks
+ * decided, and no output (zero record, no octet string); the identity encoding is an accepted key.  The line form of the
+ * context does not matter: no key is refused for the form of a table proof_gen never reads (the fail-closed case of the verify
+ * exports does not exist here).
+ * Errors: those of the keyed twin -- BBS_E_ARG for a NULL key_index with n > 0, a NULL status, a wrong number of random
+ * scalars; BBS_E_STATE without generators, or with bbs_ctx_set_mixed_lengths_gen on and bbs_ctx_set_keyed_mixed_lengths off --
+ * and BBS_E_ARG for a NULL pk_octets with n_keys > 0 or n_keys > 0xFFFFFFF0.  A missing key set is no error here.
+ * Composition: both job forms, bbs_ctx_set_keyed_mixed_lengths (per-item counts; the prefixes per (key, length) are hashed by
+ * the stage the verify jobs use), bbs_ctx_set_seeded_random_scalars with per-item seeds or a job seed.
+ * bbs_job_key_statuses and bbs_job_key_cache_report answer as for the verify jobs.
+ * THE JOB-LOCAL KEY CACHE (bbs_ctx_set_job_key_cache) serves these jobs from the same generation as the verify jobs: same
+ * lookup, pins, eviction, bypass and counters.  Hits read the slot's midstate and prefixes, waiting on the device for a slot
+ * another job is still publishing.  The MISSES of a cached proof_gen job are prepared by the FULL key stage, line table
+ * included, not by the domain-only stage: a slot is whole whoever published it, and a later bbs_*verify*_with_keys_* job may hit
+ * it.  The uncached path -- cache off, or the job bypassed -- uses the domain-only stage.
+ * NOT covered: sign with job-local keys; bbs_issuer, bbs_pool, the C++ wrapper and the Rust shim; preparing a handful of keys
+ * on the host; the subgroup test by the curve endomorphism, which would now shorten both key stages. */
+int bbs_core_proof_gen_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                        const uint32_t* key_index, const uint8_t* signatures,
+                                        const uint8_t* messages, const uint64_t* msg_off,
+                                        const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                        const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                        const uint8_t* headers, const uint64_t* hdr_off,
+                                        const uint8_t* ph, const uint64_t* ph_off,
+                                        uint8_t* proofs_fixed_out, uint8_t* commitments_out,
+                                        uint64_t* commit_off_out, int8_t* status, bbs_job** job_out);
+int bbs_core_proof_gen_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                       const uint32_t* key_index, const uint8_t* signatures,
+                                       const uint8_t* messages, const uint64_t* msg_off,
+                                       const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                       const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                       const uint8_t* headers, const uint64_t* hdr_off,
+                                       const uint8_t* ph, const uint64_t* ph_off,
+                                       uint8_t* proofs_fixed_out, uint8_t* commitments_out,
+                                       uint64_t* commit_off_out, int8_t* status);
+int bbs_proof_gen_wire_with_keys_submit(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                        const uint32_t* key_index, const uint8_t* signature_octets,
+                                        const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                        const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                        const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                        const uint8_t* headers, const uint64_t* hdr_off,
+                                        const uint8_t* ph, const uint64_t* ph_off,
+                                        uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status, bbs_job** job_out);
+int bbs_proof_gen_wire_with_keys_batch(bbs_ctx* ctx, size_t n, size_t n_keys, const uint8_t* pk_octets,
+                                       const uint32_t* key_index, const uint8_t* signature_octets,
+                                       const uint8_t* msg_bytes, const uint64_t* msg_byte_off, const uint64_t* msg_item_off,
+                                       const uint64_t* disclosed_idx, const uint64_t* didx_off,
+                                       const uint8_t* random_scalars, const uint64_t* rnd_off,
+                                       const uint8_t* headers, const uint64_t* hdr_off,
+                                       const uint8_t* ph, const uint64_t* ph_off,
+                                       uint8_t* octets_out, uint64_t* oct_off_out, int8_t* status);
 
 /* Keyed sign: ONE context signs under MANY issuer secret keys.  The reference takes the key per call (src/sign.rs:63, &self), so
  * per-item keys are its semantics.
@@ -1141,6 +1206,10 @@ int bbs_selftest_key_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_affine, c
                              const uint8_t* pk_octets, int path, uint8_t* entries_out, int8_t* status_out,
                              uint8_t* pk_affine_out);
 size_t bbs_selftest_key_entry_bytes(int curve);
+/* The domain-only key stage of the bbs_*proof_gen*_with_keys_* jobs alone: the entries and statuses of n strings, read back from
+ * the device.  The `hash` part and the status are those of bbs_selftest_key_entries for the same string; the table part is that
+ * of a key without a table (no lines, the identity flag set, entries zero).  Needs the generators; does not touch the key set. */
+int bbs_selftest_key_domain_entries(bbs_ctx* ctx, size_t n, const uint8_t* pk_octets, uint8_t* entries_out, int8_t* status_out);
 /* The prefixes per (key, length) of n keys given as octets (bbs_ctx_set_keyed_mixed_lengths), by two implementations; the caller
  * compares the outputs.  path 0: the host functions registration uses; path 1: the device stages a job with a job-local key
  * set runs (the key stage, then one lane per (key, length)).  rows_out: n x (L + 1) x bbs_selftest_hash_ctx_bytes() bytes, rows of
